@@ -14,10 +14,15 @@ region is the whole library once.  Profiles' device images and the targets are r
          bench.py --gpus N --steps K --warmup W            # one rank per GPU, strong scaling (the same 500,000 targets sharded)
 
 Rank 0 prints ONE JSON line.  `value` is whole-job GCUPS: sum over the profiles searched of M x residues of all targets,
-divided by the max-over-ranks wall time (all-pairs M*L denominator, as the HMMER literature does).  The other BASELINE configs
-are fields of the same line: `config1` (one profile x 1,000,000 targets: throughput of a stream of queries, and the latency of
-ONE query on an idle device), `scan` (hmmscan orientation, 4,000-protein block), `nhmmer` (250 Mbp chromosome).
-`--workload config1 | scan | nhmmer` prints that workload as the line instead.
+divided by the max-over-ranks wall time (all-pairs M*L denominator, as the HMMER literature does); `ms_per_step` is the
+timed region over --steps.  A plain run measures that line and nothing else.  With `--full` the other BASELINE configs are
+fields of the same line: `config1` (one profile x 1,000,000 targets: throughput of a stream of queries, and the latency of
+ONE query on an idle device), `scan` (hmmscan orientation, 4,000-protein block), `nhmmer` (250 Mbp chromosome), and every
+workload adds its cpu_baseline.  `--workload config1 | scan | nhmmer` prints that workload as the line instead.
+`--dump-outputs DIR` writes the hit lists of the last timed step as .npy files (dump_outputs); the inputs are seeded, so
+two builds can be compared output for output.
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import json
@@ -37,6 +42,9 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))     # oracle_lib, for the cpu_baseline legs only (after the timed regions)
 
+METRIC = "GCUPS (DP cells/s) + seqs/s for hmmsearch, Pfam-A vs proteome, 1/2/4/8 GPUs"
+DTYPE = "u8/i16 filters (MSV, Viterbi), f32 Forward/Backward"
+DUMP_BYTES_MAX = 63 << 20        # --dump-outputs: array data at most (the files, headers included, stay within 64 MB)
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_LANE_OPS_PER_S = 256 * 4 * 16 * 2.4e9    # 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz: packed-16 VOP3P ops take 4 cycles per
                                               # wave64 (PMC: SQ_ACTIVE_INST_VALU == SQ_INSTS_VALU quad-cycles, profiles/r01_bench_pmc.md)
@@ -336,6 +344,46 @@ def cpu_baseline(hmm, bg, flat, offsets, lengths, n, L_hint):
     }
 
 
+def dump_outputs(outdir, hits, queries):
+    """--dump-outputs: what the last timed step handed its caller, one TopHits per query, as columns DIR/<table>_<column>.npy
+    of three tables: one row per query (`query_*`, `query_index` = the profile's index in the library), per hit (`hit_*`)
+    and per domain (`domain_*`), in the order hmmsearch returned them.  Scores are float32 as the library keeps them,
+    everything else float64.  Past DUMP_BYTES_MAX in all, every table keeps a fixed, seeded sample of its rows."""
+    single = {"score", "pre_score", "sum_score", "nexpected", "bias", "correction", "envelope_score", "accuracy"}
+    rows = {"query": [], "hit": [], "domain": []}
+    for e, th in zip(queries, hits):
+        sc = th.stage_counts
+        hs = list(th)
+        rows["query"].append({"index": e, "hits": len(hs), "reported": sum(h.reported for h in hs), "included": sum(h.included for h in hs),
+                              "past_msv": sc["msv"], "past_bias": sc["bias"], "past_vit": sc["vit"], "past_fwd": sc["fwd"],
+                              "Z": th.Z, "domZ": th.domZ})
+        for h in hs:
+            ds = list(h.domains)
+            rows["hit"].append({"query": e, "target": h.seqidx, "score": h.score, "pre_score": h.pre_score, "sum_score": h.sum_score,
+                                "evalue": h.evalue, "nexpected": h.nexpected, "nregions": h.nregions, "nclustered": h.nclustered,
+                                "noverlaps": h.noverlaps, "nenvelopes": h.nenvelopes, "ndomains": len(ds),
+                                "reported": h.reported, "included": h.included})
+            for d in ds:
+                a = d.alignment
+                rows["domain"].append({"query": e, "target": h.seqidx, "env_from": d.env_from, "env_to": d.env_to,
+                                       "hmm_from": a.hmm_from, "hmm_to": a.hmm_to, "target_from": a.target_from, "target_to": a.target_to,
+                                       "score": d.score, "bias": d.bias, "correction": d.correction, "envelope_score": d.envelope_score,
+                                       "accuracy": d.accuracy, "c_evalue": d.c_evalue, "i_evalue": d.i_evalue,
+                                       "reported": d.reported, "included": d.included})
+    tables = {}
+    for name, rs in rows.items():
+        cols = list(rs[0]) if rs else []
+        tables[name] = {c: np.array([r[c] for r in rs], dtype=np.float32 if c in single else np.float64) for c in cols}
+    total = sum(a.nbytes for t in tables.values() for a in t.values())
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in tables.items():
+        for c, a in t.items():
+            if total > DUMP_BYTES_MAX:
+                keep = np.sort(np.random.default_rng(0).choice(len(a), int(len(a) * DUMP_BYTES_MAX / total), replace=False))
+                a = a[keep]
+            np.save(Path(outdir) / f"{name}_{c}.npy", a)
+
+
 def shard_bounds(lengths, world):
     """Residue-balanced contiguous target shards (hmmer.make_chunks / _hmmsearch.py:153-171 on the packed arrays)."""
     csum = np.cumsum(lengths.astype(np.int64))
@@ -386,7 +434,7 @@ def run_pfam(args, rank, world, local_rank, dist, red_dev, torch, host_threads, 
     hmms, lib_lengths, templates, bg, oms = lib["hmms"], lib["lengths"], lib["templates"], lib["bg"], lib["oms"]
     t0 = time.perf_counter()
     frac = min(0.5, 12.5 * len(hmms) / args.pfam_targets)
-    flat, offsets, lengths, nplanted = bw.make_targets(args.pfam_targets, len(hmms), templates, lib_lengths, planted_frac=frac)
+    flat, offsets, lengths, nplanted = bw.make_targets(args.pfam_targets, len(hmms), templates, lib_lengths, planted_frac=frac, entries=hmms)
     cuts = shard_bounds(lengths, world)
     lo, hi = cuts[rank], cuts[rank + 1]
     db = plan7.SequenceDatabase.from_packed(hmms[0].alphabet, flat, offsets[lo:hi], lengths[lo:hi], device=local_rank)
@@ -406,7 +454,22 @@ def run_pfam(args, rank, world, local_rank, dist, red_dev, torch, host_threads, 
     step_profiles = lambda first, n: [(first * pps + i) % len(oms) for i in range(n * pps)]
     timed_idx = step_profiles(0, args.steps)
     t0 = time.perf_counter()
-    search(oms)                     # untimed: device images of every profile become resident; pools, clocks and workers settle
+    if args.full:
+        search(oms)                 # untimed: device images of every profile become resident; pools, clocks and workers settle
+        residency = "the whole library against all targets (the cold library search)"
+    else:
+        # a plain run: the images are made by one search of the whole library against a block of this rank's targets the size
+        # of a proteome (they stay with the profiles, whatever those are searched against next); the warm-up steps settle
+        # pools, clocks and workers on the real block -- without any, one step before the warm-up's does
+        nfew = min(hi - lo, 2000)
+        few = plan7.SequenceDatabase.from_packed(hmms[0].alphabet, flat, offsets[lo:lo + nfew], lengths[lo:lo + nfew], device=local_rank)
+        for _ in hmmer.hmmsearch(oms, few, cpus=host_threads):
+            pass
+        del few
+        residency = f"the whole library against {nfew} targets"
+        if args.warmup <= 0:
+            search([oms[e] for e in step_profiles(-1, 1)])
+            residency += ", then one step against all of them"
     t_resident = time.perf_counter() - t0
     if args.warmup > 0:
         search([oms[e] for e in step_profiles(-args.warmup, args.warmup)])
@@ -437,6 +500,8 @@ def run_pfam(args, rank, world, local_rank, dist, red_dev, torch, host_threads, 
         t_max = float(b.item())
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, merged[-pps:], timed_idx[-pps:])
     nodes = float(sum(hmms[e].M for e in timed_idx))
     nprof = len(timed_idx)
     residues = float(lengths.sum())
@@ -455,7 +520,7 @@ def run_pfam(args, rank, world, local_rank, dist, red_dev, torch, host_threads, 
         "mean_M": round(nodes / nprof, 1), "mean_L": round(residues / len(lengths), 1),
         "seconds": round(t_max, 4), "ms_per_profile": round(1e3 * t_max / nprof, 4), "profiles_per_s": round(nprof / t_max, 1),
         "seqs_per_s": round(float(nprof) * len(lengths) / t_max, 1),
-        "untimed_residency_pass_seconds": round(t_resident, 2),
+        "untimed_residency_pass_seconds": round(t_resident, 2), "residency_pass": residency,
         "search_seconds_rank0": round(t_search, 4),
         "merge_seconds_rank0": {"serialise": round(t_ser, 4), "gather": round(t_gather, 4), "merge_many": round(t_merge, 4)},
         "batch": args.pfam_batch, **pipe_effective(args.pfam_depth, args.feeders, args.pfam_finishers, many=True),
@@ -662,9 +727,9 @@ def main():
                     help="headline workload through the API's own multi-device path: ONE process, hmmer.hmmsearch over this many devices "
                          "(a block of --nseq targets resident on each; P7X_BENCH_SHARE_DEVICE=1: all on this rank's device, a rehearsal) -- "
                          "next to the process-per-GPU path of --gpus N")
-    ap.add_argument("--workload", choices=("all", "config1", "pfam", "scan", "nhmmer"), default="all",
-                    help="all (default): the line is the pfam workload (BASELINE's metric config, configs[3]) with --steps / --warmup, "
-                         "and config1 / scan / nhmmer are fields; pfam / scan / nhmmer: only that workload; config1: the line is "
+    ap.add_argument("--workload", choices=("all", "config1", "pfam", "scan", "nhmmer"), default=None,
+                    help="pfam (the default): the line alone, BASELINE's metric config (configs[3]) with --steps / --warmup; all (the default with --full): "
+                         "the same line with config1 / scan / nhmmer as fields; scan / nhmmer: only that workload; config1: the line is "
                          "configs[1] (one profile x 1M targets per GPU, a step = --queries-per-step searches) with --steps / --warmup")
     for f in ("F1", "F2", "F3"):
         ap.add_argument(f"--{f}", type=float, default=None, help="diagnostics (pfam workload): filter threshold, e.g. --F1 1e-12 = the MSV stage alone")
@@ -682,7 +747,19 @@ def main():
     ap.add_argument("--pfam-batch", type=int, default=0, help="queries per device batch (0: the library's choice)")
     ap.add_argument("--pfam-depth", type=int, default=None, help="A/B, many-profile workload (default: the library's own)")
     ap.add_argument("--pfam-finishers", type=int, default=None, help="A/B, many-profile workload (default: the library's own)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the line: the default workload becomes `all` (the configs[1], scan and nhmmer fields), and the "
+                         "CPU baselines run (--no-cpu-baseline drops them).  Without it a run sets up, warms up, times the line's steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region: the hit lists of the pfam line's last timed step as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.workload is None:
+        args.workload = "all" if args.full else "pfam"
+    if not args.full:
+        args.no_cpu_baseline = True                        # the CPU legs belong to --full
+    if args.dump_outputs and args.workload not in ("all", "pfam"):
+        raise SystemExit("--dump-outputs writes the outputs of the pfam line (--workload all or pfam)")
     line_steps, line_warmup = args.steps, args.warmup      # the driver's K and W belong to the line's workload
     c1_cpu = not args.no_cpu_baseline
     if args.workload != "config1":
@@ -720,6 +797,79 @@ def main():
     for item in args.debug_option:          # after torch: the library must bind to the HIP runtime torch has loaded
         name, _, value = item.partition("=")
         _lib.set_debug_option(name, int(value or 1))
+    # the ranks of one node share its CPUs: split them instead of letting every rank start a full-size worker pool
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    host_threads = max(2, host_cpus() // max(1, local_world))
+
+    c1 = None
+    if args.workload != "pfam":          # the line of --workload config1, a field of all, a token run ahead of scan / nhmmer
+        c1 = run_config1(args, rank, world, local_rank, dist, red_dev, torch, host_threads, lib, rehearsal, c1_cpu)
+
+    pfam = scan = None
+    c1_steps, c1_warmup = args.steps, args.warmup
+    if args.workload in ("all", "pfam", "scan"):
+        library = build_library(args, local_rank)
+        if args.workload in ("all", "pfam"):
+            args.steps, args.warmup = line_steps, line_warmup
+            pfam = run_pfam(args, rank, world, local_rank, dist, red_dev, torch, host_threads, library)
+            args.steps, args.warmup = c1_steps, c1_warmup
+        if args.workload in ("all", "scan"):
+            scan = run_scan(args, rank, world, local_rank, dist, red_dev, torch, host_threads, library, "synthetic")
+            fx = run_scan(args, rank, world, local_rank, dist, red_dev, torch, host_threads, library, "fixture")
+            if scan is not None:
+                scan["fixture_proteome"] = {k: fx[k] for k in ("workload", "value", "seconds", "query_sequences", "passes_seconds_rank0", "hits_rank0", "roofline")}
+        del library
+    nh = None
+    if args.workload in ("all", "nhmmer"):
+        nh = run_nhmmer(args, rank, world, local_rank, dist, red_dev, torch)
+
+    if rank == 0:
+        out = c1
+        if args.workload in ("all", "pfam") and pfam is not None:
+            # the line is BASELINE's metric config (configs[3]); configs[1], the scan orientation and nhmmer are fields
+            first = {"metric": METRIC, "value": pfam["value"], "unit": "GCUPS", "n_gpus": world,
+                     "steps": line_steps, "warmup": line_warmup, "ms_per_step": round(1e3 * pfam["seconds"] / max(1, line_steps), 3),
+                     "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+                     "seqs_per_s": pfam["seqs_per_s"],
+                     "config": {"workload": pfam["workload"],
+                                "step": f"{pfam['profiles_per_step']} library profiles x all {pfam['targets']} targets (complete searches, hit lists merged)",
+                                "profiles_per_step": pfam["profiles_per_step"], "targets": pfam["targets"], "library": pfam["library"],
+                                "parallelism": f"targets sharded by residues over {world} GPU(s), one process each, host merge of the per-GPU TopHits",
+                                "timed_region": "one hmmer.hmmsearch call over the steps' profiles + gather + merge, barrier and synchronize on both "
+                                                "sides; device images of the profiles and the targets resident in HBM (untimed: pfam.residency_pass); "
+                                                "library defaults", **{k: pfam[k] for k in ("batch", "pipeline_depth", "feeders", "finishers", "library_defaults")}},
+                     "roofline": pfam.pop("roofline"), "cpu_baseline": pfam.pop("cpu_baseline", None),
+                     "pfam": pfam}
+            if args.workload == "all":
+                first["config1"] = c1
+            if scan is not None:
+                first["scan"] = scan
+            if nh is not None:
+                first["nhmmer"] = nh
+            out = first
+        elif args.workload in ("scan", "nhmmer"):
+            sub = scan if args.workload == "scan" else nh
+            # --workload scan / nhmmer: that workload IS the line (value, config, roofline, cpu_baseline)
+            secs = sub.get("seconds", sub.get("s_per_search", 0.0) * sub.get("searches", 1))
+            out = {"metric": METRIC, "value": sub["value"], "unit": "GCUPS", "n_gpus": world,
+                   "steps": sub.get("searches", 1), "warmup": 1, "ms_per_step": round(1e3 * secs / max(1, sub.get("searches", 1)), 3),
+                   "higher_is_better": True, "scaling": sub.get("scaling", "weak"), "vs_baseline": None,
+                   "dtype": DTYPE if args.workload != "nhmmer" else "i16 SSV scan and window filters, f32 Forward/Backward",
+                   "data": "synthetic",
+                   "config": {"workload": sub["workload"], "step": "one pass over the whole workload after one untimed pass"
+                              if args.workload != "nhmmer" else "one complete search of a stream of searches",
+                              "parallelism": f"{world} GPU(s), one process each"},
+                   "roofline": sub.get("roofline"), "cpu_baseline": sub.get("cpu_baseline"), args.workload: sub}
+        print(json.dumps(out))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def run_config1(args, rank, world, local_rank, dist, red_dev, torch, host_threads, lib, rehearsal, c1_cpu):
+    """BASELINE configs[1]: one profile (fixture --hmm, KR) against --nseq synthetic targets per GPU, a step = --queries-per-step
+    complete searches of the same query through hmmer.hmmsearch, after an untimed spin-up; then ONE query alone on the device
+    (the stand-alone kernel times of the roofline).  Rank 0 returns the configs[1] line, the other ranks None."""
+    from pyhmmer_amd import hmmer, plan7
     with plan7.HMMFile(ROOT / "tests" / "golden" / "hmms" / f"{args.hmm}.hmm") as hf:      # fixture data, not test code
         hmm = next(iter(hf))
     bg = plan7.Background(hmm.alphabet)
@@ -746,11 +896,6 @@ def main():
             parts.append(plan7.SequenceDatabase.from_packed(hmm.alphabet, f2, o2, l2, device=ids[k]))
             extra_res += int(l2.sum())
         db = _hm.ShardedDatabase.from_databases(parts)
-
-    from pyhmmer_amd import hmmer
-    # the ranks of one node share its CPUs: split them instead of letting every rank start a full-size worker pool
-    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
-    host_threads = max(2, host_cpus() // max(1, local_world))
 
     qps = max(1, args.queries_per_step)
     pli_opts = {} if args.oa_guard is None else {"oa_guard": args.oa_guard}
@@ -859,27 +1004,6 @@ def main():
     if dist is None:
         hits_total, reported_total = len(hits), len(hits.reported)
 
-    pfam = scan = None
-    c1_steps, c1_warmup = args.steps, args.warmup
-    if args.workload in ("all", "pfam", "scan"):
-        del db                       # the configs[1] target block leaves HBM first
-        lib = build_library(args, local_rank)
-        if args.workload in ("all", "pfam"):
-            args.steps, args.warmup = line_steps, line_warmup
-            pfam = run_pfam(args, rank, world, local_rank, dist, red_dev, torch, host_threads, lib)
-            args.steps, args.warmup = c1_steps, c1_warmup
-        if args.workload in ("all", "scan"):
-            scan = run_scan(args, rank, world, local_rank, dist, red_dev, torch, host_threads, lib, "synthetic")
-            fx = run_scan(args, rank, world, local_rank, dist, red_dev, torch, host_threads, lib, "fixture")
-            if scan is not None:
-                scan["fixture_proteome"] = {k: fx[k] for k in ("workload", "value", "seconds", "query_sequences", "passes_seconds_rank0", "hits_rank0", "roofline")}
-        del lib
-    nh = None
-    if args.workload in ("all", "nhmmer"):
-        if args.workload == "nhmmer":
-            del db
-        nh = run_nhmmer(args, rank, world, local_rank, dist, red_dev, torch)
-
     if rank == 0:
         ms_per_step = 1e3 * t_max / args.steps
         gcups = cells_total * nqueries / t_max / 1e9
@@ -896,11 +1020,11 @@ def main():
         om_R = (hmm.M + 1) // 2 + 1
         om_R = ((om_R + 3) // 4) * 4 if om_R <= 160 else ((om_R + 15) // 16) * 16
         out = {
-            "metric": "GCUPS (DP cells/s) + seqs/s for hmmsearch, Pfam-A vs proteome, 1/2/4/8 GPUs",
+            "metric": METRIC,
             "value": round(gcups, 2), "unit": "GCUPS",
             "n_gpus": world * max(1, inproc), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8/i16 filters (MSV, Viterbi), f32 Forward/Backward",
+            "dtype": DTYPE,
             "data": "synthetic",
             "seqs_per_s": round(seqs_total * nqueries / t_max, 1),
             "ms_per_query": round(1e3 * t_max / nqueries, 3),
@@ -966,53 +1090,10 @@ def main():
                 "pipeline": pipeline_valu_budget(hmm, args, sc, B, 1e3 * t_max / nqueries * B),
             },
         }
-        if pfam is not None:
-            out["pfam"] = pfam
-        if scan is not None:
-            out["scan"] = scan
-        if nh is not None:
-            out["nhmmer"] = nh
         if world == 1 and c1_cpu:
             out["cpu_baseline"] = cpu_baseline(hmm, bg, flat, offsets, lengths, min(args.cpu_sample, args.nseq), args.seqlen)
-        if args.workload in ("all", "pfam") and pfam is not None:
-            # the line is BASELINE's metric config (configs[3]); configs[1], the scan orientation and nhmmer are fields
-            first = {"metric": out["metric"], "value": pfam["value"], "unit": "GCUPS", "n_gpus": world,
-                     "steps": line_steps, "warmup": line_warmup, "ms_per_step": round(1e3 * pfam["seconds"] / max(1, line_steps), 3),
-                     "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": out["dtype"], "data": "synthetic",
-                     "seqs_per_s": pfam["seqs_per_s"],
-                     "config": {"workload": pfam["workload"],
-                                "step": f"{pfam['profiles_per_step']} library profiles x all {pfam['targets']} targets (complete searches, hit lists merged)",
-                                "profiles_per_step": pfam["profiles_per_step"], "targets": pfam["targets"], "library": pfam["library"],
-                                "parallelism": f"targets sharded by residues over {world} GPU(s), one process each, host merge of the per-GPU TopHits",
-                                "timed_region": "one hmmer.hmmsearch call over the steps' profiles + gather + merge, barrier and synchronize on both "
-                                                "sides; device images of the profiles and the targets resident in HBM (an untimed pass over the whole "
-                                                "library first); library defaults", **{k: pfam[k] for k in ("batch", "pipeline_depth", "feeders", "finishers", "library_defaults")}},
-                     "roofline": pfam.pop("roofline"), "cpu_baseline": pfam.pop("cpu_baseline", None),
-                     "pfam": pfam}
-            if args.workload == "all":
-                first["config1"] = out
-            if scan is not None:
-                first["scan"] = out.pop("scan", scan)
-            if nh is not None:
-                first["nhmmer"] = out.pop("nhmmer", nh)
-            out.pop("pfam", None)
-            out = first
-        elif args.workload in ("scan", "nhmmer"):
-            sub = scan if args.workload == "scan" else nh
-            # --workload scan / nhmmer: that workload IS the line (value, config, roofline, cpu_baseline)
-            secs = sub.get("seconds", sub.get("s_per_search", 0.0) * sub.get("searches", 1))
-            out = {"metric": out["metric"], "value": sub["value"], "unit": "GCUPS", "n_gpus": world,
-                   "steps": sub.get("searches", 1), "warmup": 1, "ms_per_step": round(1e3 * secs / max(1, sub.get("searches", 1)), 3),
-                   "higher_is_better": True, "scaling": sub.get("scaling", "weak"), "vs_baseline": None,
-                   "dtype": out["dtype"] if args.workload != "nhmmer" else "i16 SSV scan and window filters, f32 Forward/Backward",
-                   "data": "synthetic",
-                   "config": {"workload": sub["workload"], "step": "one pass over the whole workload after one untimed pass"
-                              if args.workload != "nhmmer" else "one complete search of a stream of searches",
-                              "parallelism": f"{world} GPU(s), one process each"},
-                   "roofline": sub.get("roofline"), "cpu_baseline": sub.get("cpu_baseline"), args.workload: sub}
-        print(json.dumps(out))
-    if dist is not None:
-        dist.destroy_process_group()
+        return out
+    return None
 
 
 if __name__ == "__main__":

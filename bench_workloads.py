@@ -136,11 +136,13 @@ def make_library(n, device=0, seed=43, count=None):
     return [cal.calibrate(make_entry(templates, e, int(lengths[e]), seed)) for e in range(count)], lengths, templates
 
 
-def make_targets(nseq, library_size, templates, lib_lengths, seed=44, planted_frac=0.5, lib_seed=43):
+def make_targets(nseq, library_size, templates, lib_lengths, seed=44, planted_frac=0.5, lib_seed=43, entries=None):
     """Flat arrays in the C-ABI's input format (255 x1..xL 255 ...), lengths lognormal, a fraction `planted_frac` of the
     targets carrying one domain sampled from the match emissions of a random entry among the first `library_size`
     of the library.  (A Pfam-like hit density is ~12 targets per family: planted_frac = 12.5 * library_size / nseq;
-    a run over the first few thousand entries plants only their domains -- the others' would be background to it.)"""
+    a run over the first few thousand entries plants only their domains -- the others' would be background to it.)
+    `entries`: the library's models if they are built already (make_library with lib_seed): entry e is entries[e] instead
+    of a second make_entry (calibration leaves the match emissions alone, so the targets are the same)."""
     from pyhmmer_amd import plan7
     rng = np.random.default_rng(seed)
     abc = templates[0].alphabet
@@ -164,7 +166,7 @@ def make_targets(nseq, library_size, templates, lib_lengths, seed=44, planted_fr
     nplanted = 0
     for a, b in zip(bounds[:-1], bounds[1:]):
         e = int(entry[a])
-        hmm = make_entry(templates, e, int(lib_lengths[e]), lib_seed)
+        hmm = entries[e] if entries is not None and e < len(entries) else make_entry(templates, e, int(lib_lengths[e]), lib_seed)
         cm = np.cumsum(hmm.match_emissions[1:].astype(np.float64), axis=1)
         cm /= cm[:, -1:]
         for tgt in planted[a:b]:

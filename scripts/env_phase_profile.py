@@ -10,7 +10,7 @@ sys.path.insert(0, ROOT)
 import bench
 from pyhmmer_amd import _lib
 
-sys.argv = ["bench.py", "--workload", "config1", "--steps", "2", "--warmup", "1"] + sys.argv[1:]
+sys.argv = ["bench.py", "--workload", "config1", "--steps", "2", "--warmup", "1", "--full"] + sys.argv[1:]
 bench.main()
 out = (C.c_ulonglong * 8)()
 fn = _lib.lib().p7x_debug_env_profile

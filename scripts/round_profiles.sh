@@ -9,7 +9,7 @@ OUT=${1:-gpurun_out/round}; B=${2:-7}
 O=$R/$OUT; mkdir -p $O; cd $R
 ( timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -5 ) > $O/tests.log
 ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ) > $O/smoke.log
-for i in 1 2; do timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_run$i.json 2> $O/bench_run$i.err; done
+for i in 1 2; do timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_run$i.json 2> $O/bench_run$i.err; done
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --workload config1 --no-cpu-baseline > $O/bench_traced.json 2> $O/bench_traced.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_alone -o alone -- python $R/scripts/config1_phases.py $B 4 > $O/alone.log 2>&1
