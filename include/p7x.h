@@ -451,6 +451,57 @@ int      p7x_tophits_get_guard_counts(const p7x_tophits *th, int64_t *f3_dropped
  * threshold and was repeated by the host stage on parser rows in upstream's order (active with oa_guard > 0) */
 int      p7x_tophits_get_ensemble_counts(const p7x_tophits *th, int64_t *sampled_on_device, int64_t *redone_by_host, int64_t *region_scans_redone);
 
+/* ------------------------------------------------------------------ hmmalign
+ * Traces of whole sequences against one profile (TraceAligner.compute_traces, plan7.pyx:9773-9830, upstream
+ * p7_tracealign_computeTraces): the profile unihit local with each sequence's own length model; Forward, Backward,
+ * posterior decoding, optimal accuracy and its traceback over the whole sequence.  On the device (p7x_align.hip) unless
+ * the test seam "host_align" = 1 asks for the host twin; device traces with a near-tie on the trace or a posterior digit
+ * within the guard band are repeated by the host twin in upstream's order.  Input: the packed block of
+ * p7x_seqdb_create.  P7X_ENODEVICE without a device (and without the seam); P7X_ERANGE when posterior decoding
+ * overflows on a sequence (upstream's generic-DP fallback is not implemented; p7x_last_error names the sequence);
+ * P7X_EMEM when one sequence alone does not fit the workspace budget ("align_workspace_gb").  host_threads: workers of
+ * the host twin (hmmalign's cpus; 0: the library's default). */
+typedef struct p7x_traces p7x_traces;
+enum { P7X_TRACE_HAS_PP = 1, P7X_TRACE_DEVICE = 2 };          /* p7x_traces_get origin bits */
+int     p7x_tracealign_compute(const p7x_oprofile *om, int device, const uint8_t *dsq, const int64_t *offsets,
+                               const int32_t *lengths, size_t n, int host_threads, p7x_traces **out);
+/* Trace accessors (Traces.__getitem__, Trace.M / L / posterior_probabilities, plan7.pyx:9280-9540): N steps in forward
+ * order (P7_TRACE st / k / i / pp), sc2 = Forward score and optimal-accuracy score (nats), the device's status word (0
+ * for host-twin traces), origin bits.  copy: st[N] k[N] i[N] pp[N], any of them NULL. */
+int64_t p7x_traces_count(const p7x_traces *tr);
+int64_t p7x_traces_nflagged(const p7x_traces *tr);           /* device traces the host twin repeated */
+/* out4: traces kept from the device, device traces the host twin repeated, device rounds, the largest device workspace
+ * (bytes) a round laid out -- at most the budget ("align_workspace_gb") */
+int     p7x_traces_stats(const p7x_traces *tr, int64_t out4[4]);
+int     p7x_traces_get(const p7x_traces *tr, int64_t idx, int32_t *N, int32_t *M, int32_t *L, float *sc2, int32_t *status, uint8_t *origin);
+int     p7x_traces_copy(const p7x_traces *tr, int64_t idx, int8_t *st, int32_t *k, int32_t *i, float *pp);
+void    p7x_traces_destroy(p7x_traces *tr);
+
+/* The multiple alignment of traces (TraceAligner.align_traces, plan7.pyx:9832-9925, upstream p7_tracealign_Seqs):
+ * traces concatenated (toff[n + 1]), origin[n] as above (P7X_TRACE_HAS_PP: the row gets a PP line; with om != NULL a
+ * PP_cons column within the guard of a digit boundary is averaged again over host-twin posteriors of its P7X_TRACE_DEVICE
+ * rows), sequences as for p7x_tracealign_compute, cs = the model's CS line [M+2] or NULL (-> SS_cons).  Rows in text
+ * form; P7X_MSA_DIGITIZE is the caller's (easel.DigitalMSA). */
+enum { P7X_MSA_TRIM = 1, P7X_MSA_ALL_CONSENSUS_COLS = 2, P7X_MSA_DIGITIZE = 4 };     /* p7_TRIM, p7_ALL_CONSENSUS_COLS, p7_DIGITIZE */
+typedef struct p7x_msa p7x_msa;
+int     p7x_msa_from_traces(int32_t M, size_t n, const int8_t *st, const int32_t *k, const int32_t *i, const float *pp,
+                            const int64_t *toff, const uint8_t *origin, const uint8_t *dsq, const int64_t *offsets,
+                            const int32_t *lengths, int32_t abc_type, const char *cs, int flags, const p7x_oprofile *om,
+                            p7x_msa **out);
+int64_t p7x_msa_alen(const p7x_msa *msa);
+/* which: 0 row idx, 1 its PP line ("" when none), 2 PP_cons, 3 RF, 4 SS_cons ("" when none): copies at most cap-1
+ * characters and returns the full length, -1 on bad arguments (MSA.alignment / TextMSA, easel.pyx MSA 5790-6400) */
+int64_t p7x_msa_get(const p7x_msa *msa, int64_t idx, int which, char *buf, size_t cap);
+void    p7x_msa_destroy(p7x_msa *msa);
+/* Stockholm text as Easel writes it (MSA.write(fh, "stockholm"), easel.pyx MSA.write; esl_msafile_stockholm.c): names
+ * padded to the longest, 200 columns per block, #=GS AC / DE, #=GR PP per row, #=GC SS_cons / PP_cons / RF.  accs,
+ * descs, pps and the annotation lines may be NULL (or hold NULL / ""); every row, and every PP / annotation line that is
+ * given, must have alen characters.  Returns the length of the text and writes it (not NUL-terminated) when cap is large
+ * enough; -1 on bad arguments (a line of another length included). */
+int64_t p7x_msa_write_stockholm(size_t n, int64_t alen, const char *const *names, const char *const *accs,
+                                const char *const *descs, const char *const *aseqs, const char *const *pps,
+                                const char *ss_cons, const char *pp_cons, const char *rf, char *buf, size_t cap);
+
 const char *p7x_last_error(void);
 
 #ifdef __cplusplus

@@ -1,21 +1,20 @@
-// p7x_envelope.hip -- rescoring of one domain envelope on CDNA4: one envelope per WAVEFRONT, all four steps of
-// upstream's rescore_isolated_domain() (p7_domaindef.c) fused into one kernel:
+// p7x_align.hip -- hmmalign on CDNA4 (upstream p7_tracealign_computeTraces, tracealign.c): one whole sequence per
+// WAVEFRONT, the profile in unihit local mode with the sequence's own length model, and the four steps of
 //
-//   1. Forward over the envelope, unihit, full target length model     (impl_sse/fwdback.c  p7_Forward)
-//   2. Backward, re-using Forward's scale factors                       (impl_sse/fwdback.c  p7_Backward)
-//   3. posterior decoding + null2 expectation + optimal-accuracy DP     (decoding.c, null2.c, optacc.c)
-//   4. optimal-accuracy traceback                                       (optacc.c  p7_OATrace)
+//   1. Forward over the sequence                                       (impl_sse/fwdback.c  p7_Forward)
+//   2. Backward, re-using Forward's scale factors                      (impl_sse/fwdback.c  p7_Backward)
+//   3. posterior decoding + optimal-accuracy DP                        (decoding.c, optacc.c)
+//   4. optimal-accuracy traceback                                      (optacc.c  p7_OATrace)
 //
-// Layout is the one of the parsers in p7x_vitfwd.hip: lane z owns nodes z*C+1 .. z*C+C, device tables are
-// [c*64 + lane].  Step 1 keeps only the envelope score and the per-row scale factors; step 2 parks Backward's M and I
-// rows in a per-wavefront HBM workspace (D is not needed: posterior decoding leaves D at zero); step 3 streams them back
-// once, row by row, while it runs Forward AGAIN next to them (same code as step 1: bit-identical values), keeps the OA
-// row in registers and writes 16 bits per cell: the back-pointers and the posterior digits of the M and I cell (all the
-// alignment display needs of the posteriors); step 4 is a serial walk over those by lane 0, followed by a lane-parallel
-// pass that attaches the posterior digit of every emitted residue.  8 + 8 + 2 bytes of HBM traffic per cell (round 1:
-// 16 + 16 + 1); lanes whose nodes are all padding move nothing.
-// The host (p7x_domaindef.cpp) turns the trace into the alignment display and applies the null2 correction.
-#include <cstdlib>
+// fused into one kernel.  This is the envelope kernel of p7x_envelope.hip with the envelope set to the whole sequence
+// (env_len = env_L = L): the same lane layout (lane z owns nodes z*C+1 .. z*C+C), tiers of nodes per lane, waves per
+// block, profile tables in LDS, the same recurrences (p7x_envfwd.hpp) and near-tie guards (p7x_oaguard.hpp).  What
+// differs: no null2 expectation (hmmalign does not score), and the trace carries the FLOAT posterior of every emitted
+// residue rather than the digit the alignment display prints -- the MSA's PP_cons line averages floats.  Phase 3 writes
+// the M and I posteriors of row r over Backward's row r, which it has just read, so the workspace is the envelope
+// kernel's: 8 + 8 + 2 bytes per cell.
+// The host (p7x_tracealign.cpp) repeats every sequence whose status word flags a near-tie on the trace, a posterior
+// within the guard of a printed digit's boundary, or a traceback failure, with the host twin in upstream's order.
 #include <cstdio>
 #include <cstdlib>
 #include "p7x_wave.hpp"
@@ -24,24 +23,16 @@
 
 namespace p7x {
 
-#ifdef P7X_ENV_PROFILE
-// build-time experiment (-DP7X_ENV_PROFILE): core-clock cycles every wavefront spent in the phases of env_kernel, summed
-// over the wavefronts of all launches since the last read: [0..3] phases 1-4, [4] rows, [5] envelopes
-__device__ unsigned long long g_env_prof[8];
-#define P7X_ENV_STAMP(slot) do { const unsigned long long now_ = __builtin_readcyclecounter(); if (lane == 0) atomicAdd(&g_env_prof[slot], now_ - stamp_); stamp_ = now_; } while (0)
-#else
-#define P7X_ENV_STAMP(slot) do { } while (0)
-#endif
+// The band of pp_code_guarded() around a PP digit boundary, in units of 10 p + 0.5: a posterior within align_pp_guard(M)
+// of a boundary flags the sequence (p7x_kernels.hpp: the band grows with the model, as the posteriors' error does).
+__device__ __forceinline__ float align_pp_band(int M) { return 0.5f - 10.0f * align_pp_guard(M); }
 
-// One block per CU: its wavefronts (env_waves(C): 8, or 4 for models of more than 448 nodes) share one copy of the
-// profile tables in LDS and each walks its own envelopes.
 // G: with the near-tie guard (a.oa_guard > 0).  Without it the kernel carries none of the guard's arithmetic.
-// LT: a long-target (nhmmer) envelope -- upstream rescore_isolated_domain(long_target = TRUE): the match odds come from a
-// table of the ENVELOPE's own (re-derived by the host for the background mixed with the envelope's composition,
-// a.env_emis; the length model is the envelope's own length through env_L), and Forward runs once more with the profile's
-// unmodified odds: that score is the envelope's, the difference the bias (a.out_orig).
-template <int C, bool G, bool LT = false>
-__global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kernel(const ArgRef ref)
+// EnvArgs as for env_kernel: nenv sequences, env_len = env_L = the sequence length; out_null2, out_orig and env_emis are
+// not used.  Status word: bit 1 decoding overflow, 2-5 traceback failures, 6 a near-tie on the trace (bits 8-15: which
+// choice; 15 a posterior digit).
+template <int C, bool G>
+__global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) align_kernel(const ArgRef ref)
 {
   constexpr int kEnvBlock = env_waves(C) * 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -53,8 +44,8 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
   const TransView<!TG> tr{ TG ? reinterpret_cast<const float4 *>(a.trans) : reinterpret_cast<const float4 *>(smem), Mpad };
   // emission odds [nrows][Mpad]: staged in LDS while they fit beside the transitions (M <= 1024), else read where they
   // lie (one coalesced 256-byte row segment per chunk and row: L2-resident, like the parsers' long-model variant)
-  constexpr bool kEmisInLds = C <= 16 && !LT;
-  const float *em_profile = kEmisInLds ? reinterpret_cast<const float *>(smem + (size_t) Mpad * 32) : reinterpret_cast<const float *>(a.emis);
+  constexpr bool kEmisInLds = C <= 16;
+  const float *em = kEmisInLds ? reinterpret_cast<const float *>(smem + (size_t) Mpad * 32) : reinterpret_cast<const float *>(a.emis);
   {
     if constexpr (!TG) {
       const float4 *gt = reinterpret_cast<const float4 *>(a.trans);
@@ -76,14 +67,15 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
   // per-wavefront workspace
   float *wsf = a.work + (size_t) wave_id * (size_t) a.work_stride;
   const size_t rows = (size_t) a.Lmax + 1;
-  float *bM = wsf, *bI = bM + rows * Mpad;  // Backward's M and I rows (Forward's are recomputed in phase 3)
+  float *bM = wsf, *bI = bM + rows * Mpad;  // Backward's M and I rows (Forward's are recomputed in phase 3); phase 3
+                                            // overwrites each row with the M and I posteriors once it has read it
   float *fx = bI + rows * Mpad;             // [rows][6]  E N J B C SCALE
   float *bx = fx + rows * 6;                // [rows][6]
   float *ox = bx + rows * 6;                // [rows][5]  OA specials E N J B C
   float *px = ox + rows * 5;                // [rows][3]  posterior N J C
   float *totr_row = px + rows * 3;          // [rows]
-  unsigned short *bp = reinterpret_cast<unsigned short *>(totr_row + rows); // [rows][Mpad] back-pointers (bits 0-3) and the posterior
-                                                                            // digits of the M (4-7) and I (8-11) cells
+  unsigned short *bp = reinterpret_cast<unsigned short *>(totr_row + rows); // [rows][Mpad] back-pointers (bits 0-3) and the
+                                                                            // near-tie flags of the cell (12-15)
   const bool lane_live = lane * C < a.M;    // lanes whose nodes are all padding neither store nor load rows
   int erank[C];                             // rank of this lane's nodes in the striped visiting order of select_e (q outer, stripe inner)
   {
@@ -93,7 +85,7 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
   }
 
   for (;;) {
-    // envelopes are taken longest first from the job's queue: a wavefront that drew a short one comes back for more
+    // sequences are taken longest first from the job's queue: a wavefront that drew a short one comes back for more
     int q = 0;
     if (lane == 0) q = atomicAdd(a.cursor, 1);
     q = rfl(q);
@@ -106,12 +98,7 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
     const uint8_t *sq = a.dsq + (((unsigned long long) ohi << 32) | olo);      // sq[0] = first residue of the envelope
     const float pmove = (2.0f + a.nj) / ((float) Lfull + 2.0f + a.nj), ploop = 1.0f - pmove;
     int status = 0;
-    const float *em = LT ? a.env_emis + (size_t) it * (size_t) a.env_emis_stride : em_profile;      // [nrows][Mpad]
 
-#ifdef P7X_ENV_PROFILE
-    unsigned long long stamp_ = __builtin_readcyclecounter();
-    if (lane == 0) { atomicAdd(&g_env_prof[4], (unsigned long long) Ld); atomicAdd(&g_env_prof[5], 1ull); }
-#endif
     // ------------------------------------------------------------------ 1. Forward (score and scale factors)
     float envsc;
     {
@@ -133,23 +120,7 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
       if (f.xC != f.xC || (Ld > 0 && f.xC == 0.0f) || __builtin_isinf(f.xC)) { envsc = __builtin_inff(); status |= 1; }
       else envsc = (float) ((double) f.totscale + log((double) (f.xC * pmove)));
     }
-    if constexpr (LT) {            // Forward with the profile's own odds: the envelope's score proper.  (Run row by row next to
-                                   // the first recurrence it was slower: 66 against 58 ms for the benchmark's two rounds.)
-      EnvForward<C> g;
-      g.init(tr, lane, pmove);
-      for (int i0 = 0; i0 < Ld; i0 += 64) {
-        const int nrow = min(64, Ld - i0);
-        const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
-        for (int r = 0; r < nrow; ++r)
-          g.row(tr, em_profile, Mpad, lane, __builtin_amdgcn_readlane((int) resid, r), pmove, ploop, a.xf_e_move, a.xf_e_loop);
-      }
-      float orig;
-      if (g.xC != g.xC || (Ld > 0 && g.xC == 0.0f) || __builtin_isinf(g.xC)) { orig = __builtin_inff(); status |= 1; }
-      else orig = (float) ((double) g.totscale + log((double) (g.xC * pmove)));
-      if (lane == 0) a.out_orig[it] = orig;
-    }
     phase_fence();
-    P7X_ENV_STAMP(0);
 
     // ------------------------------------------------------------------ 2. Backward
     bool own_scales = false;
@@ -273,9 +244,8 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
       }
     }
     phase_fence();
-    P7X_ENV_STAMP(1);
 
-    // ------------------------------------------------------------------ 3. decoding, null2 sums, optimal accuracy
+    // ------------------------------------------------------------------ 3. decoding and optimal accuracy
     float oasc;
     int e_row = -1, e_k = 0, e_s = 0, e_near = 0, c_near_row = -1;
     {
@@ -285,13 +255,12 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
       for (int c = 0; c < C; ++c) ddpass = ddpass && (tr.dd(c * 64 + lane) > 0.0f);
       float p_md0, p_dd0;                                            // leaving transitions of the previous lane's last node
       { const F8 t = tr.at((C - 1) * 64 + lane); p_md0 = dpp_shr1f(t.md, 0.0f); p_dd0 = dpp_shr1f(t.dd, 0.0f); }
-      float om_[C], oi_[C], od_[C], msum[C], isum[C];
+      float om_[C], oi_[C], od_[C];
 #pragma unroll unroll_env(C)
-      for (int c = 0; c < C; ++c) { om_[c] = oi_[c] = od_[c] = kNegInf; msum[c] = isum[c] = 0.0f; }
+      for (int c = 0; c < C; ++c) om_[c] = oi_[c] = od_[c] = kNegInf;
       float oE = kNegInf, oN = 0.0f, oJ = kNegInf, oB = 0.0f, oC = kNegInf;
-      float eN = 0.0f, eJ = 0.0f, eC = 0.0f;
       const int Q = max(2, (a.M - 1) / 4 + 1);                         // p7O_NQF(M): the striped visiting order of select_e
-      const float g1 = 1.0f - a.oa_guard, ppband = 0.5f - __builtin_fmaxf(4.0f * a.oa_guard, 2.0e-6f);     // (2e-6: what float costs the digit)
+      const float g1 = 1.0f - a.oa_guard, ppband = align_pp_band(a.M);
       const bool loopJ = ploop != 0.0f, loopE = a.xf_e_loop != 0.0f, moveE = a.xf_e_move != 0.0f, moveNJ = pmove != 0.0f;
       // Row r+1 is fetched while row r is processed: four vector rows and the twelve special-state values (one load,
       // lane l < 6 takes Forward's, lane 8 + l Backward's), so that no memory round trip sits on the row's critical path.
@@ -336,14 +305,11 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
         for (int c = 0; c < C; ++c) {
           ppm[c] = (cfm[c] * cbm[c]) * totr;
           ppi[c] = (cfi[c] * cbi[c]) * totr;
-          msum[c] = ppm[c] + msum[c];
-          isum[c] = ppi[c] + isum[c];
         }
         const float ppN = xval(xprev, 1) * xval(xthis, 8 + 1) * ploop * scaleproduct;
         const float ppJ = xval(xprev, 2) * xval(xthis, 8 + 2) * ploop * scaleproduct;
         const float ppC = xval(xprev, 4) * xval(xthis, 8 + 4) * ploop * scaleproduct;
         xprev = xthis;
-        eN += ppN; eJ += ppJ; eC += ppC;
         if (own_scales) scaleproduct *= fS / bS;
 
         // OA row.  DP values use gate() (0 when a transition is closed); the traceback rule uses -inf (block()).
@@ -377,15 +343,8 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
           om_[c] = sv + ppm[c];
           oi_[c] = iv + ppi[c];
           int near_pp = 0;
-          unsigned cm, ci;
-          // (long-target envelopes keep the digits in double: with the float form the <20, true, true> instantiation -- 256 VGPRs,
-          // 420 spilled SGPRs, scratch -- faulted on the device, round 6; their posterior digits are tested against the band alone)
-          if constexpr (G && !LT) { cm = pp_code_guarded(ppm[c], ppband, near_pp); ci = pp_code_guarded(ppi[c], ppband, near_pp); }
-          else {
-            cm = pp_code(ppm[c]); ci = pp_code(ppi[c]);
-            if constexpr (G) near_pp = pp_near(ppm[c], a.oa_guard) | pp_near(ppi[c], a.oa_guard);
-          }
-          code[c] = (unsigned short) (best | (ichoice << 2) | (cm << 4) | (ci << 8) | (near_m << 12) | (near_i << 13) | (near_pp << 15));
+          if constexpr (G) { (void) pp_code_guarded(ppm[c], ppband, near_pp); (void) pp_code_guarded(ppi[c], ppband, near_pp); }
+          code[c] = (unsigned short) (best | (ichoice << 2) | (near_m << 12) | (near_i << 13) | (near_pp << 15));
         }
         // D(r,k) = max(gate(tMD(k-1), M(r,k-1)), tDD(k-1) > 0 ? D(r,k-1) : 0), D(r,1) = -inf: a segmented max-scan
         {
@@ -417,9 +376,10 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
         __builtin_amdgcn_s_waitcnt(0x0f70);            // vmcnt(0), expcnt and lgkmcnt unconstrained
         {
           unsigned short *rb = bp + (size_t) r * Mpad + lane;
-          if (lane_live) {
+          float *rm = bM + (size_t) r * Mpad + lane, *ri = bI + (size_t) r * Mpad + lane;
+          if (lane_live) {            // row r of Backward was read in the previous iteration: its slots take the posteriors
 #pragma unroll unroll_env(C)
-            for (int c = 0; c < C; ++c) rb[c * 64] = code[c];
+            for (int c = 0; c < C; ++c) { rb[c * 64] = code[c]; rm[c * 64] = ppm[c]; ri[c * 64] = ppi[c]; }
           }
         }
         float rowmax = kNegInf;
@@ -475,23 +435,9 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
       }
       if (lane == 0) { float *o = ox; o[0] = kNegInf; o[1] = 0.0f; o[2] = kNegInf; o[3] = 0.0f; o[4] = kNegInf; }
       oasc = oC;
-      if (__builtin_isinf(scaleproduct)) status |= 2;            // p7_Decoding: eslERANGE, the envelope is dropped
-
-      // null2 by expectation: state occupancies -> residue odds
-      const float norm = (float) (1.0 / (double) (float) Ld);
-      const float xfactor = (eN * norm + eC * norm) + eJ * norm;
-      float *n2 = a.out_null2 + (size_t) it * 32;
-      for (int x = 0; x < a.K; ++x) {
-        const float *er = em + x * Mpad + lane;
-        float s = 0.0f;
-#pragma unroll unroll_env(C)
-        for (int c = 0; c < C; ++c) { s = s + (msum[c] * norm) * er[c * 64]; s = s + isum[c] * norm; }
-        s = wave_sum_f32(s);
-        if (lane == 0) n2[x] = s + xfactor;
-      }
+      if (__builtin_isinf(scaleproduct)) status |= 2;            // p7_Decoding: eslERANGE (the host names the sequence)
     }
     phase_fence();
-    P7X_ENV_STAMP(2);
 
     // ------------------------------------------------------------------ 4. traceback (p7_OATrace)
     // The walk is serial, but most of it needs no decision at all: the C states from the last row down to the row where
@@ -611,19 +557,21 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
     phase_fence();
     // posterior probability of each trace step (get_postprob), all lanes
     int pp_flag = 0;
+    const float ppband = align_pp_band(a.M);
     for (int z = lane; z < n; z += 64) {
       const uint32_t w = ta[z];
       const int s = (int) (w & 0xffu), k = (int) ((w >> 8) & 0xffffu), i = ti[z];
       const bool same = (w & 0x80000000u) != 0;
       float pp = 0.0f;
       if ((s == tM || s == tI) && i >= 1 && k >= 1) {
-        const unsigned w16 = bp[(size_t) i * Mpad + ((k - 1) % C) * 64 + (k - 1) / C];
-        pp = pp_from_code((s == tM) ? ((w16 >> 4) & 15u) : ((w16 >> 8) & 15u));
-        pp_flag |= (int) ((w16 >> 15) & 1u);
+        const size_t cell = (size_t) i * Mpad + ((k - 1) % C) * 64 + (k - 1) / C;
+        pp = (s == tM) ? bM[cell] : bI[cell];
+        pp_flag |= (int) ((bp[cell] >> 15) & 1u);
       } else if (same && i >= 1) {
         if (s == tN) pp = px[(size_t) i * 3 + 0];
         else if (s == tJ) pp = px[(size_t) i * 3 + 1];
         else if (s == tC) pp = px[(size_t) i * 3 + 2];
+        if constexpr (G) (void) pp_code_guarded(pp, ppband, pp_flag);      // the flanks are printed too (untrimmed MSAs)
       }
       tp[z] = pp;
       ta[z] = w & 0x7fffffffu;
@@ -636,24 +584,32 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
       a.tr_n[it] = n;
     }
     phase_fence();      // the workspace is about to be overwritten by this wavefront's next envelope
-    P7X_ENV_STAMP(3);
   }
 }
 
 // ---------------------------------------------------------------------------- host side
-size_t env_work_floats(int C, int Lmax)
-{ // floats per wavefront; keep in step with the carving at the top of env_kernel
+size_t align_work_floats(int C, int Lmax)
+{ // floats per wavefront; keep in step with the carving at the top of align_kernel
   const size_t rows = (size_t) Lmax + 1, Mpad = (size_t) 64 * C;
   size_t f = 2 * rows * Mpad + rows * (6 + 6 + 5 + 3 + 1);
-  f += (rows * Mpad + 1) / 2;          // back-pointers + posterior digits, 16 bits per cell
+  f += (rows * Mpad + 1) / 2;          // back-pointers and near-tie flags, 16 bits per cell
   return (f + 63) & ~(size_t) 63;
 }
 
+static size_t align_lds_bytes(int C, int nrows) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? (size_t) nrows * 4 : 0)); }
+
 template <typename K>
-static int launch_env(K kernel, const ArgRun<EnvArgs> &a, size_t lds_bytes, hipStream_t st)
+static int set_lds(K kernel, size_t lds_bytes)
 {
   if (lds_bytes > 64 * 1024)
     P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
+  return P7X_OK;
+}
+
+template <typename K>
+static int launch_align(K kernel, const ArgRun<EnvArgs> &a, size_t lds_bytes, hipStream_t st)
+{
+  const int s = set_lds(kernel, lds_bytes); if (s != P7X_OK) return s;
   int gx = 1;
   for (int i = 0; i < a.n; ++i) gx = std::max(gx, a.at(i).nblocks);
   hipLaunchKernelGGL(kernel, dim3((unsigned) gx, (unsigned) a.n), dim3((unsigned) env_waves(a.at(0).C) * 64), lds_bytes, st, a.ref());
@@ -662,70 +618,44 @@ static int launch_env(K kernel, const ArgRun<EnvArgs> &a, size_t lds_bytes, hipS
 }
 
 template <typename K>
-static int occupancy_env(K kernel, int kEnvBlock, size_t lds_bytes, int *per_cu)
+static int occupancy_align(K kernel, int block, size_t lds_bytes, int *per_cu)
 {
-  if (lds_bytes > 64 * 1024)
-    P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-  P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, kEnvBlock, lds_bytes));
-  if (debug_opt(OPT_TRACE_ENVELOPE) > 0) {
-    hipFuncAttributes fa; (void) hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernel));
-    std::fprintf(stderr, "[env] occupancy %d blocks/CU of %d threads, lds %zu, regs %d, static lds %zu, maxthreads %d\n", *per_cu, kEnvBlock, lds_bytes,
-                 fa.numRegs, fa.sharedSizeBytes, fa.maxThreadsPerBlock);
-  }
+  const int s = set_lds(kernel, lds_bytes); if (s != P7X_OK) return s;
+  P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, block, lds_bytes));
   if (*per_cu < 1) *per_cu = 1;
   return P7X_OK;
 }
 
-#define P7X_ENV_SWITCH(EXPR)                                                                                  \
+#define P7X_ALIGN_CASE(CC) \
+    case CC: { if (G_) { auto kern = align_kernel<CC, true>; return EXPR_; } else { auto kern = align_kernel<CC, false>; return EXPR_; } }
+#define P7X_ALIGN_SWITCH                                                                                      \
   switch (C) {                                                                                                \
-    case 1: { if (LT_) { auto kern = env_kernel<1, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<1, true>; return EXPR; } else { auto kern = env_kernel<1, false>; return EXPR; } }                                                     \
-    case 2: { if (LT_) { auto kern = env_kernel<2, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<2, true>; return EXPR; } else { auto kern = env_kernel<2, false>; return EXPR; } }                                                     \
-    case 3: { if (LT_) { auto kern = env_kernel<3, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<3, true>; return EXPR; } else { auto kern = env_kernel<3, false>; return EXPR; } }                                                     \
-    case 4: { if (LT_) { auto kern = env_kernel<4, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<4, true>; return EXPR; } else { auto kern = env_kernel<4, false>; return EXPR; } }                                                     \
-    case 5: { if (LT_) { auto kern = env_kernel<5, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<5, true>; return EXPR; } else { auto kern = env_kernel<5, false>; return EXPR; } }                                                     \
-    case 6: { if (LT_) { auto kern = env_kernel<6, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<6, true>; return EXPR; } else { auto kern = env_kernel<6, false>; return EXPR; } }                                                     \
-    case 8: { if (LT_) { auto kern = env_kernel<8, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<8, true>; return EXPR; } else { auto kern = env_kernel<8, false>; return EXPR; } }                                                     \
-    case 10: { if (LT_) { auto kern = env_kernel<10, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<10, true>; return EXPR; } else { auto kern = env_kernel<10, false>; return EXPR; } }                                                     \
-    case 12: { if (LT_) { auto kern = env_kernel<12, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<12, true>; return EXPR; } else { auto kern = env_kernel<12, false>; return EXPR; } }                                                     \
-    case 16: { if (LT_) { auto kern = env_kernel<16, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<16, true>; return EXPR; } else { auto kern = env_kernel<16, false>; return EXPR; } }                                                     \
-    case 20: { if (LT_) { auto kern = env_kernel<20, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<20, true>; return EXPR; } else { auto kern = env_kernel<20, false>; return EXPR; } }                                                     \
-    case 24: { if (LT_) { auto kern = env_kernel<24, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<24, true>; return EXPR; } else { auto kern = env_kernel<24, false>; return EXPR; } }                                                     \
-    case 32: { if (LT_) { auto kern = env_kernel<32, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<32, true>; return EXPR; } else { auto kern = env_kernel<32, false>; return EXPR; } } \
-    case 48: { if (LT_) { auto kern = env_kernel<48, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<48, true>; return EXPR; } else { auto kern = env_kernel<48, false>; return EXPR; } } \
-    case 64: { if (LT_) { auto kern = env_kernel<64, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<64, true>; return EXPR; } else { auto kern = env_kernel<64, false>; return EXPR; } } \
-    case 96: { if (LT_) { auto kern = env_kernel<96, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<96, true>; return EXPR; } else { auto kern = env_kernel<96, false>; return EXPR; } } \
-    case 128: { if (LT_) { auto kern = env_kernel<128, true, true>; return EXPR; } else if (G_) { auto kern = env_kernel<128, true>; return EXPR; } else { auto kern = env_kernel<128, false>; return EXPR; } }                                                     \
-    default: set_error("model too long for the envelope kernel"); return P7X_EINVAL;                         \
+    P7X_ALIGN_CASE(1) P7X_ALIGN_CASE(2) P7X_ALIGN_CASE(3) P7X_ALIGN_CASE(4) P7X_ALIGN_CASE(5) P7X_ALIGN_CASE(6)              \
+    P7X_ALIGN_CASE(8) P7X_ALIGN_CASE(10) P7X_ALIGN_CASE(12) P7X_ALIGN_CASE(16) P7X_ALIGN_CASE(20) P7X_ALIGN_CASE(24)         \
+    P7X_ALIGN_CASE(32) P7X_ALIGN_CASE(48) P7X_ALIGN_CASE(64) P7X_ALIGN_CASE(96) P7X_ALIGN_CASE(128)                         \
+    default: set_error("model too long for the alignment kernel"); return P7X_EINVAL;                         \
   }
 
-static size_t env_lds_bytes(int C, int nrows) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? (size_t) nrows * 4 : 0)); }
-
-int env_max_blocks(int C, int nrows, int num_cu, int *nblocks)
+int align_max_blocks(int C, int nrows, int num_cu, int *nblocks)
 {
-  const size_t lds = env_lds_bytes(C, nrows);
+  const size_t lds = align_lds_bytes(C, nrows);
   int per_cu = 1;
   auto finish = [&](int st) { if (st == P7X_OK) *nblocks = num_cu * per_cu; return st; };
-  const bool G_ = true, LT_ = false;            // the guarded kernel is never the smaller one
-  P7X_ENV_SWITCH(finish(occupancy_env(kern, env_waves(C) * 64, lds, &per_cu)))
+  const bool G_ = true;                         // the guarded kernel is never the smaller one
+#define EXPR_ finish(occupancy_align(kern, env_waves(C) * 64, lds, &per_cu))
+  P7X_ALIGN_SWITCH
+#undef EXPR_
 }
 
-int env_launch(const ArgRun<EnvArgs> &a, hipStream_t st)
+int align_launch(const ArgRun<EnvArgs> &a, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C;
-  const bool LT_ = a.at(0).env_emis != nullptr;
-  const size_t lds = LT_ ? (C > 64 ? (size_t) 256 : (size_t) 64 * C * 32) : env_lds_bytes(C, a.at(0).nrows);
+  const size_t lds = align_lds_bytes(C, a.at(0).nrows);
   const bool G_ = a.at(0).oa_guard > 0.0f;
-  P7X_ENV_SWITCH(launch_env(kern, a, lds, st))
+#define EXPR_ launch_align(kern, a, lds, st)
+  P7X_ALIGN_SWITCH
+#undef EXPR_
 }
 
 } // namespace p7x
-
-#ifdef P7X_ENV_PROFILE
-extern "C" int p7x_debug_env_profile(unsigned long long *out8)
-{
-  unsigned long long zero[8] = { 0 };
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(p7x::g_env_prof), sizeof zero) != hipSuccess) return 1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(p7x::g_env_prof), zero, sizeof zero) != hipSuccess;
-}
-#endif

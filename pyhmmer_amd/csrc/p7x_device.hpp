@@ -128,6 +128,9 @@ namespace p7x {
 struct LongTargetWindowRegions;
 int device_regions_of_all(const p7x_oprofile *om, const p7x_seqdb *db, std::vector<LongTargetWindowRegions> &out);
 std::unique_ptr<EnvelopeScorer> make_device_envelope_scorer(DeviceCtx *ctx, const p7x_seqdb *db, float oa_guard);
+// hmmalign (p7x_align.hip): requests are whole sequences (i = 1, j = L); the results carry float posteriors and no null2
+std::unique_ptr<EnvelopeScorer> make_device_align_scorer(DeviceCtx *ctx, const p7x_seqdb *db, float oa_guard);
+size_t align_budget_bytes();           // HBM budget of its workspace (24 GiB or half the free memory; option "align_workspace_gb")
 std::unique_ptr<EnsembleRunner> make_device_ensemble_runner(DeviceCtx *ctx, const p7x_seqdb *db, float guard);
 
 } // namespace p7x

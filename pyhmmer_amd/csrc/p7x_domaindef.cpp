@@ -1543,6 +1543,41 @@ int parser_rows_upstream(const Profile &p, const uint8_t *dsq, int L, std::vecto
   return P7X_OK;
 }
 
+// hmmalign's per-sequence step (upstream p7_tracealign_computeTraces): the profile unihit local with the sequence's own
+// length model, the whole sequence as the envelope, Forward -> Backward -> Decoding -> OptimalAccuracy -> OATrace -- the
+// steps of rescore_isolated_domain() without null2, in upstream's summation order unless <order> says otherwise (0
+// upstream, 1 the device's, -1 the "host_order" seam).  dsq1[1..L]; the trace comes out in forward order.  P7X_ERANGE:
+// p7_Decoding overflowed.
+int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order)
+{
+  out = AlignTrace{};
+  if (L <= 0) return P7X_OK;                    // an empty sequence: an empty trace
+  // two full matrices of (L + 1) x (M + 2) cells: a worker keeps them for its next sequence, but not beyond 128 MiB (a
+  // long model against a long sequence would otherwise leave gigabytes behind in every worker of the pool)
+  thread_local Workspace ws;
+  struct Shrink { Workspace &ws; ~Shrink() { if (ws.fwd.m.capacity() * sizeof(float) * 6 > ((size_t) 128 << 20)) ws = Workspace(); } } shrink{ ws };
+  Model om{ &p, p.M, {} };
+  om.prepare(order);
+  om.configure(false, L);
+  int st = forward_full(om, dsq1, L, ws.fwd, &out.fwdsc);
+  if (st != P7X_OK) return st;
+  if ((st = backward_full(om, dsq1, L, ws.fwd, ws.bck, nullptr)) != P7X_OK) return st;
+  if (decoding(om, ws.fwd, ws.bck) == P7X_ERANGE) return P7X_ERANGE;
+  optimal_accuracy(om, ws.bck, ws.fwd, &out.oasc);
+  if (oa_trace(om, ws.bck, ws.fwd, ws.tr) != P7X_OK) return P7X_EINVAL;
+  out.st = ws.tr.st; out.k = ws.tr.k; out.i = ws.tr.i; out.pp = ws.tr.pp;
+  return P7X_OK;
+}
+
+// A device trace (traceback order, EnvelopeResult's packing: state | k << 8) in forward order, as p7_trace_Reverse leaves it
+void align_trace_from_device(const uint32_t *ta, const int32_t *ti, const float *tp, int n, AlignTrace &out)
+{
+  Trace tr;
+  for (int z = 0; z < n; ++z) tr.append((int) (ta[z] & 0xffu), (int) ((ta[z] >> 8) & 0xffffu), ti[z], tp[z]);
+  tr.reverse();
+  out.st = std::move(tr.st); out.k = std::move(tr.k); out.i = std::move(tr.i); out.pp = std::move(tr.pp);
+}
+
 // Second half of rescore_isolated_domain() for envelopes rescored by the device kernel: trace -> alignment
 // display, null2 odds -> per-residue corrections.  req_index[n] is the position in <res> of local request n
 // (Domain::deferred of the placeholders of this target).

@@ -48,18 +48,21 @@ static void release_env_buffers(EnvBuffers *eb)
   for (size_t i = 0; i < ep.all.size(); ++i) if (ep.all[i] == eb) ep.busy[i] = 0;
 }
 
-static size_t env_budget_bytes()
+static size_t env_budget_bytes(int option)
 {
   size_t gb = 24;
-  if (debug_opt(OPT_ENV_WORKSPACE_GB) > 0) gb = (size_t) debug_opt(OPT_ENV_WORKSPACE_GB);      // tests: a workspace too small for every envelope at once
+  if (debug_opt(option) > 0) gb = (size_t) debug_opt(option);      // tests: a workspace too small for every envelope at once
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 2 < gb << 30) return free_b / 2;
   return gb << 30;
 }
 
+size_t align_budget_bytes() { return env_budget_bytes(OPT_ALIGN_WORKSPACE_GB); }
+
 class DeviceEnvelopeScorer final : public EnvelopeScorer {
 public:
-  DeviceEnvelopeScorer(DeviceCtx *ctx, const p7x_seqdb *db) : ctx_(ctx), db_(db) {}
+  // align: the requests are whole sequences for hmmalign's kernel (p7x_align.hip) instead of envelopes for env_kernel
+  DeviceEnvelopeScorer(DeviceCtx *ctx, const p7x_seqdb *db, bool align = false) : ctx_(ctx), db_(db), align_(align) {}
   ~DeviceEnvelopeScorer() override { if (lease_) { if (lease_->stream) (void) hipStreamSynchronize(lease_->stream); release_env_buffers(lease_); } }
 
   int begin(const std::vector<EnvelopeJob> &jobs) override
@@ -152,7 +155,7 @@ public:
     // workspace: one slab per wavefront of every job, sized for the longest envelope of the job's class
     std::map<int, int> class_Lmax;
     for (size_t j = 0; j < nj; ++j) if (meta_[j].nenv) { int &v = class_Lmax[meta_[j].C]; v = std::max(v, meta_[j].Lmax); }
-    const size_t budget = env_budget_bytes();
+    const size_t budget = env_budget_bytes(align_ ? OPT_ALIGN_WORKSPACE_GB : OPT_ENV_WORKSPACE_GB);
     int shrink = 1;
     size_t work_floats = 0;
     for (;; shrink *= 2) {
@@ -161,15 +164,16 @@ public:
         JobMeta &m = meta_[j];
         if (m.nenv == 0) continue;
         int cap_blocks = 0;
-        if ((st = env_max_blocks(m.C, jobs[j].om->p.Kp + 1, ctx_->num_cu, &cap_blocks)) != P7X_OK) return st;
+        if ((st = (align_ ? align_max_blocks : env_max_blocks)(m.C, jobs[j].om->p.Kp + 1, ctx_->num_cu, &cap_blocks)) != P7X_OK) return st;
         // the jobs share the resident blocks in proportion to their envelopes; a job with more envelopes than wavefronts
         // hands them out longest first (EnvArgs::order / cursor)
         const int share = (int) std::max<int64_t>(1, (int64_t) cap_blocks * m.nenv / nenv_tot);
         m.nblocks = std::max(1, std::min(share, (m.nenv + env_waves(m.C) - 1) / env_waves(m.C)) / shrink);
-        m.stride = env_work_floats(m.C, class_Lmax[m.C]);
+        m.stride = (align_ ? align_work_floats : env_work_floats)(m.C, class_Lmax[m.C]);
         work_floats += (size_t) m.nblocks * env_waves(m.C) * m.stride;
       }
-      if (work_floats * 4 <= budget || work_floats <= eb->work_floats) break;
+      // (envelopes: a pooled workspace that is already large enough is used at this occupancy; hmmalign keeps to its budget)
+      if (work_floats * 4 <= budget || (!align_ && work_floats <= eb->work_floats)) break;
       bool all_one = true;
       for (size_t j = 0; j < nj; ++j) if (meta_[j].nenv && meta_[j].nblocks > 1) all_one = false;
       if (all_one) { set_error("envelope workspace does not fit in device memory"); return P7X_EMEM; }
@@ -180,6 +184,7 @@ public:
       const int sst = slab_acquire(ctx_, std::max<size_t>(work_floats * 4 + work_floats, (size_t) 1 << 30), &dp, &got); if (sst != P7X_OK) return sst;
       eb->work = static_cast<float *>(dp); eb->work_bytes = got; eb->work_floats = got / 4;
     }
+    work_bytes_ = work_floats * 4;
     tick("work");
     // outputs: [out_sc 2f][null2 32f][status i][tr_n i][orig f] per envelope, then the three trace arrays
     const size_t n = (size_t) nenv_tot;
@@ -258,7 +263,7 @@ public:
       ArgRun<EnvArgs> ar;
       ar.host = h_args + run.first; ar.dev = eb->d_in + o_args + (size_t) run.first * sizeof(EnvArgs);
       ar.stride = (uint32_t) sizeof(EnvArgs); ar.n = run.second;
-      if ((st = env_launch(ar, s)) != P7X_OK) return st;
+      if ((st = (align_ ? align_launch : env_launch)(ar, s)) != P7X_OK) return st;
     }
     tick("launches");
     P7X_HIP(hipMemcpyAsync(eb->h_out, eb->d_out, out_bytes, hipMemcpyDeviceToHost, s));
@@ -298,11 +303,14 @@ public:
   }
 
   void set_oa_guard(float g) { oa_guard_ = g > 0.0f ? g : 0.0f; }
+  size_t workspace_bytes() const override { return work_bytes_; }
 
 private:
   float oa_guard_ = 0.0f;
   struct JobMeta { int64_t first = 0; int nenv = 0, C = 0, Lmax = 1, nblocks = 1; size_t stride = 0; DevProfile *dp = nullptr; };
   DeviceCtx *ctx_; const p7x_seqdb *db_;
+  bool align_ = false;
+  size_t work_bytes_ = 0;
   std::vector<EnvelopeJob> jobs_;
   std::vector<JobMeta> meta_;
   std::vector<int> order_;
@@ -316,6 +324,13 @@ private:
 std::unique_ptr<EnvelopeScorer> make_device_envelope_scorer(DeviceCtx *ctx, const p7x_seqdb *db, float oa_guard)
 {
   auto s = std::make_unique<DeviceEnvelopeScorer>(ctx, db);
+  s->set_oa_guard(oa_guard);
+  return s;
+}
+
+std::unique_ptr<EnvelopeScorer> make_device_align_scorer(DeviceCtx *ctx, const p7x_seqdb *db, float oa_guard)
+{
+  auto s = std::make_unique<DeviceEnvelopeScorer>(ctx, db, true);
   s->set_oa_guard(oa_guard);
   return s;
 }

@@ -60,6 +60,7 @@ struct EnvelopeScorer {
   // buffers stay valid until the next begin().
   virtual int begin(const std::vector<EnvelopeJob> &jobs) = 0;
   virtual int wait(std::vector<std::vector<EnvelopeResult>> &res) = 0;
+  virtual size_t workspace_bytes() const { return 0; }     // device workspace the last begin() laid out for its wavefronts
 };
 
 // The stochastic traceback ensembles of multi-domain regions can be handed to the device as well (p7x_ensemble.hip): a
@@ -83,6 +84,10 @@ struct EnsembleRunner {
 uint32_t fast_rng_state(uint32_t seed);          // esl_randomness_Init for the LCG
 // p7_ForwardParser / p7_BackwardParser special-state rows ((L+1) x [E,N,J,B,C,SCALE], multihit, length model of L) in upstream's
 // summation order (the full-matrix engine; the target's DP matrices are scratch): dsq[1..L]
+// hmmalign's host twin (p7x_domaindef.cpp): the trace of one whole sequence, forward order, float posteriors
+struct AlignTrace { std::vector<int8_t> st; std::vector<int> k, i; std::vector<float> pp; float fwdsc = 0.0f, oasc = 0.0f; };
+int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order = 0);
+void align_trace_from_device(const uint32_t *ta, const int32_t *ti, const float *tp, int n, AlignTrace &out);
 int parser_rows_upstream(const Profile &p, const uint8_t *dsq, int L, std::vector<float> &fx, std::vector<float> &bx);
 
 // p7_domaindef_ByPosteriorHeuristics (p7_domaindef.pxd:69-72).  dsq is 1-indexed (dsq[1..L]);

@@ -186,6 +186,17 @@ size_t env_work_floats(int C, int Lmax);
 int env_max_blocks(int C, int nrows, int num_cu, int *nblocks);
 // every record of the run has the same C and nrows; grid.x = the widest job's nblocks
 int env_launch(const ArgRun<EnvArgs> &a, hipStream_t st);
+// ---- hmmalign (p7x_align.hip): the envelope kernel's four steps over whole sequences, float posteriors on the trace,
+// no null2.  Same arguments (EnvArgs, env_len = env_L), same workspace carving.
+size_t align_work_floats(int C, int Lmax);
+// Half-width of the guard band around a PP digit boundary, in posterior units.  The device's float posteriors differ from
+// the host twin's by an error that grows with the model (at most 1.25e-6 for the fixture models of <= 262 nodes against the
+// proteome, 7.5e-6 at M = 6,000; about 1e-9 M): the band is at least three times that, and never below 1e-5.  A residue on
+// the trace whose posterior lies within it flags the sequence (kernel); a PP_cons column whose mean does is averaged
+// again over host-twin posteriors (p7x_tracealign.cpp).
+__host__ __device__ inline float align_pp_guard(int M) { return 1.0e-5f + 2.5e-9f * (float) M; }
+int align_max_blocks(int C, int nrows, int num_cu, int *nblocks);
+int align_launch(const ArgRun<EnvArgs> &a, hipStream_t st);
 
 // ---- stochastic traceback ensembles of multi-domain regions (p7x_ensemble.hip; upstream p7_domaindef.c
 // region_trace_ensemble): a multihit Forward fill of the region that leaves, per cell and per row, the integer

@@ -21,7 +21,7 @@ import numpy as np
 
 __all__ = [
     "Alphabet", "Sequence", "TextSequence", "DigitalSequence",
-    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile",
+    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA",
 ]
 
 _AMINO = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -624,3 +624,130 @@ class SequenceFile:
         if self.digital:
             return DigitalSequenceBlock(self.alphabet, out)
         return TextSequenceBlock(out)
+
+
+class MSA:
+    """A multiple sequence alignment (reference ``easel.pyx`` ``MSA`` / ``TextMSA`` / ``DigitalMSA``; ``ESL_MSA``).
+
+    Rows are kept as text: residues, ``-`` for deletions and ``.`` for gaps in insert columns, inserts in lower case (as
+    hmmalign builds them).  Optional per-column / per-row annotation: ``posterior_probabilities`` (``#=GR PP``),
+    ``pp_consensus`` (``#=GC PP_cons``), ``reference`` (``#=GC RF``), ``secondary_structure`` (``#=GC SS_cons``).
+    """
+
+    def __init__(self, name: Optional[str] = None, description: Optional[str] = None, accession: Optional[str] = None,
+                 sequences: Optional[Iterable] = None):
+        self.name, self.description, self.accession = name, description, accession
+        self._names: List[str] = []
+        self._rows: List[str] = []
+        self._descs: List[str] = []
+        self._accs: List[str] = []
+        self.posterior_probabilities: Optional[List[str]] = None
+        self.pp_consensus: Optional[str] = None
+        self.reference: Optional[str] = None
+        self.secondary_structure: Optional[str] = None
+        for seq in sequences or ():
+            self._add(seq)
+
+    def _add(self, seq) -> None:
+        row = seq.sequence if isinstance(seq, TextSequence) else seq.alphabet.decode(seq.sequence)
+        if self._rows and len(row) != len(self._rows[0]):
+            raise ValueError("all the sequences of an alignment must have the same length")
+        if seq.name in self._names:
+            raise ValueError(f"duplicate sequence name {seq.name!r}")
+        self._names.append(seq.name)
+        self._rows.append(row)
+        self._descs.append(seq.description or "")
+        self._accs.append(seq.accession or "")
+
+    @classmethod
+    def _from_rows(cls, names, rows, descs, accs, pp=None, pp_cons=None, rf=None, ss_cons=None, alphabet=None):
+        self = cls.__new__(cls)
+        MSA.__init__(self)
+        if alphabet is not None:
+            self.alphabet = alphabet
+        self._names, self._rows, self._descs, self._accs = list(names), list(rows), list(descs), list(accs)
+        self.posterior_probabilities, self.pp_consensus, self.reference, self.secondary_structure = pp, pp_cons, rf, ss_cons
+        return self
+
+    def __len__(self) -> int:
+        """The alignment length (number of columns), as ``len(MSA)`` in the reference."""
+        return len(self._rows[0]) if self._rows else 0
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, MSA) or type(self) is not type(other):
+            return NotImplemented
+        return (self._names == other._names and self._rows == other._rows and self._descs == other._descs
+                and self._accs == other._accs and self.posterior_probabilities == other.posterior_probabilities
+                and self.pp_consensus == other.pp_consensus and self.reference == other.reference
+                and self.secondary_structure == other.secondary_structure
+                and getattr(self, "alphabet", None) == getattr(other, "alphabet", None))
+
+    def __repr__(self) -> str:
+        return f"<{type(self).__name__} nseq={len(self._rows)} alen={len(self)}>"
+
+    @property
+    def names(self) -> tuple:
+        return tuple(self._names)
+
+    @property
+    def alignment(self) -> tuple:
+        return tuple(self._rows)
+
+    def write(self, fh, format: str = "stockholm") -> None:
+        """Write the alignment to a file object (binary or text) in Stockholm format, as Easel's writer prints it."""
+        if format != "stockholm":
+            raise ValueError(f"unsupported MSA format: {format!r} (only 'stockholm')")
+        fh.write(self._stockholm() if isinstance(fh, io.TextIOBase) else self._stockholm().encode())
+
+    def _stockholm(self) -> str:
+        import ctypes as C
+        from . import _lib
+        n = len(self._rows)
+        arr = lambda xs: (C.c_char_p * max(n, 1))(*[x.encode() if x else None for x in xs])
+        names, rows = arr(self._names), arr(self._rows)
+        accs, descs = arr(self._accs), arr(self._descs)
+        pps = arr(self.posterior_probabilities) if self.posterior_probabilities is not None else None
+        enc = lambda x: x.encode() if x else None
+        args = (n, len(self), names, accs, descs, rows, pps, enc(self.secondary_structure), enc(self.pp_consensus),
+                enc(self.reference))
+        fn = _lib.lib().p7x_msa_write_stockholm
+        size = fn(*args, None, 0)
+        if size < 0:
+            raise ValueError(_lib.last_error())
+        buf = C.create_string_buffer(int(size) + 1)
+        fn(*args, buf, size + 1)
+        return buf.raw[:size].decode()
+
+
+class TextMSA(MSA):
+    """An alignment of text sequences (reference ``easel.pyx`` ``TextMSA``)."""
+
+    @property
+    def sequences(self) -> List[TextSequence]:
+        return [TextSequence(name=nm, description=d, accession=a, sequence=r)
+                for nm, r, d, a in zip(self._names, self._rows, self._descs, self._accs)]
+
+    def digitize(self, alphabet: Alphabet) -> "DigitalMSA":
+        return DigitalMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
+                                     self.pp_consensus, self.reference, self.secondary_structure, alphabet=alphabet)
+
+
+class DigitalMSA(MSA):
+    """An alignment of digital sequences (reference ``easel.pyx`` ``DigitalMSA``).  Gap characters are digitised to
+    the alphabet's gap code; ``alignment`` gives the rows as text, as the reference textizes them."""
+
+    def __init__(self, alphabet: Alphabet, name: Optional[str] = None, description: Optional[str] = None,
+                 accession: Optional[str] = None, sequences: Optional[Iterable] = None):
+        self.alphabet = alphabet
+        super().__init__(name, description, accession, sequences)
+
+    @property
+    def sequences(self) -> List[DigitalSequence]:
+        gap = self.alphabet.symbols[self.alphabet.K]
+        return [DigitalSequence(self.alphabet, name=nm, description=d, accession=a,
+                                sequence=self.alphabet.encode(r.upper().replace(".", gap).replace("-", gap)))
+                for nm, r, d, a in zip(self._names, self._rows, self._descs, self._accs)]
+
+    def textize(self) -> TextMSA:
+        return TextMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
+                                  self.pp_consensus, self.reference, self.secondary_structure)

@@ -22,7 +22,7 @@ from . import _lib
 from .easel import Alphabet, DigitalSequenceBlock, SequenceFile
 from .plan7 import HMM, LongTargetsPipeline, OptimizedProfile, Pipeline, Profile, SequenceDatabase, TopHits
 
-__all__ = ["hmmsearch", "hmmscan", "nhmmer", "hmmpress", "make_chunks", "ShardedDatabase", "ReplicatedDatabase"]
+__all__ = ["hmmsearch", "hmmscan", "nhmmer", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase", "ReplicatedDatabase"]
 
 
 def make_chunks(block: DigitalSequenceBlock, n: int) -> List[DigitalSequenceBlock]:
@@ -988,3 +988,22 @@ def nhmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = 
                     fut.result()
                 except BaseException:           # noqa: BLE001
                     pass
+
+
+def hmmalign(hmm, sequences, *, cpus: int = 0, digitize: bool = False, trim: bool = False, all_consensus_cols: bool = True,
+             device: int = 0):
+    """Align sequences to a model and return the MSA (reference ``hmmer/_hmmalign.py``; upstream ``hmmalign``).
+
+    The traces of all sequences are computed in one call on the device (``p7x_align.hip``), which aligns many
+    sequences side by side; ``cpus`` is the number of worker threads of the host twin for the sequences the device
+    flags (0: the library's default).  Returns a `~pyhmmer_amd.easel.TextMSA`, or a `~pyhmmer_amd.easel.DigitalMSA`
+    with ``digitize``.
+    """
+    from .plan7 import TraceAligner
+    if cpus < 0:
+        raise ValueError(f"invalid number of CPUs: {cpus!r}")
+    if not isinstance(sequences, DigitalSequenceBlock):
+        sequences = DigitalSequenceBlock(hmm.alphabet, sequences)
+    aligner = TraceAligner(device=device, cpus=cpus)
+    traces = aligner.compute_traces(hmm, sequences)
+    return aligner.align_traces(hmm, sequences, traces, digitize=digitize, trim=trim, all_consensus_cols=all_consensus_cols)

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import re
 import sys
 import weakref
 from typing import Iterable, Iterator, List, Optional, Sequence, Union
@@ -28,6 +29,7 @@ from .errors import (AlphabetMismatch, AllocationError, InvalidParameter, Missin
 __all__ = [
     "HMM", "HMMFile", "HMMPressedFile", "Background", "Profile", "OptimizedProfile", "OptimizedProfileBlock", "EvalueParameters", "Cutoffs",
     "Pipeline", "LongTargetsPipeline", "SequenceDatabase", "TopHits", "Hit", "Domain", "Domains", "Alignment",
+    "Trace", "Traces", "TraceAligner",
 ]
 
 CUTOFF_UNSET = -99999.0
@@ -2460,3 +2462,200 @@ class SequenceDatabase:
         if bias:
             out["filtersc"] = bs
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------- hmmalign
+_T_M, _T_D, _T_I, _T_S, _T_N, _T_B, _T_E, _T_C, _T_T, _T_J = range(1, 11)      # p7T_* (p7_trace.pxd)
+
+
+class Trace:
+    """A state path of one sequence through a model (reference ``plan7.pyx:9280-9540``, ``P7_TRACE``): states ``st``,
+    nodes ``k`` and residue positions ``i`` in forward order, and -- for traces computed by `TraceAligner` -- the
+    posterior probability of every step (0 where nothing is emitted)."""
+
+    __slots__ = ("st", "k", "i", "_pp", "_M", "_L", "_device")
+
+    def __init__(self, posteriors: bool = False):
+        self.st = np.zeros(0, dtype=np.int8)
+        self.k = np.zeros(0, dtype=np.int32)
+        self.i = np.zeros(0, dtype=np.int32)
+        self._pp = np.zeros(0, dtype=np.float32) if posteriors else None
+        self._M = self._L = 0
+        self._device = False
+
+    @classmethod
+    def from_sequence(cls, sequence) -> "Trace":
+        """The trace of a sequence aligned to itself: B, one match state per residue, E (``M = L = len(sequence)``)."""
+        n = len(sequence)
+        self = cls()
+        self.st = np.array([_T_B] + [_T_M] * n + [_T_E], dtype=np.int8)
+        self.k = np.array([0] + list(range(1, n + 1)) + [0], dtype=np.int32)
+        self.i = self.k.copy()
+        self._M = self._L = n
+        return self
+
+    def __repr__(self) -> str:
+        return f"<{type(self).__name__} M={self._M!r} L={self._L!r}>"
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, Trace):
+            return NotImplemented
+        if (self._M, self._L) != (other._M, other._L) or not (np.array_equal(self.st, other.st) and
+                                                            np.array_equal(self.k, other.k) and np.array_equal(self.i, other.i)):
+            return False
+        if self._pp is not None and other._pp is not None:
+            return bool(np.array_equal(self._pp, other._pp))
+        return True
+
+    __hash__ = None
+
+    @property
+    def M(self) -> int:
+        return self._M
+
+    @property
+    def L(self) -> int:
+        return self._L
+
+    @property
+    def posterior_probabilities(self) -> Optional[np.ndarray]:
+        return self._pp
+
+    def expected_accuracy(self) -> float:
+        """``p7_trace_GetExpectedAccuracy``: the sum of the posterior probabilities along the trace."""
+        if self._pp is None:
+            raise ValueError("trace has no posterior probabilities")
+        acc = np.float32(0.0)
+        for p in self._pp:
+            acc = np.float32(acc + p)
+        return float(acc)
+
+
+class Traces(list):
+    """A list of `Trace` objects (reference ``plan7.pyx:9541-9744``); membership and ``index`` compare contents."""
+
+    # compute_traces: traces kept from the device, sequences the device flagged and the host twin aligned again, device
+    # rounds, the largest device workspace (bytes) a round used
+    ndevice: int = 0
+    nflagged: int = 0
+    rounds: int = 0
+    workspace_bytes: int = 0
+
+    def __init__(self, iterable: Iterable = ()):
+        super().__init__(iterable)
+
+    def __getitem__(self, index):
+        out = super().__getitem__(index)
+        return Traces(out) if isinstance(index, slice) else out
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}({list.__repr__(self)})"
+
+    def index(self, value, start: int = 0, stop: int = sys.maxsize) -> int:
+        return super().index(value, start, stop)
+
+    def copy(self) -> "Traces":
+        return Traces(self)
+
+
+class TraceAligner:
+    """Aligns sequences to a model (reference ``plan7.pyx:9745-9925``; upstream ``p7_tracealign_computeTraces`` and
+    ``p7_tracealign_Seqs``).  The traces are computed on the device (``p7x_align.hip``); without a device the call raises
+    `~pyhmmer_amd.errors.DeviceUnavailable` (the test seam ``host_align`` selects the host twin)."""
+
+    def __init__(self, device: int = 0, cpus: int = 0):
+        self.device = device
+        self.cpus = cpus          # workers of the host twin (the sequences it repeats); 0: the library's default
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}()"
+
+    def __reduce__(self):
+        return type(self), (self.device, self.cpus)
+
+    @staticmethod
+    def _check(hmm: HMM, sequences: DigitalSequenceBlock) -> None:
+        if not hmm.alphabet == sequences.alphabet:
+            raise AlphabetMismatch(hmm.alphabet, sequences.alphabet)
+        hmm.validate(tolerance=1e-3)
+
+    def compute_traces(self, hmm: HMM, sequences: DigitalSequenceBlock) -> Traces:
+        traces = Traces()
+        if len(sequences) == 0:
+            return traces
+        self._check(hmm, sequences)
+        om = OptimizedProfile(hmm, Background(hmm.alphabet), 400)
+        pk = sequences.packed()
+        lib = _lib.lib()
+        h = C.c_void_p()
+        st = lib.p7x_tracealign_compute(om._handle, self.device, pk.dsq.ctypes.data, pk.offsets.ctypes.data,
+                                        pk.lengths.ctypes.data, pk.n, int(self.cpus), C.byref(h))
+        if st != 0:
+            detail = _lib.last_error()
+            m = re.search(r"sequence (\d+)", detail)
+            if m and int(m.group(1)) < len(sequences):
+                detail = detail.replace(m.group(0), f"sequence {sequences[int(m.group(1))].name!r}")
+            raise status_to_exception(st, "p7x_tracealign_compute", detail)
+        try:
+            N, M, L, status, origin = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint8()
+            sc = np.zeros(2, dtype=np.float32)
+            for idx in range(pk.n):
+                lib.p7x_traces_get(h, idx, C.byref(N), C.byref(M), C.byref(L), sc.ctypes.data, C.byref(status), C.byref(origin))
+                t = Trace(posteriors=True)
+                n = N.value
+                t.st, t.k, t.i = np.empty(n, np.int8), np.empty(n, np.int32), np.empty(n, np.int32)
+                t._pp = np.empty(n, np.float32)
+                lib.p7x_traces_copy(h, idx, t.st.ctypes.data, t.k.ctypes.data, t.i.ctypes.data, t._pp.ctypes.data)
+                t._M, t._L, t._device = M.value, L.value, bool(origin.value & 2)
+                traces.append(t)
+            stats = np.zeros(4, dtype=np.int64)
+            lib.p7x_traces_stats(h, stats.ctypes.data)
+            traces.ndevice, traces.nflagged, traces.rounds, traces.workspace_bytes = (int(x) for x in stats)
+        finally:
+            lib.p7x_traces_destroy(h)
+        return traces
+
+    def align_traces(self, hmm: HMM, sequences: DigitalSequenceBlock, traces: Traces, digitize: bool = False,
+                     trim: bool = False, all_consensus_cols: bool = False):
+        from .easel import DigitalMSA, TextMSA
+        cls = DigitalMSA if digitize else TextMSA
+        nseq, ntr = len(sequences), len(traces)
+        if nseq != ntr:
+            raise ValueError(f"Sequences and traces lengths mismatch ({nseq} sequences, {ntr} traces)")
+        if nseq == 0:
+            return DigitalMSA(hmm.alphabet) if digitize else TextMSA()
+        self._check(hmm, sequences)
+        flags = (1 if trim else 0) | (2 if all_consensus_cols else 0) | (4 if digitize else 0)
+        toff = np.zeros(nseq + 1, dtype=np.int64)
+        toff[1:] = np.cumsum([len(t.st) for t in traces])
+        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt) for x in xs]) if xs else np.zeros(0, dt))
+        st = cat([t.st for t in traces], np.int8)
+        k = cat([t.k for t in traces], np.int32)
+        i = cat([t.i for t in traces], np.int32)
+        pp = cat([t._pp if t._pp is not None else np.zeros(len(t.st), np.float32) for t in traces], np.float32)
+        origin = np.array([(1 if t._pp is not None else 0) | (2 if t._device else 0) for t in traces], dtype=np.uint8)
+        om = OptimizedProfile(hmm, Background(hmm.alphabet), 400) if origin.any() and (origin & 2).any() else None
+        pk = sequences.packed()
+        cs = (" " + hmm.consensus_structure + "\0").encode() if hmm.consensus_structure else None
+        lib = _lib.lib()
+        h = C.c_void_p()
+        stc = lib.p7x_msa_from_traces(hmm.M, nseq, st.ctypes.data, k.ctypes.data, i.ctypes.data, pp.ctypes.data, toff.ctypes.data,
+                                      origin.ctypes.data, pk.dsq.ctypes.data, pk.offsets.ctypes.data, pk.lengths.ctypes.data,
+                                      hmm.alphabet.type_code, cs, flags, om._handle if om is not None else None, C.byref(h))
+        if stc != 0:
+            raise status_to_exception(stc, "p7x_msa_from_traces", _lib.last_error())
+        try:
+            alen = int(lib.p7x_msa_alen(h))
+            buf = C.create_string_buffer(alen + 1)
+
+            def get(idx, which):
+                lib.p7x_msa_get(h, idx, which, buf, alen + 1)
+                return buf.value.decode()
+            rows = [get(r, 0) for r in range(nseq)]
+            pps = [get(r, 1) for r in range(nseq)]
+            pp_cons, rf, ss = get(0, 2), get(0, 3), get(0, 4)
+        finally:
+            lib.p7x_msa_destroy(h)
+        return cls._from_rows([s.name for s in sequences], rows, [s.description or "" for s in sequences],
+                              [s.accession or "" for s in sequences], pps if any(pps) else None, pp_cons or None, rf or None,
+                              ss or None, alphabet=hmm.alphabet if digitize else None)
