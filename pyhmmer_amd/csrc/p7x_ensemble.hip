@@ -555,16 +555,11 @@ __global__ void __launch_bounds__(64) ens_walk_kernel(const EnsArgs a)
 static int ens_forward_launch(int C, const EnsArgs &a, const int *d_reg_list, int n, hipStream_t st)
 {
   if (n <= 0) return P7X_OK;
-#define P7X_ENS_CASE(CC) case CC: hipLaunchKernelGGL(ens_forward_kernel<CC>, dim3((unsigned) n), dim3(64), 0, st, a, d_reg_list); break;
-  switch (C) {
-    P7X_ENS_CASE(1) P7X_ENS_CASE(2) P7X_ENS_CASE(3) P7X_ENS_CASE(4) P7X_ENS_CASE(5) P7X_ENS_CASE(6) P7X_ENS_CASE(8) P7X_ENS_CASE(10)
-    P7X_ENS_CASE(12) P7X_ENS_CASE(16) P7X_ENS_CASE(20) P7X_ENS_CASE(24) P7X_ENS_CASE(32) P7X_ENS_CASE(48) P7X_ENS_CASE(64)
-    P7X_ENS_CASE(96) P7X_ENS_CASE(128)
-    default: set_error("model too long for the ensemble kernel"); return P7X_EINVAL;
-  }
-#undef P7X_ENS_CASE
-  P7X_HIP(hipGetLastError());
-  return P7X_OK;
+  return node_tier_dispatch(C, "model too long for the ensemble kernel", [&](auto tier) -> int {
+    hipLaunchKernelGGL(ens_forward_kernel<decltype(tier)::value>, dim3((unsigned) n), dim3(64), 0, st, a, d_reg_list);
+    P7X_HIP(hipGetLastError());
+    return P7X_OK;
+  });
 }
 
 static int ens_walk_launch(const EnsArgs &a, hipStream_t st)

@@ -1,4 +1,4 @@
-// p7x_envscore.hip -- host side of the envelope kernel (p7x_envelope.hip): batches the envelope requests of one search,
+// p7x_envscore.hip -- host side of the envelope kernel (p7x_envkernel.hpp): batches the envelope requests of one search,
 // runs env_kernel on a leased stream and hands the results (scores, null2 odds, optimal-accuracy traces) back to the
 // host stage (p7x_domaindef.cpp / p7x_tophits.cpp) through the EnvelopeScorer interface.
 #include "p7x_wave.hpp"
@@ -61,7 +61,7 @@ size_t align_budget_bytes() { return env_budget_bytes(OPT_ALIGN_WORKSPACE_GB); }
 
 class DeviceEnvelopeScorer final : public EnvelopeScorer {
 public:
-  // align: the requests are whole sequences for hmmalign's kernel (p7x_align.hip) instead of envelopes for env_kernel
+  // align: the requests are whole sequences for env_kernel's alignment mode (hmmalign) instead of envelopes
   DeviceEnvelopeScorer(DeviceCtx *ctx, const p7x_seqdb *db, bool align = false) : ctx_(ctx), db_(db), align_(align) {}
   ~DeviceEnvelopeScorer() override { if (lease_) { if (lease_->stream) (void) hipStreamSynchronize(lease_->stream); release_env_buffers(lease_); } }
 
@@ -164,12 +164,12 @@ public:
         JobMeta &m = meta_[j];
         if (m.nenv == 0) continue;
         int cap_blocks = 0;
-        if ((st = (align_ ? align_max_blocks : env_max_blocks)(m.C, jobs[j].om->p.Kp + 1, ctx_->num_cu, &cap_blocks)) != P7X_OK) return st;
+        if ((st = env_max_blocks(align_ ? EnvMode::Align : EnvMode::Envelope, m.C, jobs[j].om->p.Kp + 1, ctx_->num_cu, &cap_blocks)) != P7X_OK) return st;
         // the jobs share the resident blocks in proportion to their envelopes; a job with more envelopes than wavefronts
         // hands them out longest first (EnvArgs::order / cursor)
         const int share = (int) std::max<int64_t>(1, (int64_t) cap_blocks * m.nenv / nenv_tot);
         m.nblocks = std::max(1, std::min(share, (m.nenv + env_waves(m.C) - 1) / env_waves(m.C)) / shrink);
-        m.stride = (align_ ? align_work_floats : env_work_floats)(m.C, class_Lmax[m.C]);
+        m.stride = env_work_floats(m.C, class_Lmax[m.C]);
         work_floats += (size_t) m.nblocks * env_waves(m.C) * m.stride;
       }
       // (envelopes: a pooled workspace that is already large enough is used at this occupancy; hmmalign keeps to its budget)
@@ -263,7 +263,8 @@ public:
       ArgRun<EnvArgs> ar;
       ar.host = h_args + run.first; ar.dev = eb->d_in + o_args + (size_t) run.first * sizeof(EnvArgs);
       ar.stride = (uint32_t) sizeof(EnvArgs); ar.n = run.second;
-      if ((st = (align_ ? align_launch : env_launch)(ar, s)) != P7X_OK) return st;
+      const EnvMode mode = align_ ? EnvMode::Align : ar.at(0).env_emis ? EnvMode::LongTarget : EnvMode::Envelope;
+      if ((st = env_launch(mode, ar, s)) != P7X_OK) return st;
     }
     tick("launches");
     P7X_HIP(hipMemcpyAsync(eb->h_out, eb->d_out, out_bytes, hipMemcpyDeviceToHost, s));

@@ -1,5 +1,6 @@
 // p7x_kernels.hpp -- launch interfaces of the HIP kernels (one translation unit per kernel family).
 #pragma once
+#include <type_traits>
 #include "p7x_device.hpp"
 
 namespace p7x {
@@ -86,6 +87,20 @@ int  msv_exact_launch(int R, int K, const ArgRun<MsvArgs> &amb, int num_cu, hipS
 
 // ---- wave-per-sequence stages (p7x_vitfwd.hip): Viterbi filter, Forward / Backward parsers
 // Node k = z*C + c + 1 lives in lane z, chunk position c; device tables are stored [c*64 + z].
+// The tiers of C, nodes per lane, that the wave-per-sequence kernels, the envelope / alignment kernel and the ensemble
+// fill are instantiated for (M <= 64 C; the last one: M <= 8192): every dispatch on C and vit_pick_C() expand this list.
+#define P7X_NODE_TIERS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(16) X(20) X(24) X(32) X(48) X(64) X(96) X(128)
+// f(std::integral_constant<int, C>()) where C is a tier (f picks and launches its kernel's instantiation for it), else
+// the error <too_long>
+template <class F> int node_tier_dispatch(int C, const char *too_long, F &&f)
+{
+  switch (C) {
+#define P7X_TIER_CASE(CC) case CC: return f(std::integral_constant<int, CC>());
+    P7X_NODE_TIERS(P7X_TIER_CASE)
+#undef P7X_TIER_CASE
+    default: set_error(too_long); return P7X_EINVAL;
+  }
+}
 struct WaveSeqArgs {
   int M, C;                 // C = nodes per lane, Mpad = 64*C
   const void *trans;        // Viterbi: uint4[Mpad] (8 x int16); Forward: float4[2*Mpad] (8 x f32)
@@ -148,7 +163,7 @@ bool vitpk_pick(int M, int *T, int *P);
 void vitpk_build_tables(const Profile &p, int T, int P, std::vector<uint32_t> &trans, std::vector<uint32_t> &emis);
 int  vitpk_launch(int T, int P, const ArgRun<VitPkArgs> &a, int num_cu, hipStream_t st);
 
-// ---- envelope rescoring (p7x_envelope.hip): Forward + Backward + decoding/null2/optimal accuracy + traceback,
+// ---- envelope rescoring and hmmalign (p7x_envkernel.hpp, instantiated by p7x_envelope.hip and p7x_align.hip): Forward + Backward + decoding/null2/optimal accuracy + traceback,
 // one domain envelope per wavefront.  Trace steps come back in traceback order (T first): tr_a = state | k << 8,
 // tr_i = residue index inside the envelope (1..Ld, as the traceback saw it), tr_pp = posterior of that step.
 struct EnvArgs {
@@ -182,19 +197,29 @@ struct EnvArgs {
 // nodes per lane on, four (one per SIMD, 512 registers): the row state of two would spill to scratch, which made the
 // envelopes of long models 1.4-3.6x slower than half the occupancy does (scripts/env_by_length.py)
 constexpr int env_waves(int C) { return C >= 8 ? 4 : 8; }
-size_t env_work_floats(int C, int Lmax);
-int env_max_blocks(int C, int nrows, int num_cu, int *nblocks);
-// every record of the run has the same C and nrows; grid.x = the widest job's nblocks
-int env_launch(const ArgRun<EnvArgs> &a, hipStream_t st);
-// ---- hmmalign (p7x_align.hip): the envelope kernel's four steps over whole sequences, float posteriors on the trace,
-// no null2.  Same arguments (EnvArgs, env_len = env_L), same workspace carving.
-size_t align_work_floats(int C, int Lmax);
+// What env_kernel is instantiated for: a protein envelope; a long-target envelope (EnvArgs::env_emis, out_orig); hmmalign:
+// the four steps over whole sequences (env_len = env_L), float posteriors on the trace, no null2
+enum class EnvMode { Envelope, LongTarget, Align };
+// floats per wavefront of EnvArgs::work, every mode: the carving at the top of env_kernel
+inline size_t env_work_floats(int C, int Lmax)
+{
+  const size_t rows = (size_t) Lmax + 1, Mpad = (size_t) 64 * C;
+  size_t f = 2 * rows * Mpad + rows * (6 + 6 + 5 + 3 + 1);
+  f += (rows * Mpad + 1) / 2;          // back-pointers, near-tie flags and posterior digits: 16 bits per cell
+  return (f + 63) & ~(size_t) 63;
+}
+// Align: as the envelope modes, through align_max_blocks / align_launch of p7x_align.hip
+int env_max_blocks(EnvMode mode, int C, int nrows, int num_cu, int *nblocks);
+// every record of the run has the same C, nrows and mode; grid.x = the widest job's nblocks
+int env_launch(EnvMode mode, const ArgRun<EnvArgs> &a, hipStream_t st);
 // Half-width of the guard band around a PP digit boundary, in posterior units.  The device's float posteriors differ from
 // the host twin's by an error that grows with the model (at most 1.25e-6 for the fixture models of <= 262 nodes against the
 // proteome, 7.5e-6 at M = 6,000; about 1e-9 M): the band is at least three times that, and never below 1e-5.  A residue on
 // the trace whose posterior lies within it flags the sequence (kernel); a PP_cons column whose mean does is averaged
 // again over host-twin posteriors (p7x_tracealign.cpp).
 __host__ __device__ inline float align_pp_guard(int M) { return 1.0e-5f + 2.5e-9f * (float) M; }
+// The band of pp_code_guarded() (p7x_oaguard.hpp) around a PP digit boundary, in units of 10 p + 0.5, that this guard makes
+__host__ __device__ inline float align_pp_band(int M) { return 0.5f - 10.0f * align_pp_guard(M); }
 int align_max_blocks(int C, int nrows, int num_cu, int *nblocks);
 int align_launch(const ArgRun<EnvArgs> &a, hipStream_t st);
 

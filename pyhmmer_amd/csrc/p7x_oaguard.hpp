@@ -1,5 +1,5 @@
-// p7x_oaguard.hpp -- device helpers of the optimal-accuracy step shared by the envelope kernel (p7x_envelope.hip) and
-// the alignment kernel (p7x_align.hip): gates of the OA recursion, the posterior digit of the alignment display and the
+// p7x_oaguard.hpp -- device helpers of the optimal-accuracy step of the envelope / alignment kernel (p7x_envkernel.hpp):
+// gates of the OA recursion, the posterior digit of the alignment display and the
 // near-tie guards that tell the host which choices its own summation order has to decide.
 #pragma once
 #include "p7x_wave.hpp"

@@ -101,7 +101,7 @@ int device_traces(const p7x_oprofile *om, int device, const uint8_t *dsq, const 
   std::vector<std::vector<EnvelopeResult>> res;
   for (size_t pos = 0; pos < order.size();) {
     const int first = order[pos], Lr = lengths[first];
-    if (align_work_floats(C, Lr) * 4 * (size_t) env_waves(C) > budget) {
+    if (env_work_floats(C, Lr) * 4 * (size_t) env_waves(C) > budget) {
       char buf[200];
       std::snprintf(buf, sizeof buf, "hmmalign: sequence %d (L = %d) alone does not fit the alignment workspace (%.1f GB)", first, Lr, budget / 1e9);
       set_error(buf);

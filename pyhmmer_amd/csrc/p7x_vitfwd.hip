@@ -648,7 +648,9 @@ __global__ void __launch_bounds__(kWsBlock) bck_kernel(const ArgRef ref)
 }
 
 // ---------------------------------------------------------------------------- host side
-static const int kCList[] = { 1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64, 96, 128 };      // M <= 8192
+#define P7X_TIER_ITEM(CC) CC,
+static const int kCList[] = { P7X_NODE_TIERS(P7X_TIER_ITEM) };      // M <= 8192
+#undef P7X_TIER_ITEM
 
 int vit_pick_C(int M)
 {
@@ -694,56 +696,19 @@ static int launch_ws(K kernel, const ArgRun<WaveSeqArgs> &a, size_t lds_bytes, i
   return P7X_OK;
 }
 
-#define P7X_C_SWITCH(KERNEL, BYTES_PER_NODE, EBYTES)                                                        \
-  switch (C) {                                                                                              \
-    case 1:  return launch_ws(KERNEL<1>,  a, (size_t) 64 * 1  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 2:  return launch_ws(KERNEL<2>,  a, (size_t) 64 * 2  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 3:  return launch_ws(KERNEL<3>,  a, (size_t) 64 * 3  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 4:  return launch_ws(KERNEL<4>,  a, (size_t) 64 * 4  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 5:  return launch_ws(KERNEL<5>,  a, (size_t) 64 * 5  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 6:  return launch_ws(KERNEL<6>,  a, (size_t) 64 * 6  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 8:  return launch_ws(KERNEL<8>,  a, (size_t) 64 * 8  * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 10: return launch_ws(KERNEL<10>, a, (size_t) 64 * 10 * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 12: return launch_ws(KERNEL<12>, a, (size_t) 64 * 12 * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 16: return launch_ws(KERNEL<16>, a, (size_t) 64 * 16 * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 20: return launch_ws(KERNEL<20>, a, (size_t) 64 * 20 * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 24: return launch_ws(KERNEL<24>, a, (size_t) 64 * 24 * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 32: return launch_ws(KERNEL<32>, a, (size_t) 64 * 32 * (BYTES_PER_NODE + nrows * EBYTES), num_cu, st); \
-    case 48: return launch_ws(KERNEL<48>, a, (size_t) 64 * 48 * BYTES_PER_NODE, num_cu, st);                \
-    case 64: return launch_ws(KERNEL<64>, a, (size_t) 64 * 64 * BYTES_PER_NODE, num_cu, st);                \
-    case 96: return launch_ws(KERNEL<96>, a, (size_t) 64 * 96 * BYTES_PER_NODE, num_cu, st);                \
-    case 128: return launch_ws(KERNEL<128>, a, (size_t) 64 * 128 * BYTES_PER_NODE, num_cu, st);             \
-    default: set_error("model too long for the wave-per-sequence kernels (M > 8192)"); return P7X_EINVAL;  \
-  }
+// Dynamic LDS of the parsers: the transitions, 32 bytes per node (M > 4096: read through L2), and the emission rows while
+// they fit beside them (M <= 1024: the instantiations without EG)
+static size_t fwd_lds_bytes(int C, int nrows) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? nrows * 4 : 0)); }
 
 int vit_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
-  P7X_C_SWITCH(vit_kernel, 16, 2)
+  return node_tier_dispatch(C, "model too long for the wave-per-sequence kernels (M > 8192)", [&](auto tier) {
+    constexpr int CC = decltype(tier)::value;      // transitions 16 bytes per node; the emission rows up to M = 2048
+    return launch_ws(vit_kernel<CC>, a, (size_t) 64 * CC * (16 + (CC <= 32 ? nrows * 2 : 0)), num_cu, st);
+  });
 }
-
-#define P7X_CF_SWITCH(KERNEL)                                                                               \
-  switch (C) {                                                                                              \
-    case 1:  return launch_ws(KERNEL<1>,  a, (size_t) 64 * 1  * (32 + nrows * 4), num_cu, st);           \
-    case 2:  return launch_ws(KERNEL<2>,  a, (size_t) 64 * 2  * (32 + nrows * 4), num_cu, st);           \
-    case 3:  return launch_ws(KERNEL<3>,  a, (size_t) 64 * 3  * (32 + nrows * 4), num_cu, st);           \
-    case 4:  return launch_ws(KERNEL<4>,  a, (size_t) 64 * 4  * (32 + nrows * 4), num_cu, st);           \
-    case 5:  return launch_ws(KERNEL<5>,  a, (size_t) 64 * 5  * (32 + nrows * 4), num_cu, st);           \
-    case 6:  return launch_ws(KERNEL<6>,  a, (size_t) 64 * 6  * (32 + nrows * 4), num_cu, st);           \
-    case 8:  return launch_ws(KERNEL<8>,  a, (size_t) 64 * 8  * (32 + nrows * 4), num_cu, st);           \
-    case 10: return launch_ws(KERNEL<10>, a, (size_t) 64 * 10 * (32 + nrows * 4), num_cu, st);           \
-    case 12: return launch_ws(KERNEL<12>, a, (size_t) 64 * 12 * (32 + nrows * 4), num_cu, st);           \
-    case 16: return launch_ws(KERNEL<16>, a, (size_t) 64 * 16 * (32 + nrows * 4), num_cu, st);           \
-    case 20: return launch_ws(KERNEL<20, true>, a, (size_t) 64 * 20 * 32, num_cu, st);                     \
-    case 24: return launch_ws(KERNEL<24, true>, a, (size_t) 64 * 24 * 32, num_cu, st);                     \
-    case 32: return launch_ws(KERNEL<32, true>, a, (size_t) 64 * 32 * 32, num_cu, st);                     \
-    case 48: return launch_ws(KERNEL<48, true>, a, (size_t) 64 * 48 * 32, num_cu, st);                     \
-    case 64: return launch_ws(KERNEL<64, true>, a, (size_t) 64 * 64 * 32, num_cu, st);                     \
-    case 96: return launch_ws(KERNEL<96, true>, a, (size_t) 256, num_cu, st);                              \
-    case 128: return launch_ws(KERNEL<128, true>, a, (size_t) 256, num_cu, st);                            \
-    default: set_error("model too long for the Forward/Backward kernels (M > 8192)"); return P7X_EINVAL;   \
-  }
 
 int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st)
 {
@@ -779,39 +744,26 @@ int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st)
     P7X_HIP(hipGetLastError());
     return P7X_OK;
   };
-  switch (C) {
-    case 1:  return go(msv_wave_kernel<1>);
-    case 2:  return go(msv_wave_kernel<2>);
-    case 3:  return go(msv_wave_kernel<3>);
-    case 4:  return go(msv_wave_kernel<4>);
-    case 5:  return go(msv_wave_kernel<5>);
-    case 6:  return go(msv_wave_kernel<6>);
-    case 8:  return go(msv_wave_kernel<8>);
-    case 10: return go(msv_wave_kernel<10>);
-    case 12: return go(msv_wave_kernel<12>);
-    case 16: return go(msv_wave_kernel<16>);
-    case 20: return go(msv_wave_kernel<20>);
-    case 24: return go(msv_wave_kernel<24>);
-    case 32: return go(msv_wave_kernel<32>);
-    case 48: return go(msv_wave_kernel<48>);
-    case 64: return go(msv_wave_kernel<64>);
-    case 96: return go(msv_wave_kernel<96>);
-    case 128: return go(msv_wave_kernel<128>);
-    default: set_error("no wave-per-target MSV kernel for this model length"); return P7X_EINVAL;
-  }
+  return node_tier_dispatch(C, "no wave-per-target MSV kernel for this model length", [&](auto tier) { return go(msv_wave_kernel<decltype(tier)::value>); });
 }
 
 int fwd_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
-  P7X_CF_SWITCH(fwd_kernel)
+  return node_tier_dispatch(C, "model too long for the Forward/Backward kernels (M > 8192)", [&](auto tier) {
+    constexpr int CC = decltype(tier)::value;
+    return launch_ws(fwd_kernel<CC, (CC > 16)>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
+  });
 }
 int bck_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
-  P7X_CF_SWITCH(bck_kernel)
+  return node_tier_dispatch(C, "model too long for the Forward/Backward kernels (M > 8192)", [&](auto tier) {
+    constexpr int CC = decltype(tier)::value;
+    return launch_ws(bck_kernel<CC, (CC > 16)>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
+  });
 }
 
 } // namespace p7x

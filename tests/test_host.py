@@ -192,7 +192,7 @@ def test_envelope_kernel_isa_keeps_memory_round_trips_out_of_its_row_loops(tmp_p
         import isa_inner_loops
     finally:
         sys.path.pop(0)
-    for inst in ("ILi5ELb1ELb0E", "ILi3ELb1ELb0E", "ILi12ELb1ELb0E"):          # the benchmark's class, a short and a long one
+    for inst in ("ILi5ELb1ELNS_7EnvModeE0E", "ILi3ELb1ELNS_7EnvModeE0E", "ILi12ELb1ELNS_7EnvModeE0E"):          # the benchmark's class, a short and a long one
         loops = isa_inner_loops.loops(asm, "env_kernel" + inst)
         rows = [l for l in loops if l[4] >= 2 and l[2] > 200]           # row loops (the traceback walk, a pointer chase, is shorter)
         assert len(rows) >= 3, loops
