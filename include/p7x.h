@@ -302,6 +302,10 @@ int  p7x_debug_choice(const float *p, int n, uint32_t x, int *via_thresholds, in
  * summation order and in upstream's, and for every cell the integer thresholds of its choice points in both: out12[0] =
  * thresholds compared, [1] = largest difference / 2^32, [2 + b] = how many differ by more than 2^-(24 - b), b = 0..9. */
 int  p7x_debug_order_spread(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t i, int32_t j, int multihit, double *out12);
+/* Test seam of the host parsers in upstream's summation order (the rows-only Forward / Backward engines of the host stage,
+ * whose rows the region-scan guard scans again): the special-state rows of dsq1[1..L], multihit with the length model of L,
+ * fx / bx = (L+1) x [E,N,J,B,C,SCALE] floats each. */
+int  p7x_debug_parser_rows(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, float *fx, float *bx);
 /* Test seam of the long-target SSV scan's tables (host code, no device): the registers per lane R the kernel takes for this
  * model, the most a cell can lose in one row with a canonical residue (byte units), and the table it stages in LDS --
  * [parity][x < 4][q][lane][c] packed pairs (lo, hi) of bias - rb[x][k], register j = 4q + c of the lane holding nodes

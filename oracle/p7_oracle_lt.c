@@ -4,7 +4,7 @@
  * include/libhmmer/p7_pipeline.pxd:131-143; driven by LongTargetsPipeline._search_loop_longtarget,
  * src/pyhmmer/plan7.pyx:7541-7664), for ONE strand of ONE block of a target: dsq[1..L], the bottom strand already
  * reverse-complemented by the caller, as the reference hands it to the pipeline.  Plain scalar C, written apart from the
- * product's p7x_longtarget.inc.hpp and sharing no code with it; it builds on this directory's own filters
+ * product's p7x_longtarget_host.cpp and sharing no code with it; it builds on this directory's own filters
  * (p7o_ssv_longtarget, p7o_msv, p7o_bias_filter, p7o_fwd).  What it restates, from upstream p7_pipeline.c / p7_scoredata.c /
  * impl_sse/vitfilter.c / p7_domaindef.c:
  *

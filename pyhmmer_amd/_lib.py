@@ -18,7 +18,7 @@ CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libp7x.so"
 
 SOURCES = ["p7x_profile.cpp", "p7x_device.hip", "p7x_devimage.hip", "p7x_msv.hip", "p7x_vitfwd.hip", "p7x_vitpk.hip", "p7x_fwdpk.hip", "p7x_envelope.hip", "p7x_ensemble.hip", "p7x_ssvlong.hip", "p7x_longtarget.hip",
-           "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp"]
+           "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp"]
 
 
 def _hipcc() -> str:
@@ -233,6 +233,7 @@ _SIGNATURES = {
     "p7x_debug_log_of_float": (C.c_int, [C.c_int, _VP, _VP, C.c_size_t]),
     "p7x_debug_choice": (C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
     "p7x_debug_order_spread": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int, _VP]),
+    "p7x_debug_parser_rows": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP]),
     "p7x_debug_ssv_tables": (C.c_int64, [_VP, C.c_int, _VP, _VP, _VP, C.c_size_t]),
     "p7x_debug_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "p7x_longtargets_release_resident": (C.c_int, [C.c_int, C.c_uint64]),

@@ -12,7 +12,7 @@
 // Matrices are un-striped (node k at index k).  Where upstream's results depend on the order in which
 // the striped SSE code visits cells (tie-breaks in the OA traceback, cumulative sums in the stochastic
 // traceback) that visiting order is reproduced.  Runs only for ~1e-5 of random targets plus true homologs.
-#include "p7x_host.hpp"
+#include "p7x_hostdp.hpp"
 #include "p7x_choice.hpp"
 #include <algorithm>
 #include <atomic>
@@ -24,8 +24,6 @@
 #include <cstring>
 
 namespace p7x {
-
-int vit_pick_C(int M);          // p7x_vitfwd.hip: nodes per lane of the wave-per-target kernels, a function of M alone
 
 // optional host profile (option "host_profile"): accumulated nanoseconds per phase, printed by host_prof_dump()
 #define g_prof_on (debug_opt(OPT_HOST_PROFILE) > 0)
@@ -52,9 +50,6 @@ namespace {
 #else
 #define P7X_MULTIVERSION __attribute__((target_clones("avx2", "default")))
 #endif
-
-enum { sM = 1, sD = 2, sI = 3, sS = 4, sN = 5, sB = 6, sE = 7, sC = 8, sT = 9, sJ = 10 };   // p7T_* (p7_trace.pxd)
-enum { xE_ = 0, xN_ = 1, xJ_ = 2, xB_ = 3, xC_ = 4, xS_ = 5, NX = 6 };
 
 // ---------------------------------------------------------------- Easel "fast" RNG (esl_randomness_CreateFast)
 struct FastRng {
@@ -149,118 +144,16 @@ static inline float lanes_sum(float *v)
   return v[63];
 }
 
-// ---------------------------------------------------------------- the query in a given configuration
-// Long-target (nhmmer) variant of envelope rescoring, upstream rescore_isolated_domain(..., long_target = TRUE, ...)
-struct LongTargetOpts {
-  bool do_null2 = true;                // false: upstream passes scores_arr == NULL and the model is not re-parameterised
-  const float *match_prob = nullptr;   // [M+1][K] match emission probabilities of the core model (fwd_emissions_arr)
-  int max_env_extra = 20;              // an envelope is trimmed to its alignment +- this many residues
-};
+// ---------------------------------------------------------------- p7_Forward / p7_Backward
+// One body per direction and summation order.  Each is written once for both answers to "where does row r live":
+//   FULL   every DP row stays in the Matrix (row r at r): p7_Forward / p7_Backward, for decoding and the tracebacks;
+//   !FULL  only the special-state rows, the scale factors and the score come out: p7_ForwardParser / p7_BackwardParser.
+//          The lanes bodies then roll over two Matrix rows (row r at r & 1); the upstream bodies compute on their striped
+//          rows anyway and simply do not copy them out.
+// The bodies are inlined into plain cloned entry points below (target_clones does not go on templates).
+#define P7X_INLINE static inline __attribute__((always_inline))
+template <bool FULL> static inline int row_at(int r) { return FULL ? r : (r & 1); }
 
-struct Model {
-  const Profile *p;
-  int M;
-  float xf[4][2];                 // [E,N,J,C][MOVE,LOOP] for the current mode / length
-  const float *rf_over = nullptr; // [Kp][M+1] replacement match odds (long targets: composition-adjusted background)
-  const LongTargetOpts *lt = nullptr;
-  const float *tf(int t) const { return p->tf.data() + (size_t) t * (M + 1); }
-  const float *rf(int x) const { return (rf_over ? rf_over : p->rf_.data()) + (size_t) x * (M + 1); }
-  // Order of operations.  The sums whose result depends on the order of the float additions -- the D->D chains, the row
-  // sums xE / xB, the null2 expectation -- run in the order of the device kernels (p7x_envelope.hip, p7x_wave.hpp): lane z
-  // of a 64-lane wavefront owns the C consecutive nodes zC+1 .. zC+C, walks them in order, and the lanes are combined by
-  // the wavefront's scan / reduction trees (lanes_scan_up / lanes_scan_down / lanes_sum below).  Host twin and device
-  // therefore produce the same bits, and every discrete decision taken from them (optimal-accuracy traceback, the
-  // stochastic tracebacks' choices) is the same decision.  Upstream's own order (four striped lanes, serial D->D sweeps)
-  // is a third one; what the fixtures pin is reproduced by all of them.
-  int C = 1;                                        // nodes per lane: vit_pick_C(M), the device image's choice
-  float ddprod[64];                                 // product of the D->D transitions of a lane's nodes, in node order
-  // upstream = true (the default; option "host_order" = 1 selects the device's order instead): those sums run as
-  // impl_sse runs them -- four stripes, node k in stripe (k-1)/Q at position (k-1)%Q, serial D->D sweeps, row sums
-  // stripe by stripe and then (s0+s1)+(s2+s3) -- so that every float, and with it every decision, is the reference's.
-  // The host stage uses it for whatever it computes itself, in particular for the envelopes and regions the device
-  // flags as too close to call (near-tie guards of p7x_envelope.hip / p7x_ensemble.hip).
-  bool upstream = true;
-  int Q = 0;
-  std::vector<float> st;                            // [8][Q][4] transitions in the striped layout (padding: 0)
-  const float *sT(int t) const { return st.data() + (size_t) t * Q * 4; }
-  // [Kp][Q][4] match odds in the striped layout, of whatever rf() currently stands for (rebuilt when that changes: the
-  // long-target path swaps in composition-adjusted odds per envelope)
-  mutable std::vector<float> sr; mutable const float *sr_of = nullptr;
-  const float *sR(int x) const
-  {
-    const float *base = rf(0);
-    if (sr_of != base || sr.size() != (size_t) p->Kp * Q * 4) {
-      sr.assign((size_t) p->Kp * Q * 4, 0.0f);
-      for (int y = 0; y < p->Kp; ++y) {
-        const float *r = rf(y);
-        float *d = sr.data() + (size_t) y * Q * 4;
-        for (int q = 0; q < Q; ++q) for (int z = 0; z < 4; ++z) { const int k = q + 1 + z * Q; if (k <= M) d[q * 4 + z] = r[k]; }
-      }
-      sr_of = base;
-    }
-    return sr.data() + (size_t) x * Q * 4;
-  }
-  std::vector<float> rfT;                           // [M+1][kKpad] match odds, residue-minor (null2_by_trace)
-  static constexpr int kKpad = 24;
-  void prepare_rfT()
-  {
-    rfT.assign((size_t) (M + 1) * kKpad, 0.0f);
-    for (int x = 0; x < p->K && x < kKpad; ++x) { const float *r = rf(x); for (int k = 1; k <= M; ++k) rfT[(size_t) k * kKpad + x] = r[k]; }
-  }
-  void prepare(int order = -1)
-  {
-    upstream = order >= 0 ? order == 0 : debug_opt(OPT_HOST_ORDER) <= 0;
-    Q = p->Q4();
-    st.assign((size_t) 8 * Q * 4, 0.0f);
-    for (int t = 0; t < 8; ++t) {
-      const float *src = tf(t);
-      const int last = (t == 4 || t == 7) ? M - 1 : M;        // M -> D and D -> D do not leave node M
-      for (int q = 0; q < Q; ++q) for (int z = 0; z < 4; ++z) { const int k = q + 1 + z * Q; if (k <= last) st[((size_t) t * Q + q) * 4 + z] = src[k]; }
-    }
-    C = vit_pick_C(M);
-    if (C <= 0) C = (M + 63) / 64;                  // beyond the device kernels' reach: the same rule, continued
-    const float *tDD = tf(7);
-    for (int z = 0; z < 64; ++z) {
-      float pr = 1.0f;
-      for (int c = 0; c < C; ++c) { const int k = z * C + c + 1; pr *= (k <= M ? tDD[k] : 0.0f); }
-      ddprod[z] = pr;
-    }
-  }
-  void configure(bool multihit, int L)
-  { // p7_oprofile_ReconfigMultihit / ReconfigUnihit (+ ReconfigLength)
-    const float nj = multihit ? 1.0f : 0.0f;
-    xf[XE][MOVE] = multihit ? 0.5f : 1.0f;
-    xf[XE][LOOP] = multihit ? 0.5f : 0.0f;
-    const float pmove = (2.0f + nj) / ((float) L + 2.0f + nj), ploop = 1.0f - pmove;
-    for (int s : {XN, XJ, XC}) { xf[s][MOVE] = pmove; xf[s][LOOP] = ploop; }
-  }
-};
-
-// Full DP matrix: rows 0..L, per row three arrays of M+1 floats (M, I, D) plus the specials.
-struct Matrix {
-  int M = 0, L = 0;
-  std::vector<float> m, i, d, x, scratch;
-  float totscale = 0.0f;
-  bool own_scales = false;
-  void resize(int M_, int L_)
-  {
-    M = M_; L = L_;
-    const size_t n = (size_t) (L + 1) * (M + 2);
-    if (m.size() < n) { m.resize(n); i.resize(n); d.resize(n); }
-    if (x.size() < (size_t) (L + 1) * NX) x.resize((size_t) (L + 1) * NX);
-    if (scratch.size() < (size_t) (M + 4) + 4 * (size_t) (L + 1)) scratch.resize((size_t) (M + 4) + 4 * (size_t) (L + 1));
-  }
-  float *M_(int r) { return m.data() + (size_t) r * (M + 2); }
-  float *I_(int r) { return i.data() + (size_t) r * (M + 2); }
-  float *D_(int r) { return d.data() + (size_t) r * (M + 2); }
-  const float *M_(int r) const { return m.data() + (size_t) r * (M + 2); }
-  const float *I_(int r) const { return i.data() + (size_t) r * (M + 2); }
-  const float *D_(int r) const { return d.data() + (size_t) r * (M + 2); }
-  float &X(int r, int s) { return x[(size_t) r * NX + s]; }
-  float X(int r, int s) const { return x[(size_t) r * NX + s]; }
-};
-
-// ---------------------------------------------------------------- p7_Forward (full matrix)
 // dsq is 1-indexed over the envelope: residues dsq[1..L].
 // D(i,k) = M(i,k-1) tMD(k-1) + D(i,k-1) tDD(k-1), k = 1..M, given the finished M row; returns xE = sum_k M(i,k) + D(i,k).
 // EnvForward<C>::row (p7x_envelope.hip) operation for operation: every lane runs its own chain from a zero carry, the
@@ -289,10 +182,11 @@ static float dchain_forward(const Model &om, const float *__restrict mc, float *
   return lanes_sum(es);
 }
 
-P7X_MULTIVERSION int forward_full_lanes(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *ret_sc)
+template <bool FULL>
+P7X_INLINE int forward_lanes(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *ret_sc)
 {
   const int M = om.M;
-  ox.resize(M, L);
+  ox.resize(M, L, FULL ? -1 : 2);
   const float *__restrict bm = om.tf(0), *__restrict tMM = om.tf(1), *__restrict tIM = om.tf(2), *__restrict tDM = om.tf(3),
               *__restrict tMI = om.tf(5), *__restrict tII = om.tf(6);
   float *m0 = ox.M_(0), *i0 = ox.I_(0), *d0 = ox.D_(0);
@@ -302,8 +196,9 @@ P7X_MULTIVERSION int forward_full_lanes(const Model &om, const uint8_t *dsq, int
   ox.totscale = 0.0f; ox.own_scales = true;
   for (int r = 1; r <= L; ++r) {
     const float *__restrict rf = om.rf(dsq[r]);
-    const float *__restrict mp = ox.M_(r - 1), *__restrict ip = ox.I_(r - 1), *__restrict dp = ox.D_(r - 1);
-    float *__restrict mc = ox.M_(r), *__restrict ic = ox.I_(r), *__restrict dc = ox.D_(r);
+    const int rp = row_at<FULL>(r - 1), rc = row_at<FULL>(r);
+    const float *__restrict mp = ox.M_(rp), *__restrict ip = ox.I_(rp), *__restrict dp = ox.D_(rp);
+    float *__restrict mc = ox.M_(rc), *__restrict ic = ox.I_(rc), *__restrict dc = ox.D_(rc);
     mc[0] = ic[0] = dc[0] = 0.0f;
     for (int k = 1; k <= M; ++k) {
       float sv = xB * bm[k];
@@ -334,7 +229,6 @@ P7X_MULTIVERSION int forward_full_lanes(const Model &om, const uint8_t *dsq, int
   return P7X_OK;
 }
 
-// ---------------------------------------------------------------- p7_Backward (full matrix)
 // D(i,k) = base(k) + D(i,k+1) tDD(k), k = M..1 (D(i,M+1) = 0); on entry dc[k] = base(k).  The envelope kernel's d_chain:
 // every lane folds its nodes from the last to the first, the scan composes the lanes from 63 downwards, and each lane
 // then recomputes its chain from the carry it was handed.
@@ -356,7 +250,7 @@ static void dchain_backward(const Model &om, float *__restrict dc)
     for (int k = k1; k >= k0; --k) { dc[k] = dc[k] + w * tDD[k]; w = dc[k]; }
   }
 }
-// sum_k v(k) w(k) as the kernels form it: a lane's nodes in order, then the reduction tree (v = nullptr: sum of w)
+// sum_k v(k) w(k) as the kernels form it: a lane's nodes in order, then the reduction tree
 static float lanes_dot(const Model &om, const float *__restrict v, const float *__restrict w)
 {
   const int M = om.M, C = om.C;
@@ -370,10 +264,12 @@ static float lanes_dot(const Model &om, const float *__restrict v, const float *
   return lanes_sum(es);
 }
 
-P7X_MULTIVERSION int backward_full_lanes(const Model &om, const uint8_t *dsq, int L, const Matrix &fwd, Matrix &bck, float *ret_sc)
+// fx: Forward's special rows (its scale factors are Backward's until a row sum outgrows them: own_scales)
+template <bool FULL>
+P7X_INLINE int backward_lanes(const Model &om, const uint8_t *dsq, int L, const float *fx, Matrix &bck, float *ret_sc)
 {
   const int M = om.M;
-  bck.resize(M, L);
+  bck.resize(M, L, FULL ? -1 : 2);
   const float *__restrict bm = om.tf(0), *__restrict tMM = om.tf(1), *__restrict tIM = om.tf(2), *__restrict tDM = om.tf(3),
               *__restrict tMD = om.tf(4), *__restrict tMI = om.tf(5), *__restrict tII = om.tf(6);
   bck.own_scales = false;
@@ -383,13 +279,14 @@ P7X_MULTIVERSION int backward_full_lanes(const Model &om, const uint8_t *dsq, in
   float *__restrict me = bck.scratch.data();          // [M+3] work row (no allocation inside the multiversioned body)
   for (int k = 0; k <= M + 2; ++k) me[k] = 0.0f;
   {
-    float *__restrict mc = bck.M_(L), *__restrict ic = bck.I_(L), *__restrict dc = bck.D_(L);
+    const int rc = row_at<FULL>(L);
+    float *__restrict mc = bck.M_(rc), *__restrict ic = bck.I_(rc), *__restrict dc = bck.D_(rc);
     mc[M + 1] = ic[M + 1] = dc[M + 1] = 0.0f;
     for (int k = 1; k <= M; ++k) { dc[k] = xE; ic[k] = 0.0f; }
     dchain_backward(om, dc);
     for (int k = 1; k <= M; ++k) mc[k] = xE + dc[k + 1] * tMD[k];
     mc[0] = ic[0] = dc[0] = 0.0f;
-    float sc = fwd.X(L, xS_);
+    float sc = fx[(size_t) L * NX + xS_];
     if (sc > 1.0f) {
       xE = xE / sc; xN = xN / sc; xC = xC / sc; xJ = xJ / sc; xB = xB / sc;
       const float inv = 1.0 / sc;
@@ -401,8 +298,9 @@ P7X_MULTIVERSION int backward_full_lanes(const Model &om, const uint8_t *dsq, in
   }
   for (int r = L - 1; r >= 1; --r) {
     const float *__restrict rf = om.rf(dsq[r + 1]);
-    const float *__restrict mn = bck.M_(r + 1), *__restrict in = bck.I_(r + 1);
-    float *__restrict mc = bck.M_(r), *__restrict ic = bck.I_(r), *__restrict dc = bck.D_(r);
+    const int rn = row_at<FULL>(r + 1), rc = row_at<FULL>(r);
+    const float *__restrict mn = bck.M_(rn), *__restrict in = bck.I_(rn);
+    float *__restrict mc = bck.M_(rc), *__restrict ic = bck.I_(rc), *__restrict dc = bck.D_(rc);
     for (int k = 1; k <= M; ++k) me[k] = mn[k] * rf[k];                      // M(i+1,k) e(x_{i+1},k)
     me[M + 1] = 0.0f;
     xB = lanes_dot(om, me, bm);
@@ -423,7 +321,7 @@ P7X_MULTIVERSION int backward_full_lanes(const Model &om, const uint8_t *dsq, in
     for (int k = 1; k <= M; ++k) mc[k] += dc[k + 1] * tMD[k];
     mc[0] = ic[0] = dc[0] = 0.0f;
     if (xB > 1.0e16) bck.own_scales = true;
-    float sc = bck.own_scales ? ((xB > 1.0e4) ? xB : 1.0f) : fwd.X(r, xS_);
+    float sc = bck.own_scales ? ((xB > 1.0e4) ? xB : 1.0f) : fx[(size_t) r * NX + xS_];
     bck.X(r, xS_) = sc;
     if (sc > 1.0f) {
       xE /= sc; xN /= sc; xJ /= sc; xB /= sc; xC /= sc;
@@ -435,26 +333,26 @@ P7X_MULTIVERSION int backward_full_lanes(const Model &om, const uint8_t *dsq, in
   }
   {
     const float *__restrict rf = om.rf(dsq[1]);
-    const float *__restrict mn = bck.M_(1);
+    const float *__restrict mn = bck.M_(row_at<FULL>(1));
     for (int k = 1; k <= M; ++k) me[k] = mn[k] * rf[k];
     xB = lanes_dot(om, me, bm);
     xN = (xB * om.xf[XN][MOVE]) + (xN * om.xf[XN][LOOP]);
     bck.X(0, xB_) = xB; bck.X(0, xC_) = 0.0f; bck.X(0, xJ_) = 0.0f; bck.X(0, xN_) = xN; bck.X(0, xE_) = 0.0f; bck.X(0, xS_) = 1.0f;
-    float *mc = bck.M_(0), *ic = bck.I_(0), *dc = bck.D_(0);
-    for (int k = 0; k <= M + 1; ++k) mc[k] = ic[k] = dc[k] = 0.0f;
+    if (FULL) { float *mc = bck.M_(0), *ic = bck.I_(0), *dc = bck.D_(0); for (int k = 0; k <= M + 1; ++k) mc[k] = ic[k] = dc[k] = 0.0f; }
   }
   if (std::isnan(xN) || (L > 0 && xN == 0.0f) || std::isinf(xN)) { if (ret_sc) *ret_sc = INFINITY; return P7X_ERANGE; }
   if (ret_sc) *ret_sc = bck.totscale + std::log((double) xN);
   return P7X_OK;
 }
 
-
-// ---------------------------------------------------------------- p7_Forward / p7_Backward in upstream's order
-// impl_sse/fwdback.c forward_engine / backward_engine with do_full = TRUE, restated on four-float vectors: vector q of a row
-// holds nodes q+1, q+1+Q, q+1+2Q, q+1+3Q (padding nodes carry zero transitions and emissions, as p7_oprofile_Convert pads
-// them).  Every multiplication and addition of the vector code is performed on the same operands in the same order; the
-// rows go to the un-striped Matrix afterwards.  forward_parser_striped() (p7x_longtarget.inc.hpp) is the do_full = FALSE
-// sibling.
+// ---------------------------------------------------------------- ... in upstream's order
+// impl_sse/fwdback.c forward_engine / backward_engine restated on four-float vectors: vector q of a row holds nodes q+1,
+// q+1+Q, q+1+2Q, q+1+3Q (padding nodes carry zero transitions and emissions, as p7_oprofile_Convert pads them).  Every
+// multiplication and addition of the vector code is performed on the same operands in the same order: node k lives in
+// stripe z = (k-1) / Q of vector q = (k-1) % Q; xE is four per-stripe sums over q (match cells first, delete cells after
+// the delete chain) folded as (s0 + s1) + (s2 + s3); the D->D chain is one serial sweep per stripe and then up to three
+// carry sweeps from stripe to stripe (always three when M < 100, else until no cell grows).  FULL is upstream's do_full:
+// the rows go to the un-striped Matrix afterwards.
 typedef float V4 __attribute__((vector_size(16), aligned(4)));      // four stripes side by side (the compiler's own vector type: one SIMD operation per vector operation)
 static inline V4 v4_set(float a) { return V4{ a, a, a, a }; }
 static inline V4 v4_add(const V4 &a, const V4 &b) { return a + b; }
@@ -469,16 +367,13 @@ static inline void unstripe(const StripedRow &r, int Q, int M, float *mc, float 
     for (int z = 0; z < 4; ++z) { const int k = q + 1 + z * Q; if (k <= M) { mc[k] = r.m[q][z]; ic[k] = r.i[q][z]; dc[k] = r.d[q][z]; } }
   mc[0] = ic[0] = dc[0] = 0.0f; mc[M + 1] = ic[M + 1] = dc[M + 1] = 0.0f;
 }
-static inline void stripe_emissions(const float *rf, int Q, int M, std::vector<V4> &rv)
-{
-  for (int q = 0; q < Q; ++q) for (int z = 0; z < 4; ++z) { const int k = q + 1 + z * Q; rv[(size_t) q][z] = k <= M ? rf[k] : 0.0f; }
-}
 
-struct StripedScratch { StripedRow a, b; std::vector<V4> rv; };     // per thread, owned by the dispatchers below (no thread_local inside a cloned function)
-P7X_MULTIVERSION int forward_full_upstream(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *ret_sc, StripedScratch &ss)
+struct StripedScratch { StripedRow a, b; };     // per thread, owned by the callers of the entry points (no thread_local inside a cloned function)
+template <bool FULL>
+P7X_INLINE int forward_upstream(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *ret_sc, StripedScratch &ss)
 {
   const int M = om.M, Q = om.Q;
-  ox.resize(M, L);
+  ox.resize(M, L, FULL ? -1 : 0);
   const V4 *tBM = reinterpret_cast<const V4 *>(om.sT(0)), *tMM = reinterpret_cast<const V4 *>(om.sT(1)), *tIM = reinterpret_cast<const V4 *>(om.sT(2)),
            *tDM = reinterpret_cast<const V4 *>(om.sT(3)), *tMD = reinterpret_cast<const V4 *>(om.sT(4)), *tMI = reinterpret_cast<const V4 *>(om.sT(5)),
            *tII = reinterpret_cast<const V4 *>(om.sT(6)), *tDD = reinterpret_cast<const V4 *>(om.sT(7));
@@ -486,7 +381,7 @@ P7X_MULTIVERSION int forward_full_upstream(const Model &om, const uint8_t *dsq, 
   row.resize(Q);
   const V4 zero = v4_set(0.0f);
   for (int q = 0; q < Q; ++q) row.m[q] = row.d[q] = row.i[q] = zero;
-  { float *m0 = ox.M_(0), *i0 = ox.I_(0), *d0 = ox.D_(0); for (int k = 0; k <= M + 1; ++k) m0[k] = i0[k] = d0[k] = 0.0f; }
+  if (FULL) { float *m0 = ox.M_(0), *i0 = ox.I_(0), *d0 = ox.D_(0); for (int k = 0; k <= M + 1; ++k) m0[k] = i0[k] = d0[k] = 0.0f; }
   float xE = 0.f, xN = 1.f, xJ = 0.f, xB = om.xf[XN][MOVE], xC = 0.f;
   ox.X(0, xE_) = xE; ox.X(0, xN_) = xN; ox.X(0, xJ_) = xJ; ox.X(0, xB_) = xB; ox.X(0, xC_) = xC; ox.X(0, xS_) = 1.0f;
   ox.totscale = 0.0f; ox.own_scales = true;
@@ -545,17 +440,18 @@ P7X_MULTIVERSION int forward_full_upstream(const Model &om, const uint8_t *dsq, 
       xE = 1.0;
     } else ox.X(r, xS_) = 1.0f;
     ox.X(r, xE_) = xE; ox.X(r, xN_) = xN; ox.X(r, xJ_) = xJ; ox.X(r, xB_) = xB; ox.X(r, xC_) = xC;
-    unstripe(row, Q, M, ox.M_(r), ox.I_(r), ox.D_(r));
+    if (FULL) unstripe(row, Q, M, ox.M_(r), ox.I_(r), ox.D_(r));
   }
   if (std::isnan(xC) || (L > 0 && xC == 0.0f) || std::isinf(xC)) { if (ret_sc) *ret_sc = INFINITY; return P7X_ERANGE; }
   if (ret_sc) *ret_sc = ox.totscale + std::log((double) (xC * om.xf[XC][MOVE]));
   return P7X_OK;
 }
 
-P7X_MULTIVERSION int backward_full_upstream(const Model &om, const uint8_t *dsq, int L, const Matrix &fwd, Matrix &bck, float *ret_sc, StripedScratch &ss)
+template <bool FULL>
+P7X_INLINE int backward_upstream(const Model &om, const uint8_t *dsq, int L, const float *fx, Matrix &bck, float *ret_sc, StripedScratch &ss)
 {
   const int M = om.M, Q = om.Q;
-  bck.resize(M, L);
+  bck.resize(M, L, FULL ? -1 : 0);
   const V4 *tBM = reinterpret_cast<const V4 *>(om.sT(0)), *tMM = reinterpret_cast<const V4 *>(om.sT(1)), *tIM = reinterpret_cast<const V4 *>(om.sT(2)),
            *tDM = reinterpret_cast<const V4 *>(om.sT(3)), *tMD = reinterpret_cast<const V4 *>(om.sT(4)), *tMI = reinterpret_cast<const V4 *>(om.sT(5)),
            *tII = reinterpret_cast<const V4 *>(om.sT(6)), *tDD = reinterpret_cast<const V4 *>(om.sT(7));
@@ -592,12 +488,12 @@ P7X_MULTIVERSION int backward_full_upstream(const Model &om, const uint8_t *dsq,
     const V4 xEv = v4_set(xE);
     for (int q = 0; q < Q; ++q) { cur->m[q] = cur->d[q] = xEv; cur->i[q] = zero; }
     close_row(*cur, cur->d[Q - 1], xEv, false);
-    const float sc = fwd.X(L, xS_);
+    const float sc = fx[(size_t) L * NX + xS_];
     if (sc > 1.0f) { xE = xE / sc; xN = xN / sc; xC = xC / sc; xJ = xJ / sc; xB = xB / sc; rescale(*cur, sc); }
     bck.X(L, xS_) = sc;
     bck.totscale = std::log((double) sc);
     bck.X(L, xE_) = xE; bck.X(L, xN_) = xN; bck.X(L, xJ_) = xJ; bck.X(L, xB_) = xB; bck.X(L, xC_) = xC;
-    unstripe(*cur, Q, M, bck.M_(L), bck.I_(L), bck.D_(L));
+    if (FULL) unstripe(*cur, Q, M, bck.M_(L), bck.I_(L), bck.D_(L));
   }
   for (int r = L - 1; r >= 1; --r) {
     std::swap(cur, nxt);
@@ -623,7 +519,7 @@ P7X_MULTIVERSION int backward_full_upstream(const Model &om, const uint8_t *dsq,
     const V4 xEv = v4_set(xE);
     close_row(*cur, v4_add(cur->d[0], xEv), xEv, true);
     if (xB > 1.0e16) bck.own_scales = true;
-    const float sc = bck.own_scales ? ((xB > 1.0e4) ? xB : 1.0f) : fwd.X(r, xS_);
+    const float sc = bck.own_scales ? ((xB > 1.0e4) ? xB : 1.0f) : fx[(size_t) r * NX + xS_];
     bck.X(r, xS_) = sc;
     if (sc > 1.0f) {
       xE /= sc; xN /= sc; xJ /= sc; xB /= sc; xC /= sc;
@@ -631,7 +527,7 @@ P7X_MULTIVERSION int backward_full_upstream(const Model &om, const uint8_t *dsq,
       bck.totscale += std::log((double) sc);
     }
     bck.X(r, xE_) = xE; bck.X(r, xN_) = xN; bck.X(r, xJ_) = xJ; bck.X(r, xB_) = xB; bck.X(r, xC_) = xC;
-    unstripe(*cur, Q, M, bck.M_(r), bck.I_(r), bck.D_(r));
+    if (FULL) unstripe(*cur, Q, M, bck.M_(r), bck.I_(r), bck.D_(r));
   }
   {
     const V4 *rv = reinterpret_cast<const V4 *>(om.sR(dsq[1]));
@@ -640,19 +536,29 @@ P7X_MULTIVERSION int backward_full_upstream(const Model &om, const uint8_t *dsq,
     xB = v4_hsum(xBv);
     xN = (xB * om.xf[XN][MOVE]) + (xN * om.xf[XN][LOOP]);
     bck.X(0, xB_) = xB; bck.X(0, xC_) = 0.0f; bck.X(0, xJ_) = 0.0f; bck.X(0, xN_) = xN; bck.X(0, xE_) = 0.0f; bck.X(0, xS_) = 1.0f;
-    float *mc = bck.M_(0), *ic = bck.I_(0), *dc = bck.D_(0);
-    for (int k = 0; k <= M + 1; ++k) mc[k] = ic[k] = dc[k] = 0.0f;
+    if (FULL) { float *mc = bck.M_(0), *ic = bck.I_(0), *dc = bck.D_(0); for (int k = 0; k <= M + 1; ++k) mc[k] = ic[k] = dc[k] = 0.0f; }
   }
   if (std::isnan(xN) || (L > 0 && xN == 0.0f) || std::isinf(xN)) { if (ret_sc) *ret_sc = INFINITY; return P7X_ERANGE; }
   if (ret_sc) *ret_sc = bck.totscale + std::log((double) xN);
   return P7X_OK;
 }
 
+// the cloned entry points: (direction, order) x (full matrix, rows only)
+P7X_MULTIVERSION int forward_full_lanes(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *sc) { return forward_lanes<true>(om, dsq, L, ox, sc); }
+P7X_MULTIVERSION int forward_rows_lanes(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *sc) { return forward_lanes<false>(om, dsq, L, ox, sc); }
+P7X_MULTIVERSION int backward_full_lanes(const Model &om, const uint8_t *dsq, int L, const float *fx, Matrix &bck, float *sc) { return backward_lanes<true>(om, dsq, L, fx, bck, sc); }
+P7X_MULTIVERSION int backward_rows_lanes(const Model &om, const uint8_t *dsq, int L, const float *fx, Matrix &bck, float *sc) { return backward_lanes<false>(om, dsq, L, fx, bck, sc); }
+P7X_MULTIVERSION int forward_full_upstream(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *sc, StripedScratch &ss) { return forward_upstream<true>(om, dsq, L, ox, sc, ss); }
+P7X_MULTIVERSION int forward_rows_upstream(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *sc, StripedScratch &ss) { return forward_upstream<false>(om, dsq, L, ox, sc, ss); }
+P7X_MULTIVERSION int backward_full_upstream(const Model &om, const uint8_t *dsq, int L, const float *fx, Matrix &bck, float *sc, StripedScratch &ss) { return backward_upstream<true>(om, dsq, L, fx, bck, sc, ss); }
+P7X_MULTIVERSION int backward_rows_upstream(const Model &om, const uint8_t *dsq, int L, const float *fx, Matrix &bck, float *sc, StripedScratch &ss) { return backward_upstream<false>(om, dsq, L, fx, bck, sc, ss); }
+
 static StripedScratch &striped_scratch() { thread_local StripedScratch *ss = new StripedScratch(); return *ss; }     // (leaked with its thread: a few KB)
 static inline int forward_full(const Model &om, const uint8_t *dsq, int L, Matrix &ox, float *ret_sc)
 { return om.upstream ? forward_full_upstream(om, dsq, L, ox, ret_sc, striped_scratch()) : forward_full_lanes(om, dsq, L, ox, ret_sc); }
 static inline int backward_full(const Model &om, const uint8_t *dsq, int L, const Matrix &fwd, Matrix &bck, float *ret_sc)
-{ return om.upstream ? backward_full_upstream(om, dsq, L, fwd, bck, ret_sc, striped_scratch()) : backward_full_lanes(om, dsq, L, fwd, bck, ret_sc); }
+{ return om.upstream ? backward_full_upstream(om, dsq, L, fwd.x.data(), bck, ret_sc, striped_scratch()) : backward_full_lanes(om, dsq, L, fwd.x.data(), bck, ret_sc); }
+
 
 // ---------------------------------------------------------------- p7_Decoding: posteriors into <bck> (in place)
 // NOTE: only the M and I posteriors are formed.  bck.D_ keeps Backward's delete values afterwards (upstream zeroes them): a
@@ -745,52 +651,6 @@ P7X_MULTIVERSION void null2_by_expectation(const Model &om, Matrix &pp, float *n
   }
   finish_null2(*om.p, null2);
 }
-
-// ---------------------------------------------------------------- traces
-struct Trace {
-  std::vector<int8_t> st; std::vector<int> k, i; std::vector<float> pp;
-  int ndom = 0;
-  std::vector<int> tfrom, tto, sqfrom, sqto, hmmfrom, hmmto;
-  void clear() { st.clear(); k.clear(); i.clear(); pp.clear(); ndom = 0; tfrom.clear(); tto.clear(); sqfrom.clear(); sqto.clear(); hmmfrom.clear(); hmmto.clear(); }
-  void append(int s, int kk, int ii, float p)
-  { // p7_trace_AppendWithPP
-    int iv = 0, kv = 0; float pv = 0.0f;
-    switch (s) {
-      case sN: case sC: case sJ:
-        if (!st.empty() && st.back() == s) { iv = ii; pv = p; }
-        break;
-      case sD: kv = kk; break;
-      case sM: case sI: iv = ii; kv = kk; pv = p; break;
-      default: break;
-    }
-    st.push_back((int8_t) s); k.push_back(kv); i.push_back(iv); pp.push_back(pv);
-  }
-  void reverse()
-  { // p7_trace_Reverse: N,C,J emit on transition, so their i/pp move one step when the order flips
-    const int N = (int) st.size();
-    for (int z = 0; z < N; ++z)
-      if ((st[z] == sN || st[z] == sC || st[z] == sJ) && z + 1 < N && st[z] == st[z + 1]) {
-        if (i[z] == 0 && i[z + 1] > 0) { i[z] = i[z + 1]; i[z + 1] = 0; pp[z] = pp[z + 1]; pp[z + 1] = 0.0f; }
-      }
-    std::reverse(st.begin(), st.end()); std::reverse(k.begin(), k.end());
-    std::reverse(i.begin(), i.end()); std::reverse(pp.begin(), pp.end());
-  }
-  void index()
-  { // p7_trace_Index
-    ndom = 0; tfrom.clear(); tto.clear(); sqfrom.clear(); sqto.clear(); hmmfrom.clear(); hmmto.clear();
-    for (int z = 0; z < (int) st.size(); ++z)
-      switch (st[z]) {
-        case sB: tfrom.push_back(z); tto.push_back(0); sqfrom.push_back(0); sqto.push_back(0); hmmfrom.push_back(0); hmmto.push_back(0); break;
-        case sM:
-          if (sqfrom[ndom] == 0) sqfrom[ndom] = i[z];
-          if (hmmfrom[ndom] == 0) hmmfrom[ndom] = k[z];
-          sqto[ndom] = i[z]; hmmto[ndom] = k[z];
-          break;
-        case sE: tto[ndom] = z; ndom++; break;
-        default: break;
-      }
-  }
-};
 
 // ---------------------------------------------------------------- p7_OptimalAccuracy + p7_OATrace
 inline float gate(float t, float v) { return t > 0.0f ? v : 0.0f; }   // upstream: and(cmpgt(t,0), v)
@@ -1141,6 +1001,8 @@ void sp_cluster(const std::vector<SpCoord> &sp, int nsamples, float min_overlap,
   std::stable_sort(sigc.begin(), sigc.end(), [](const SpCoord &a, const SpCoord &b) { return a.i < b.i; });
 }
 
+} // anonymous namespace
+
 // ---------------------------------------------------------------- p7_alidisplay_Create (domain 0 of an OA trace)
 void make_alidisplay(const Profile &p, const Trace &tr, const uint8_t *dsq, int L, Domain &dom)
 {
@@ -1190,15 +1052,13 @@ void make_alidisplay(const Profile &p, const Trace &tr, const uint8_t *dsq, int 
   }
 }
 
-struct Workspace { Matrix fwd, bck; Trace tr; std::vector<float> wm, wi; };
-
 // ---------------------------------------------------------------- rescore_isolated_domain
 // upstream reparameterize_model + p7_oprofile_UpdateFwdEmissionScores: the background becomes
 //   bg'[x] = (1 - s) * composition(dsq[i..j])[x] + s * bg->f[x],   s = 25 / min(100, max(50, n)),  n = window length
 // (0.25 for every window of 100 residues or more), and the match odds rf'[x][k] = match_prob[k][x] / bg'[x], degenerate
 // codes by expectation under bg'.  Pinned by bmyD1/bmyD2.tbl and the RF00001 answers (all windows there are > 100 nt; the
 // short-window branch of s is restated from upstream and not pinned by any fixture).
-static void reparameterize(const Profile &p, const LongTargetOpts &lt, const uint8_t *dsq, int n, int i, int j, std::vector<float> &rf)
+void reparameterize(const Profile &p, const LongTargetOpts &lt, const uint8_t *dsq, int n, int i, int j, std::vector<float> &rf)
 {
   const int M = p.M, K = p.K, Kp = p.Kp;
   const Alphabet &abc = Alphabet::get(p.abc_type);
@@ -1231,7 +1091,7 @@ static void reparameterize(const Profile &p, const LongTargetOpts &lt, const uin
 }
 
 int rescore_isolated_domain(const Profile &p, Model &om, const uint8_t *dsq, int L, int i, int j, bool null2_is_done,
-                            Workspace &ws, DomainDefResult &dd)
+                            DomainWorkspace &ws, DomainDefResult &dd)
 {
   const LongTargetOpts *lt = om.lt;
   int Ld = j - i + 1;
@@ -1303,7 +1163,6 @@ int rescore_isolated_domain(const Profile &p, Model &om, const uint8_t *dsq, int
   return P7X_OK;
 }
 
-} // anonymous namespace
 
 // ---------------------------------------------------------------- p7_domaindef_ByPosteriorHeuristics
 // Step 1: posterior decoding of the special states (p7_DomainDecoding) and the region scan.
@@ -1348,9 +1207,12 @@ int domaindef_regions(const Profile &p, int L, const float *fx, const float *bx,
   return P7X_OK;
 }
 
+static thread_local const LongTargetOpts *t_long_target = nullptr;     // LongTargetScope: set by the long-target pipeline around its calls
+LongTargetScope::LongTargetScope(const LongTargetOpts &lt) { t_long_target = &lt; }
+LongTargetScope::~LongTargetScope() { t_long_target = nullptr; }
+
 // Step 2 for a multi-domain region: region_trace_ensemble (sampled tracebacks from a multihit Forward matrix of the
 // region, single-linkage clustering of their domain coordinates), then every surviving envelope is rescored.
-static thread_local const LongTargetOpts *t_long_target = nullptr;     // set by the long-target pipeline around its calls
 
 int domaindef_multi_region(const Profile &p, const uint8_t *dsq, int L, int i, int j, uint32_t seed, bool do_reseeding,
                            MultiRegionState &state, DomainDefResult &dd, std::vector<Domain> &out,
@@ -1359,7 +1221,7 @@ int domaindef_multi_region(const Profile &p, const uint8_t *dsq, int L, int i, i
   const int nsamples = 200;                                                  // p7_domaindef.pxd:43-48
   const float min_overlap = 0.8f, min_posterior = 0.25f, min_endpointp = 0.02f;
   const bool of_smaller = true; const int max_diagdiff = 4;
-  thread_local Workspace ws;
+  thread_local DomainWorkspace ws;
   Model om{ &p, p.M, {} };
   om.lt = t_long_target;
   om.prepare();
@@ -1479,7 +1341,7 @@ static int dispatch_regions(const Profile &p, const uint8_t *dsq, int L, const R
 {
   Model om{ &p, p.M, {} };
   om.lt = t_long_target;
-  thread_local Workspace ws;
+  thread_local DomainWorkspace ws;
   bool prepared = false;
   MultiRegionState state;
   for (int ri = 0; ri < nregs; ++ri) {
@@ -1528,20 +1390,88 @@ int domaindef_finish_multi(const Profile &p, const uint8_t *dsq, int L, uint32_t
 
 uint32_t fast_rng_state(uint32_t seed) { FastRng r; r.init(seed); return r.x; }
 
+// ---------------------------------------------------------------- the parsers: special-state rows only
+// The rows-only engines write into a Matrix whose special rows are the caller's vector (lent for the call).
+struct RowsOf {
+  Matrix mx; std::vector<float> &v;
+  explicit RowsOf(std::vector<float> &rows) : v(rows) { mx.x.swap(v); }
+  ~RowsOf() { v.swap(mx.x); v.resize((size_t) (mx.L + 1) * NX); }
+};
+
+int forward_parser_lanes(const Model &om, const uint8_t *dsq, int L, std::vector<float> &fx, float *ret_sc)
+{
+  RowsOf f(fx);
+  return forward_rows_lanes(om, dsq, L, f.mx, ret_sc);
+}
+
+// (a 2,400-residue window of a 1,200-node model would stream 70 MB of full matrices through the host caches for rows the
+// region scan never reads)
+int backward_parser_lanes(const Model &om, const uint8_t *dsq, int L, const std::vector<float> &fx, std::vector<float> &bx)
+{
+  RowsOf b(bx);
+  return backward_rows_lanes(om, dsq, L, fx.data(), b.mx, nullptr);
+}
+
+// p7_ForwardParser / p7_BackwardParser special-state rows in upstream's summation order, for the region-scan guard
+// (p7x_tophits.cpp).  Memory: the rows themselves and O(M) of striped DP rows, whatever L x M is.
 int parser_rows_upstream(const Profile &p, const uint8_t *dsq, int L, std::vector<float> &fx, std::vector<float> &bx)
 {
-  thread_local Workspace ws;
   Model om{ &p, p.M, {} };
   om.prepare(0);
   om.configure(true, L);
-  int st = forward_full(om, dsq, L, ws.fwd, nullptr);
+  RowsOf f(fx), b(bx);
+  const int st = forward_rows_upstream(om, dsq, L, f.mx, nullptr, striped_scratch());
   if (st != P7X_OK) return st;
-  st = backward_full(om, dsq, L, ws.fwd, ws.bck, nullptr);
-  if (st != P7X_OK) return st;
-  fx.assign(ws.fwd.x.begin(), ws.fwd.x.begin() + (size_t) (L + 1) * NX);
-  bx.assign(ws.bck.x.begin(), ws.bck.x.begin() + (size_t) (L + 1) * NX);
-  return P7X_OK;
+  return backward_rows_upstream(om, dsq, L, f.mx.x.data(), b.mx, nullptr, striped_scratch());
 }
+
+// The F3 tie-breaker (the guard in p7x_tophits.cpp): the Forward parser score in upstream's summation order.  The device
+// kernels and the lanes engines use other (faster) association orders, a few ulps apart -- which only matters for a target
+// whose P-value sits on the F3 threshold.  dsq1[1..L]; multihit, length model of L as the pipeline configures the parser.
+int host_forward_parser_exact(const Profile &p, const uint8_t *dsq1, int L, float *sc)
+{
+  Model om{ &p, p.M, {} };
+  om.prepare(0);
+  om.configure(true, L);
+  Matrix ox;
+  return forward_rows_upstream(om, dsq1, L, ox, sc, striped_scratch());
+}
+
+// p7_bg_FilterScore: Forward score of the two-state composition HMM (esl_hmm_Forward), float arithmetic as upstream
+float bias_filter_score(const Profile &p, const uint8_t *dsq, int64_t L)
+{
+  const Alphabet &abc = Alphabet::get(p.abc_type);
+  float eo[MAXKP][2];
+  for (int x = 0; x < p.Kp; ++x) { eo[x][0] = 1.0f; eo[x][1] = 1.0f; }
+  for (int x = 0; x < p.K; ++x) { eo[x][0] = p.bgf[x] / p.bgf[x]; eo[x][1] = p.compo[x] / p.bgf[x]; }
+  for (int x = p.K + 1; x <= p.Kp - 3; ++x)
+    for (int s = 0; s < 2; ++s) {
+      float e = 0.0f, den = 0.0f;
+      for (int y = 0; y < p.K; ++y) if (abc.degen[x][y]) { e += (s == 0 ? p.bgf[y] : p.compo[y]); den += p.bgf[y]; }
+      eo[x][s] = den > 0.0f ? e / den : 0.0f;
+    }
+  const float p1 = (float) L / (float) (L + 1);
+  const float L1 = (float) ((double) (float) p.M / 8.0);
+  const float t00 = p1, t01 = 1.0f - p1, t10 = 1.0f / (L1 + 1.0f), t11 = L1 / (L1 + 1.0f);
+  float dp0 = eo[dsq[1]][0] * 0.999f, dp1 = eo[dsq[1]][1] * 0.001f;
+  float mx = std::max(0.0f, std::max(dp0, dp1));
+  dp0 /= mx; dp1 /= mx;
+  float logsc = 0.0f;
+  logsc += (float) std::log((double) mx);
+  for (int64_t i = 2; i <= L; ++i) {
+    const int x = dsq[i];
+    float n0 = 0.0f; n0 += dp0 * t00; n0 += dp1 * t10; n0 *= eo[x][0];
+    float n1 = 0.0f; n1 += dp0 * t01; n1 += dp1 * t11; n1 *= eo[x][1];
+    mx = std::max(0.0f, std::max(n0, n1));
+    dp0 = n0 / mx; dp1 = n1 / mx;
+    logsc += (float) std::log((double) mx);
+  }
+  float last = 0.0f; last += dp0 * 1.0f; last += dp1 * 1.0f;
+  logsc += (float) std::log((double) last);
+  return logsc + (float) L * logf(p1) + logf((float) (1. - (double) p1));
+}
+// the null score the F3 guard compares a Forward score against
+float host_filter_null_score(const Profile &p, const uint8_t *dsq1, int L, bool do_bias) { return do_bias ? bias_filter_score(p, dsq1, L) : null1_score(L); }
 
 // hmmalign's per-sequence step (upstream p7_tracealign_computeTraces): the profile unihit local with the sequence's own
 // length model, the whole sequence as the envelope, Forward -> Backward -> Decoding -> OptimalAccuracy -> OATrace -- the
@@ -1554,8 +1484,8 @@ int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrac
   if (L <= 0) return P7X_OK;                    // an empty sequence: an empty trace
   // two full matrices of (L + 1) x (M + 2) cells: a worker keeps them for its next sequence, but not beyond 128 MiB (a
   // long model against a long sequence would otherwise leave gigabytes behind in every worker of the pool)
-  thread_local Workspace ws;
-  struct Shrink { Workspace &ws; ~Shrink() { if (ws.fwd.m.capacity() * sizeof(float) * 6 > ((size_t) 128 << 20)) ws = Workspace(); } } shrink{ ws };
+  thread_local DomainWorkspace ws;
+  struct Shrink { DomainWorkspace &ws; ~Shrink() { if (ws.fwd.m.capacity() * sizeof(float) * 6 > ((size_t) 128 << 20)) ws = DomainWorkspace(); } } shrink{ ws };
   Model om{ &p, p.M, {} };
   om.prepare(order);
   om.configure(false, L);
@@ -1585,7 +1515,7 @@ int domaindef_finish_deferred(const Profile &p, const uint8_t *dsq, int L, const
                               const std::vector<int> &req_index, DomainDefResult &dd,
                               const std::vector<EnvelopeResult> *res2, const std::vector<int> *req_index2)
 {
-  thread_local Workspace ws;
+  thread_local DomainWorkspace ws;
   std::vector<Domain> kept;
   kept.reserve(dd.dcl.size());
   // the device's answer for envelope i..j -> a Domain; null2_done: the region's ensemble already set dd.n2sc on i..j
@@ -1716,4 +1646,24 @@ extern "C" int p7x_debug_order_spread(const p7x_oprofile *om, const uint8_t *dsq
   return P7X_OK;
 }
 
-#include "p7x_longtarget.inc.hpp"
+
+extern "C" int p7x_forward_parser_exact(const p7x_oprofile *om, const uint8_t *dsq, int32_t L, float *sc)
+{
+  using namespace p7x;
+  if (!om || !sc || L < 0 || (L > 0 && !dsq)) { set_error("p7x_forward_parser_exact: bad arguments"); return P7X_EINVAL; }
+  return host_forward_parser_exact(om->p, dsq, L, sc);
+}
+
+// Test seam of the rows-only engines in upstream's order: the parsers' special-state rows of dsq1[1..L] (multihit, length
+// model of L) as the region-scan guard gets them (parser_rows_upstream), (L+1) x [E,N,J,B,C,SCALE] floats each.
+extern "C" int p7x_debug_parser_rows(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, float *fx, float *bx)
+{
+  using namespace p7x;
+  if (!om || !dsq1 || L < 1 || !fx || !bx) { set_error("p7x_debug_parser_rows: bad arguments"); return P7X_EINVAL; }
+  std::vector<float> f, b;
+  const int st = parser_rows_upstream(om->p, dsq1, L, f, b);
+  if (st != P7X_OK) return st;
+  std::memcpy(fx, f.data(), f.size() * sizeof(float));
+  std::memcpy(bx, b.data(), b.size() * sizeof(float));
+  return P7X_OK;
+}

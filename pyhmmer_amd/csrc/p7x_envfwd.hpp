@@ -1,6 +1,6 @@
 // p7x_envfwd.hpp -- one row of the full Forward recurrence with the row state in registers (upstream impl_sse/fwdback.c
 // p7_Forward), shared by the envelope kernel (p7x_envelope.hip: unihit, an envelope) and the ensemble kernel
-// (p7x_ensemble.hip: multihit, a multi-domain region).  The host twin's forward_full() (p7x_domaindef.cpp) performs the
+// (p7x_ensemble.hip: multihit, a multi-domain region).  The host twin's forward_lanes() (p7x_domaindef.cpp) performs the
 // same operations in the same order; what is decided from these values is decided alike on both sides.
 #pragma once
 #include "p7x_wave.hpp"

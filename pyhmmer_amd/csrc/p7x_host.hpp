@@ -83,12 +83,12 @@ struct EnsembleRunner {
 };
 uint32_t fast_rng_state(uint32_t seed);          // esl_randomness_Init for the LCG
 // p7_ForwardParser / p7_BackwardParser special-state rows ((L+1) x [E,N,J,B,C,SCALE], multihit, length model of L) in upstream's
-// summation order (the full-matrix engine; the target's DP matrices are scratch): dsq[1..L]
+// summation order (the rows-only engines of p7x_domaindef.cpp: no DP matrix): dsq[1..L]
+int parser_rows_upstream(const Profile &p, const uint8_t *dsq, int L, std::vector<float> &fx, std::vector<float> &bx);
 // hmmalign's host twin (p7x_domaindef.cpp): the trace of one whole sequence, forward order, float posteriors
 struct AlignTrace { std::vector<int8_t> st; std::vector<int> k, i; std::vector<float> pp; float fwdsc = 0.0f, oasc = 0.0f; };
 int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order = 0);
 void align_trace_from_device(const uint32_t *ta, const int32_t *ti, const float *tp, int n, AlignTrace &out);
-int parser_rows_upstream(const Profile &p, const uint8_t *dsq, int L, std::vector<float> &fx, std::vector<float> &bx);
 
 // p7_domaindef_ByPosteriorHeuristics (p7_domaindef.pxd:69-72).  dsq is 1-indexed (dsq[1..L]);
 // fwd_xmx / bck_xmx are the parsers' special-state rows, (L+1) x [E,N,J,B,C,SCALE].
@@ -173,7 +173,7 @@ void host_parallel_for(int n, int nthreads, const std::function<void(int)> &body
 void tophits_set_stages(p7x_tophits *th, std::vector<uint8_t> &&stage);
 float kahan_fsum(const float *v, int n);
 
-// ---- long targets (p7x_longtarget.inc.hpp <-> p7x_longtarget.hip)
+// ---- long targets (p7x_longtarget_host.cpp <-> p7x_longtarget.hip)
 struct LongTargetRow { int64_t pos; int k, sc; };            // a row of a strand block that reached the SSV threshold, and the cell upstream picks
 struct LongTargetSeed { int64_t target, block_start; int strand; int64_t n; int k; int64_t length; };   // an SSV window seed of one block
 // (target, block, strand) units of a long-target search in the order of the reference's loop, and the part that owns one
@@ -219,6 +219,7 @@ struct LongTargetWindowScorer {
 int longtarget_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, const uint8_t *dsq, const int64_t *offsets, const int64_t *lengths,
                         size_t n, const char *const *names, const char *const *accs, const char *const *descs,
                         const std::vector<LongTargetSeed> &seeds, p7x_tophits **out, LongTargetWindowScorer *filters = nullptr);
+// ---- the F3 guard's tie-breaker (p7x_domaindef.cpp): Forward parser score in upstream's summation order, and the filter's null score
 int host_forward_parser_exact(const Profile &p, const uint8_t *dsq1, int L, float *sc);     // dsq1[1..L]
 float host_filter_null_score(const Profile &p, const uint8_t *dsq1, int L, bool do_bias);
 void host_prof_dump();

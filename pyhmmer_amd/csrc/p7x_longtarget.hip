@@ -1,5 +1,5 @@
 // p7x_longtarget.hip -- device half of the long-target (nhmmer) search: the SSV scan of every target strand
-// (p7x_ssvlong.hip) and the hand-over of the rows it reports to the host tail (p7x_longtarget.inc.hpp).
+// (p7x_ssvlong.hip) and the hand-over of the rows it reports to the host tail (p7x_longtarget_host.cpp).
 // Reference: LongTargetsPipeline._search_loop_longtargets, plan7.pyx:7541-7664; p7_Pipeline_LongTarget,
 // p7_pipeline.pxd:131-143.
 #include "p7x_device.hpp"

@@ -1,5 +1,5 @@
-// p7x_longtarget.inc.hpp -- host tail of p7_Pipeline_LongTarget (nhmmer), included at the end of p7x_domaindef.cpp
-// (it drives that file's envelope machinery).
+// p7x_longtarget_host.cpp -- host tail of p7_Pipeline_LongTarget (nhmmer).  It drives the envelope machinery of
+// p7x_domaindef.cpp through p7x_hostdp.hpp.
 //
 // Restates, from upstream HMMER 3.3/3.4 (absent from the reference checkout; entry points and structs in
 // include/libhmmer/p7_pipeline.pxd:131-143, p7_scoredata.pxd:16-30, called from plan7.pyx:7541-7664):
@@ -12,6 +12,12 @@
 // The SSV scan itself runs on the device (p7x_ssvlong.hip); everything here sees only the few windows it seeds.
 // Parity status: restated from memory of upstream and pinned only by the reference's nhmmer fixtures
 // (tests/golden/tables/bmyD{1,2}.tbl, the RF00001 known answers); see DESIGN.md.
+#include "p7x_hostdp.hpp"
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <mutex>
 
 namespace p7x {
@@ -22,12 +28,6 @@ struct LtWindow { int64_t n = 0; int k = 0; int64_t length = 0; };     // first 
 
 // ---------------------------------------------------------------- scalar filters on one window
 struct LtLengthModel { uint8_t tjb_b; int16_t xw_move; float nullsc; };
-
-static float lt_null1(int64_t L)
-{
-  const float p1 = (float) L / (float) (L + 1);
-  return (float) L * std::log((double) p1) + std::log(1. - p1);        // p7_bg_NullOne
-}
 
 // p7_MSVFilter on dsq[1..L] with the length model of L (u8 arithmetic of impl_sse/msvfilter.c)
 static float lt_msv(const Profile &p, const uint8_t *dsq, int64_t L)
@@ -57,40 +57,6 @@ static float lt_msv(const Profile &p, const uint8_t *dsq, int64_t L)
   sc /= p.scale_b;
   sc -= 3.0f;
   return sc;
-}
-
-// p7_bg_FilterScore: Forward score of the two-state composition HMM (esl_hmm_Forward), float arithmetic as upstream
-static float lt_bias_filter(const Profile &p, const uint8_t *dsq, int64_t L)
-{
-  const Alphabet &abc = Alphabet::get(p.abc_type);
-  float eo[MAXKP][2];
-  for (int x = 0; x < p.Kp; ++x) { eo[x][0] = 1.0f; eo[x][1] = 1.0f; }
-  for (int x = 0; x < p.K; ++x) { eo[x][0] = p.bgf[x] / p.bgf[x]; eo[x][1] = p.compo[x] / p.bgf[x]; }
-  for (int x = p.K + 1; x <= p.Kp - 3; ++x)
-    for (int s = 0; s < 2; ++s) {
-      float e = 0.0f, den = 0.0f;
-      for (int y = 0; y < p.K; ++y) if (abc.degen[x][y]) { e += (s == 0 ? p.bgf[y] : p.compo[y]); den += p.bgf[y]; }
-      eo[x][s] = den > 0.0f ? e / den : 0.0f;
-    }
-  const float p1 = (float) L / (float) (L + 1);
-  const float L1 = (float) ((double) (float) p.M / 8.0);
-  const float t00 = p1, t01 = 1.0f - p1, t10 = 1.0f / (L1 + 1.0f), t11 = L1 / (L1 + 1.0f);
-  float dp0 = eo[dsq[1]][0] * 0.999f, dp1 = eo[dsq[1]][1] * 0.001f;
-  float mx = std::max(0.0f, std::max(dp0, dp1));
-  dp0 /= mx; dp1 /= mx;
-  float logsc = 0.0f;
-  logsc += (float) std::log((double) mx);
-  for (int64_t i = 2; i <= L; ++i) {
-    const int x = dsq[i];
-    float n0 = 0.0f; n0 += dp0 * t00; n0 += dp1 * t10; n0 *= eo[x][0];
-    float n1 = 0.0f; n1 += dp0 * t01; n1 += dp1 * t11; n1 *= eo[x][1];
-    mx = std::max(0.0f, std::max(n0, n1));
-    dp0 = n0 / mx; dp1 = n1 / mx;
-    logsc += (float) std::log((double) mx);
-  }
-  float last = 0.0f; last += dp0 * 1.0f; last += dp1 * 1.0f;
-  logsc += (float) std::log((double) last);
-  return logsc + (float) L * logf(p1) + logf((float) (1. - (double) p1));
 }
 
 static inline int16_t sat16(int v) { return (int16_t) std::max(-32768, std::min(32767, v)); }
@@ -142,227 +108,6 @@ static void lt_viterbi_longtarget(const Profile &p, const uint8_t *dsq, int64_t 
     for (int k = 2; k <= M; ++k) dn[k] = (int16_t) std::max((int) sat16(mn[k - 1] + tw(4, k - 1)), (int) sat16(dn[k - 1] + tw(7, k - 1)));
     mm.swap(mn); im.swap(in_); dm.swap(dn);
   }
-}
-
-// Forward / Backward parsers on a window (multihit, length model of the window): special-state rows only, two rolling
-// DP rows.  Same arithmetic and scaling as forward_full / backward_full above; rows are (L+1) x [E,N,J,B,C,SCALE].
-static int lt_forward_parser(Model &om, const uint8_t *dsq, int L, std::vector<float> &xmx, float *ret_sc)
-{
-  const int M = om.M;
-  const float *__restrict bm = om.tf(0), *__restrict tMM = om.tf(1), *__restrict tIM = om.tf(2), *__restrict tDM = om.tf(3),
-              *__restrict tMI = om.tf(5), *__restrict tII = om.tf(6);
-  std::vector<float> buf((size_t) 6 * (M + 2), 0.0f);
-  float *mp = buf.data(), *ip = mp + (M + 2), *dp = ip + (M + 2), *mc = dp + (M + 2), *ic = mc + (M + 2), *dc = ic + (M + 2);
-  xmx.assign((size_t) (L + 1) * NX, 0.0f);
-  float xE = 0.f, xN = 1.f, xJ = 0.f, xB = om.xf[XN][MOVE], xC = 0.f, totscale = 0.0f;
-  xmx[xN_] = xN; xmx[xB_] = xB; xmx[xS_] = 1.0f;
-  for (int r = 1; r <= L; ++r) {
-    const float *__restrict rf = om.rf(dsq[r]);
-    mc[0] = ic[0] = dc[0] = 0.0f;
-    for (int k = 1; k <= M; ++k) {
-      float sv = xB * bm[k];
-      sv = sv + mp[k - 1] * tMM[k];
-      sv = sv + ip[k - 1] * tIM[k];
-      sv = sv + dp[k - 1] * tDM[k];
-      mc[k] = sv * rf[k];
-      ic[k] = mp[k] * tMI[k] + ip[k] * tII[k];
-    }
-    xE = dchain_forward(om, mc, dc);
-    mc[M + 1] = ic[M + 1] = dc[M + 1] = 0.0f;
-    xN = xN * om.xf[XN][LOOP];
-    xC = (xC * om.xf[XC][LOOP]) + (xE * om.xf[XE][MOVE]);
-    xJ = (xJ * om.xf[XJ][LOOP]) + (xE * om.xf[XE][LOOP]);
-    xB = (xJ * om.xf[XJ][MOVE]) + (xN * om.xf[XN][MOVE]);
-    float *row = xmx.data() + (size_t) r * NX;
-    if (xE > 1.0e4) {
-      xN = xN / xE; xC = xC / xE; xJ = xJ / xE; xB = xB / xE;
-      const float inv = 1.0 / xE;
-      for (int q = 1; q <= M; ++q) { mc[q] *= inv; dc[q] *= inv; ic[q] *= inv; }
-      row[xS_] = xE;
-      totscale += std::log((double) xE);
-      xE = 1.0;
-    } else row[xS_] = 1.0f;
-    row[xE_] = xE; row[xN_] = xN; row[xJ_] = xJ; row[xB_] = xB; row[xC_] = xC;
-    std::swap(mp, mc); std::swap(ip, ic); std::swap(dp, dc);
-  }
-  if (std::isnan(xC) || (L > 0 && xC == 0.0f) || std::isinf(xC)) { if (ret_sc) *ret_sc = INFINITY; return P7X_ERANGE; }
-  if (ret_sc) *ret_sc = totscale + std::log((double) (xC * om.xf[XC][MOVE]));
-  return P7X_OK;
-}
-
-// Backward parser on a window: the special-state rows only, two rolling DP rows.  Operation for operation backward_full()
-// (same D chains, same sums), without its (L+1) x M matrices -- a 2,400-residue window of a 1,200-node model would
-// stream 70 MB through the host caches for rows the region scan never reads.  fx: Forward's rows (scale factors).
-static int lt_backward_parser(const Model &om, const uint8_t *dsq, int L, const std::vector<float> &fx, std::vector<float> &bx)
-{
-  const int M = om.M;
-  const float *__restrict bm = om.tf(0), *__restrict tMM = om.tf(1), *__restrict tIM = om.tf(2), *__restrict tDM = om.tf(3),
-              *__restrict tMD = om.tf(4), *__restrict tMI = om.tf(5), *__restrict tII = om.tf(6);
-  std::vector<float> buf((size_t) 7 * (M + 3), 0.0f);
-  float *mc = buf.data(), *ic = mc + (M + 3), *dc = ic + (M + 3), *mn = dc + (M + 3), *in = mn + (M + 3), *dn = in + (M + 3), *me = dn + (M + 3);
-  bx.assign((size_t) (L + 1) * NX, 0.0f);
-  auto X = [&](int r, int s) -> float & { return bx[(size_t) r * NX + s]; };
-  auto FS = [&](int r) { return fx[(size_t) r * NX + xS_]; };
-  bool own_scales = false;
-  float xJ = 0.f, xB = 0.f, xN = 0.f;
-  float xC = om.xf[XC][MOVE];
-  float xE = xC * om.xf[XE][MOVE];
-  {
-    mc[M + 1] = ic[M + 1] = dc[M + 1] = 0.0f;
-    for (int k = 1; k <= M; ++k) { dc[k] = xE; ic[k] = 0.0f; }
-    dchain_backward(om, dc);
-    for (int k = 1; k <= M; ++k) mc[k] = xE + dc[k + 1] * tMD[k];
-    mc[0] = ic[0] = dc[0] = 0.0f;
-    const float sc = FS(L);
-    if (sc > 1.0f) {
-      xE = xE / sc; xN = xN / sc; xC = xC / sc; xJ = xJ / sc; xB = xB / sc;
-      const float inv = 1.0 / sc;
-      for (int k = 1; k <= M; ++k) { mc[k] *= inv; dc[k] *= inv; ic[k] *= inv; }
-    }
-    X(L, xS_) = sc;
-    X(L, xE_) = xE; X(L, xN_) = xN; X(L, xJ_) = xJ; X(L, xB_) = xB; X(L, xC_) = xC;
-  }
-  for (int r = L - 1; r >= 1; --r) {
-    std::swap(mc, mn); std::swap(ic, in); std::swap(dc, dn);           // row r+1 becomes "next"
-    const float *__restrict rf = om.rf(dsq[r + 1]);
-    for (int k = 1; k <= M; ++k) me[k] = mn[k] * rf[k];
-    me[M + 1] = 0.0f;
-    xB = lanes_dot(om, me, bm);
-    xC = xC * om.xf[XC][LOOP];
-    xJ = (xB * om.xf[XJ][MOVE]) + (xJ * om.xf[XJ][LOOP]);
-    xN = (xB * om.xf[XN][MOVE]) + (xN * om.xf[XN][LOOP]);
-    xE = (xC * om.xf[XE][MOVE]) + (xJ * om.xf[XE][LOOP]);
-    mc[M + 1] = ic[M + 1] = dc[M + 1] = 0.0f;
-    for (int k = 1; k < M; ++k) {
-      const float mek = me[k + 1];
-      ic[k] = in[k] * tII[k] + mek * tIM[k + 1];
-      dc[k] = mek * tDM[k + 1] + xE;
-      mc[k] = (in[k] * tMI[k] + mek * tMM[k + 1]) + xE;
-    }
-    ic[M] = in[M] * tII[M]; dc[M] = xE; mc[M] = in[M] * tMI[M] + xE;
-    dchain_backward(om, dc);
-    for (int k = 1; k <= M; ++k) mc[k] += dc[k + 1] * tMD[k];
-    mc[0] = ic[0] = dc[0] = 0.0f;
-    if (xB > 1.0e16) own_scales = true;
-    const float sc = own_scales ? ((xB > 1.0e4) ? xB : 1.0f) : FS(r);
-    X(r, xS_) = sc;
-    if (sc > 1.0f) {
-      xE /= sc; xN /= sc; xJ /= sc; xB /= sc; xC /= sc;
-      const float inv = 1.0 / sc;
-      for (int k = 1; k <= M; ++k) { mc[k] *= inv; dc[k] *= inv; ic[k] *= inv; }
-    }
-    X(r, xE_) = xE; X(r, xN_) = xN; X(r, xJ_) = xJ; X(r, xB_) = xB; X(r, xC_) = xC;
-  }
-  {
-    const float *__restrict rf = om.rf(dsq[1]);
-    for (int k = 1; k <= M; ++k) me[k] = mc[k] * rf[k];
-    xB = lanes_dot(om, me, bm);
-    xN = (xB * om.xf[XN][MOVE]) + (xN * om.xf[XN][LOOP]);
-    X(0, xB_) = xB; X(0, xC_) = 0.0f; X(0, xJ_) = 0.0f; X(0, xN_) = xN; X(0, xE_) = 0.0f; X(0, xS_) = 1.0f;
-  }
-  if (std::isnan(xN) || (L > 0 && xN == 0.0f) || std::isinf(xN)) return P7X_ERANGE;
-  return P7X_OK;
-}
-
-// ---------------------------------------------------------------- Forward parser in upstream's summation order
-// impl_sse/fwdback.c forward_engine() adds its floats in the order the striped 4-lane vectors impose: node k lives in
-// lane z = (k-1) / Q of vector q = (k-1) % Q; xE is four per-lane sums over q (match cells first, delete cells after
-// the delete chain) folded as (l0 + l1) + (l2 + l3); the D->D chain is one serial sweep per lane and then up to three
-// carry sweeps from lane to lane (always three when M < 100, else until no cell grows).  The device kernels and
-// forward_full() above use other (faster) association orders, a few ulps apart -- which only matters for a target
-// whose P-value sits on the F3 threshold.  This routine is the tie-breaker for exactly those targets (the guard in
-// p7x_tophits.cpp): plain scalar code, lane by lane, same operations in the same order.
-// dsq[1..L]; multihit, length model of L as the pipeline configures the parser.
-static int forward_parser_striped(const Profile &p, const uint8_t *dsq, int L, float *ret_sc)
-{
-  const int M = p.M, Q = p.Q4();
-  Model om{ &p, M, {} };
-  om.configure(true, L);
-  const float *bm = om.tf(0), *tMM = om.tf(1), *tIM = om.tf(2), *tDM = om.tf(3), *tMD = om.tf(4), *tMI = om.tf(5), *tII = om.tf(6), *tDD = om.tf(7);
-  struct V { float v[4]; };
-  std::vector<V> mmo((size_t) Q, V{{0, 0, 0, 0}}), dmo = mmo, imo = mmo;
-  // transitions of vector q, lane z (node k = q + 1 + z Q); padding nodes, and the transitions that would leave node M, are zero
-  std::vector<V> vBM((size_t) Q), vMM = vBM, vIM = vBM, vDM = vBM, vMD = vBM, vMI = vBM, vII = vBM, vDD = vBM;
-  for (int q = 0; q < Q; ++q)
-    for (int z = 0; z < 4; ++z) {
-      const int k = q + 1 + z * Q;
-      const bool in = k <= M;
-      vBM[q].v[z] = in ? bm[k] : 0.0f; vMM[q].v[z] = in ? tMM[k] : 0.0f; vIM[q].v[z] = in ? tIM[k] : 0.0f; vDM[q].v[z] = in ? tDM[k] : 0.0f;
-      vMI[q].v[z] = in ? tMI[k] : 0.0f; vII[q].v[z] = in ? tII[k] : 0.0f;
-      vMD[q].v[z] = (k < M) ? tMD[k] : 0.0f; vDD[q].v[z] = (k < M) ? tDD[k] : 0.0f;
-    }
-  auto rightshift = [](const V &a) { return V{{ 0.0f, a.v[0], a.v[1], a.v[2] }}; };
-  float xE = 0.f, xN = 1.f, xJ = 0.f, xB = om.xf[XN][MOVE], xC = 0.f, totscale = 0.0f;
-  std::vector<V> rv((size_t) Q);
-  for (int i = 1; i <= L; ++i) {
-    const float *rf = om.rf(dsq[i]);
-    for (int q = 0; q < Q; ++q) for (int z = 0; z < 4; ++z) { const int k = q + 1 + z * Q; rv[q].v[z] = k <= M ? rf[k] : 0.0f; }
-    V dcv{{0, 0, 0, 0}}, xEv{{0, 0, 0, 0}};
-    V mpv = rightshift(mmo[Q - 1]), dpv = rightshift(dmo[Q - 1]), ipv = rightshift(imo[Q - 1]);
-    for (int q = 0; q < Q; ++q) {
-      V sv;
-      for (int z = 0; z < 4; ++z) {
-        float s = xB * vBM[q].v[z];
-        s = s + mpv.v[z] * vMM[q].v[z];
-        s = s + ipv.v[z] * vIM[q].v[z];
-        s = s + dpv.v[z] * vDM[q].v[z];
-        s = s * rv[q].v[z];
-        sv.v[z] = s;
-        xEv.v[z] = xEv.v[z] + s;
-      }
-      mpv = mmo[q]; dpv = dmo[q]; ipv = imo[q];
-      mmo[q] = sv;
-      dmo[q] = dcv;
-      for (int z = 0; z < 4; ++z) {
-        dcv.v[z] = sv.v[z] * vMD[q].v[z];
-        const float t = mpv.v[z] * vMI[q].v[z];
-        imo[q].v[z] = t + ipv.v[z] * vII[q].v[z];
-      }
-    }
-    dcv = rightshift(dcv);
-    dmo[0] = V{{0, 0, 0, 0}};
-    for (int q = 0; q < Q; ++q)
-      for (int z = 0; z < 4; ++z) { dmo[q].v[z] = dcv.v[z] + dmo[q].v[z]; dcv.v[z] = dmo[q].v[z] * vDD[q].v[z]; }
-    if (M < 100) {
-      for (int j = 1; j < 4; ++j) {
-        dcv = rightshift(dcv);
-        for (int q = 0; q < Q; ++q)
-          for (int z = 0; z < 4; ++z) { dmo[q].v[z] = dcv.v[z] + dmo[q].v[z]; dcv.v[z] = dcv.v[z] * vDD[q].v[z]; }
-      }
-    } else {
-      for (int j = 1; j < 4; ++j) {
-        bool grew = false;
-        dcv = rightshift(dcv);
-        for (int q = 0; q < Q; ++q)
-          for (int z = 0; z < 4; ++z) {
-            const float s = dcv.v[z] + dmo[q].v[z];
-            if (s > dmo[q].v[z]) grew = true;
-            dmo[q].v[z] = s;
-            dcv.v[z] = dcv.v[z] * vDD[q].v[z];
-          }
-        if (!grew) break;
-      }
-    }
-    for (int q = 0; q < Q; ++q) for (int z = 0; z < 4; ++z) xEv.v[z] = dmo[q].v[z] + xEv.v[z];
-    {
-      const float a0 = xEv.v[0] + xEv.v[1], a2 = xEv.v[2] + xEv.v[3];
-      xE = a0 + a2;
-    }
-    xN = xN * om.xf[XN][LOOP];
-    xC = (xC * om.xf[XC][LOOP]) + (xE * om.xf[XE][MOVE]);
-    xJ = (xJ * om.xf[XJ][LOOP]) + (xE * om.xf[XE][LOOP]);
-    xB = (xJ * om.xf[XJ][MOVE]) + (xN * om.xf[XN][MOVE]);
-    if (xE > 1.0e4) {
-      xN = xN / xE; xC = xC / xE; xJ = xJ / xE; xB = xB / xE;
-      const float inv = 1.0 / xE;
-      for (int q = 0; q < Q; ++q) for (int z = 0; z < 4; ++z) { mmo[q].v[z] = mmo[q].v[z] * inv; dmo[q].v[z] = dmo[q].v[z] * inv; imo[q].v[z] = imo[q].v[z] * inv; }
-      totscale += std::log((double) xE);
-      xE = 1.0;
-    }
-  }
-  if (std::isnan(xC) || (L > 0 && xC == 0.0f) || std::isinf(xC)) { *ret_sc = INFINITY; return P7X_ERANGE; }
-  *ret_sc = totscale + std::log((double) (xC * om.xf[XC][MOVE]));
-  return P7X_OK;
 }
 
 // ---------------------------------------------------------------- windows
@@ -419,7 +164,7 @@ static double lt_gumbel_invsurv(double P, double mu, double lambda) { return mu 
 static void lt_ssv_threshold(const Profile &p, int max_length, double F1, int *sc_thresh, int *xB, int *tjb)
 {
   const double invP = lt_gumbel_invsurv(F1, p.evparam[P7X_MMU], p.evparam[P7X_MLAMBDA]);
-  const float nullsc = lt_null1(max_length);
+  const float nullsc = null1_score(max_length);
   const int tjb_b = unbiased_byteify(p.scale_b, logf(3.0f / (float) (max_length + 3)));
   *sc_thresh = (int) std::ceil(((nullsc + (invP * kLog2) + 3.0) * p.scale_b) + p.base_b + p.tec_b + tjb_b);
   *xB = std::max((int) p.base_b - tjb_b - (int) p.tbm_b, 0);
@@ -474,40 +219,6 @@ static bool lt_replay(const Profile &p, const uint8_t *dsq, int64_t from, int64_
   return false;
 }
 
-struct LtRow { int64_t pos; int k, sc; };       // a row the device scan reported: position on the strand, upstream's cell
-
-// Upstream's sequential bookkeeping over the rows the reset-free scan reported for one block of one strand.  Rows are
-// positions inside the block (1..L), ascending.
-static void lt_seeds_from_rows(const Profile &p, const uint8_t *dsq, int64_t L, const std::vector<LtRow> &rows, int sc_thresh, int xB,
-                               std::vector<LtWindow> &seeds)
-{
-  const int M = p.M;
-  // The scan restarts (all cells at the begin score) behind every seed and at the block start; rows up to M behind a
-  // restart are its "shadow": a diagonal through them may have begun before the restart, so the reset-free scores of the
-  // device do not apply there.  Outside shadows they are upstream's.
-  int64_t restart = 0;             // the scan restarted at row restart + 1
-  bool shadow = true;              // rows restart + 1 .. restart + M still have to be looked at
-  int64_t skip_to = 0;             // rows up to here are behind us (consumed by a seed's diagonal, or replayed)
-  size_t idx = 0;
-  while (idx < rows.size()) {
-    const LtRow &r = rows[idx];
-    if (r.pos <= skip_to) { ++idx; continue; }
-    int64_t row = r.pos; int k = r.k, sc = r.sc;
-    if (shadow && r.pos <= restart + M) {
-      // replay the scan from the restart; a true crossing can only be at a row the device reported, so the replay ends at
-      // the last reported row inside the shadow
-      int64_t to = r.pos;
-      for (size_t j = idx; j < rows.size() && rows[j].pos <= restart + M; ++j) to = rows[j].pos;
-      to = std::min(to, L);
-      if (!lt_replay(p, dsq, restart + 1, to, sc_thresh, xB, &row, &k, &sc)) { skip_to = to; shadow = false; continue; }
-    }
-    LtWindow w;
-    const int64_t end = lt_seed_from_cell(p, dsq, L, row, k, sc, xB, &w);
-    seeds.push_back(w);
-    restart = end; shadow = true; skip_to = end;
-  }
-}
-
 // ---------------------------------------------------------------- one window past the SSV filter
 struct LtTarget { int64_t idx; const char *name, *acc, *desc; int64_t length; };
 
@@ -527,10 +238,10 @@ struct LtCounters { uint64_t n_past_msv = 0, n_past_bias = 0, n_past_vit = 0, n_
 static bool lt_forward_test(const p7x_pipeline_cfg &cfg, const Profile &p, int64_t window_len, const uint8_t *subseq, float fwdsc)
 {
   const int64_t F3_L = std::min<int64_t>(window_len, cfg.B3);
-  const float nullsc = lt_null1(window_len);
+  const float nullsc = null1_score((int) window_len);
   float filtersc = nullsc;
   if (cfg.do_biasfilter) {
-    float bias_filtersc = lt_bias_filter(p, subseq, window_len);
+    float bias_filtersc = bias_filter_score(p, subseq, window_len);
     bias_filtersc -= nullsc;
     filtersc = nullsc + (bias_filtersc * (F3_L > window_len ? 1.0f : (float) F3_L / (float) window_len));
   }
@@ -552,7 +263,7 @@ static int lt_post_viterbi(const p7x_pipeline_cfg &cfg, const Profile &p, const 
   DomainDefResult dd;
   int st = P7X_OK;
   if (dev && dev->n == -1) return P7X_OK;                      // p7_DomainDecoding: eslERANGE, nothing comes of this window
-  t_long_target = &lto;
+  LongTargetScope scope(lto);
   if (dev && dev->n >= 0) {
     st = domaindef_from_regions(p, subseq, (int) window_len, dev->nexpected, dev->regs.data(), dev->n, cfg.seed, cfg.seed != 0, dd, nullptr, 0);
   } else {
@@ -563,11 +274,10 @@ static int lt_post_viterbi(const p7x_pipeline_cfg &cfg, const Profile &p, const 
     om.configure(true, (int) window_len);
     std::vector<float> fx, bx;
     float sc2 = 0.0f;
-    lt_forward_parser(om, subseq, (int) window_len, fx, &sc2);
-    lt_backward_parser(om, subseq, (int) window_len, fx, bx);
+    forward_parser_lanes(om, subseq, (int) window_len, fx, &sc2);
+    backward_parser_lanes(om, subseq, (int) window_len, fx, bx);
     st = domaindef_by_posterior_heuristics(p, subseq, (int) window_len, fx.data(), bx.data(), cfg.seed, cfg.seed != 0, dd, nullptr, 0);
   }
-  t_long_target = nullptr;
   if (st != P7X_OK) return st == P7X_ERANGE ? P7X_OK : st;
   if ((debug_opt(OPT_TRACE_LONGTARGET) > 0)) {
     std::fprintf(stderr, "[lt] window start %lld len %lld compl %d fwd %.3f: nregions %d nclustered %d nenvelopes %d ndom %zu\n",
@@ -592,7 +302,7 @@ static int lt_window_hits(const p7x_pipeline_cfg &cfg, const Profile &p, int max
     bitscore -= 2 * log(2. / (env_len + 2)) + (env_len - ali_len) * log((float) env_len / (float) (env_len + 2));
     bitscore += 2 * log(2. / (max_length + 2));
     bitscore += (std::max<int64_t>(max_length, env_len) - ali_len) * log((float) max_length / (float) (max_length + 2));
-    const float dom_nullsc = lt_null1(std::max<int64_t>(max_length, env_len));
+    const float dom_nullsc = null1_score((int) std::max<int64_t>(max_length, env_len));
     const float dom_bias = cfg.do_null2 ? dom.domcorrection : 0.0f;      // long targets: the correction is the bias (no omega prior)
     const float dom_score = (bitscore - (dom_nullsc + dom_bias)) / (float) kLog2;
     const double dom_lnP = exp_logsurv(dom_score, p.evparam[P7X_FTAU], p.evparam[P7X_FLAMBDA]);
@@ -641,7 +351,7 @@ static LtPrefilter lt_window_prefilter(const p7x_pipeline_cfg &cfg, const Profil
 {
   LtPrefilter out;
   const int64_t F1_L = std::min<int64_t>(window_len, cfg.B1), F2_L = std::min<int64_t>(window_len, cfg.B2);
-  const float nullsc = lt_null1(window_len);
+  const float nullsc = null1_score((int) window_len);
   // the full MSV score of the window (SSV only seeded it)
   const float usc = (wf && wf->have) ? wf->usc : lt_msv(p, subseq, window_len);
   double P = gumbel_surv((usc - nullsc) / kLog2, p.evparam[P7X_MMU], p.evparam[P7X_MLAMBDA]);
@@ -649,7 +359,7 @@ static LtPrefilter lt_window_prefilter(const p7x_pipeline_cfg &cfg, const Profil
   ctr.n_past_msv++; ctr.pos_past_msv += (uint64_t) window_len;
   float bias_filtersc = 0.0f, filtersc = nullsc;
   if (cfg.do_biasfilter) {
-    bias_filtersc = ((wf && wf->have) ? wf->bias_filtersc : lt_bias_filter(p, subseq, window_len)) - nullsc;
+    bias_filtersc = ((wf && wf->have) ? wf->bias_filtersc : bias_filter_score(p, subseq, window_len)) - nullsc;
     filtersc = nullsc + (bias_filtersc * (F1_L > window_len ? 1.0f : (float) F1_L / (float) window_len));
     P = gumbel_surv((usc - filtersc) / kLog2, p.evparam[P7X_MMU], p.evparam[P7X_MLAMBDA]);
     if (P > cfg.F1) return out;
@@ -683,65 +393,6 @@ static void lt_block_windows(const LtScoreData &sd, int max_length, int64_t bloc
 }
 
 // ---------------------------------------------------------------- hit list: E-values, duplicates
-// E-values, duplicates, order and thresholds of a long-target hit list whose hits still carry per-window P-values
-static void lt_finalize(p7x_tophits *th, int max_length, double res_count)
-{
-  std::vector<Hit> &hits = th->hits;
-  // p7_tophits_ComputeNhmmerEvalues: the P-value of a hit refers to one window of max_length; scale by the windows searched
-  for (Hit &h : hits) {
-    h.lnP += std::log((double) ((float) res_count / (float) max_length));
-    h.dcl[0].lnP = h.lnP;
-    h.sortkey = -1.0 * h.lnP;
-  }
-  // p7_tophits_SortBySeqidxAndAlipos + p7_tophits_RemoveDuplicates: the same region found in two overlapping blocks or
-  // windows; the hit with the better E-value stays
-  std::vector<size_t> ord(hits.size());
-  for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
-  auto lo = [&](const Hit &h) { return std::min(h.dcl[0].iali, h.dcl[0].jali); };
-  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
-    if (hits[a].seqidx != hits[b].seqidx) return hits[a].seqidx < hits[b].seqidx;
-    const bool ca = hits[a].dcl[0].iali > hits[a].dcl[0].jali, cb = hits[b].dcl[0].iali > hits[b].dcl[0].jali;
-    if (ca != cb) return !ca;
-    if (lo(hits[a]) != lo(hits[b])) return lo(hits[a]) < lo(hits[b]);
-    return a < b;
-  });
-  size_t j = 0;
-  for (size_t q = 1; q < ord.size(); ++q) {
-    Hit &hj = hits[ord[j]], &hi = hits[ord[q]];
-    const bool cj = hj.dcl[0].iali > hj.dcl[0].jali, ci = hi.dcl[0].iali > hi.dcl[0].jali;
-    bool dup = false;
-    if (hj.seqidx == hi.seqidx && cj == ci) {
-      const int64_t sj = std::min(hj.dcl[0].iali, hj.dcl[0].jali), ej = std::max(hj.dcl[0].iali, hj.dcl[0].jali);
-      const int64_t si = std::min(hi.dcl[0].iali, hi.dcl[0].jali), ei = std::max(hi.dcl[0].iali, hi.dcl[0].jali);
-      const int64_t inter = std::min(ei, ej) - std::max(si, sj) + 1;
-      const int64_t li = ei - si + 1, lj = ej - sj + 1;
-      // upstream: only hits on similar parts of the model (their model ranges intersect) can be duplicates of each
-      // other -- tandem or partial repeat copies with flush ends but different model ranges are both kept
-      const int hmm_inter = std::min(hi.dcl[0].hmmto, hj.dcl[0].hmmto) - std::max(hi.dcl[0].hmmfrom, hj.dcl[0].hmmfrom) + 1;
-      if (hmm_inter > 0 && ((std::llabs(si - sj) <= 3) || (std::llabs(ei - ej) <= 3) || inter >= 0.95 * (double) li || inter >= 0.95 * (double) lj)) dup = true;
-    }
-    if (dup) {
-      const size_t remove = hi.lnP < hj.lnP ? j : q;
-      hits[ord[remove]].flags |= P7X_IS_DUPLICATE;
-      if (remove == j) j = q;
-    } else j = q;
-  }
-  th->order.clear(); th->sorted_by_key = false;
-  tophits_sort_by_key(*th);
-  tophits_threshold(*th);
-  th->ctr.n_output = th->ctr.pos_output = 0;
-  for (const Hit &h : th->hits)
-    if (h.flags & (P7X_IS_REPORTED | P7X_IS_INCLUDED)) { th->ctr.n_output++; th->ctr.pos_output += 1 + (uint64_t) std::llabs(h.dcl[0].jali - h.dcl[0].iali); }
-  th->lt_unfinished = false;
-}
-
-static double lt_res_count(const p7x_pipeline_cfg &cfg, uint64_t nres)
-{
-  double res_count = (double) nres;
-  if (cfg.Z_setby != P7X_ZSETBY_NTARGETS) { res_count = 1000000.0 * cfg.Z; if (cfg.strands == P7X_STRAND_BOTH) res_count *= 2; }
-  return res_count;
-}
-
 static void lt_finish_tophits(const p7x_pipeline_cfg &cfg_in, const Profile &p, int max_length, uint64_t nres, uint64_t nseqs,
                               const LtCounters &ctr, std::vector<Hit> &hits, p7x_tophits **out)
 {
@@ -756,7 +407,7 @@ static void lt_finish_tophits(const p7x_pipeline_cfg &cfg_in, const Profile &p, 
   th->lt_evalue_window = max_length;
   th->lt_unfinished = true;
   // one part of several: the parts are finished together (p7x_tophits_merge_longtargets)
-  if (cfg_in.lt_nparts <= 1) lt_finalize(th.get(), max_length, lt_res_count(cfg_in, nres));
+  if (cfg_in.lt_nparts <= 1) longtarget_finalize(th.get(), max_length, longtarget_res_count(cfg_in, nres));
   *out = th.release();
 }
 
@@ -767,20 +418,13 @@ static void lt_match_probabilities(const Profile &p, std::vector<float> &mp)
     for (int x = 0; x < p.K; ++x) mp[(size_t) k * p.K + x] = p.rf_[(size_t) x * (p.M + 1) + k] * p.bgf[x];
 }
 
-static const uint8_t *lt_complement_table(int abc_type)
-{ // Easel's complement of every DNA / RNA residue code: ACGT-RYMKSWHBVDN*~
-  static const uint8_t comp[18] = { 3, 2, 1, 0, 4, 6, 5, 8, 7, 9, 10, 14, 13, 12, 11, 15, 16, 17 };
-  (void) abc_type;
-  return comp;
-}
-
-struct LtSeedIn { int64_t target, block_start; int strand; LtWindow w; };
+} // namespace
 
 // The whole host side for a set of targets, given the SSV seeds of every (target, block, strand).  <filters>, when
 // given, scores all windows of a target in one device batch before the host sees them.
-static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, const uint8_t *dsq, const int64_t *offsets, const int64_t *lengths, size_t n,
-                       const char *const *names, const char *const *accs, const char *const *descs,
-                       const std::vector<LtSeedIn> &seeds_in, p7x_tophits **out, LongTargetWindowScorer *filters)
+int longtarget_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, const uint8_t *dsq, const int64_t *offsets, const int64_t *lengths, size_t n,
+                        const char *const *names, const char *const *accs, const char *const *descs,
+                        const std::vector<LongTargetSeed> &seeds_in, p7x_tophits **out, LongTargetWindowScorer *filters)
 {
   const Profile &p = om->p;
   if (p.abc_type != P7X_DNA && p.abc_type != P7X_RNA) { set_error("long-target pipeline needs a nucleotide model"); return P7X_EINVAL; }
@@ -792,7 +436,7 @@ static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, cons
   LtScoreData sd; lt_scoredata(p, sd);
   std::vector<float> mp; lt_match_probabilities(p, mp);
   LongTargetOpts lto; lto.do_null2 = cfg.do_null2 != 0; lto.match_prob = mp.data();
-  const uint8_t *comp = lt_complement_table(p.abc_type);
+  const uint8_t *comp = longtarget_complement(p.abc_type);
   std::vector<Hit> hits;
   LtCounters ctr;
   uint64_t nres = 0;
@@ -833,7 +477,7 @@ static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, cons
         const bool mine = units.mine(unit++);                // another part's unit: only its residues are counted here
         std::vector<LtWindow> seeds;
         while (sidx < seeds_in.size() && seeds_in[sidx].target == (int64_t) t && seeds_in[sidx].block_start == i && seeds_in[sidx].strand == strand)
-          seeds.push_back(seeds_in[sidx++].w);
+          { const LongTargetSeed &s = seeds_in[sidx++]; seeds.push_back(LtWindow{ s.n, s.k, s.length }); }
         BlockJob job{ t, i, bn, bc, bw, strand, nres, {}, nwin };
         if (mine) lt_block_windows(sd, max_length, bn, std::move(seeds), job.windows);
         nwin += job.windows.size();
@@ -964,7 +608,7 @@ static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, cons
         Model om{ &p, p.M, {} };
         om.prepare(); om.configure(true, (int) vj[z].vw.length);
         std::vector<float> fx;
-        lt_forward_parser(om, subs[z].data(), (int) vj[z].vw.length, fx, &fwd_of[z]);
+        forward_parser_lanes(om, subs[z].data(), (int) vj[z].vw.length, fx, &fwd_of[z]);
       }
       pass[z] = lt_forward_test(cfg, p, vj[z].vw.length, subs[z].data(), fwd_of[z]) ? 1 : 0;
       if (!pass[z]) std::vector<uint8_t>().swap(subs[z]);
@@ -1023,10 +667,9 @@ static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, cons
       if (dev_env && dr && dr->n >= 0) {           // phase A: regions -> queued envelopes; multi-domain regions resolved here, on the host
         jc[z].n_past_fwd++; jc[z].pos_past_fwd += (uint64_t) vw.length;
         WinDD &w = wdd[z];
-        t_long_target = &lto;
+        LongTargetScope scope(lto);
         int st = domaindef_from_regions(p, subs[z].data(), (int) vw.length, dr->nexpected, dr->regs.data(), dr->n, cfg.seed, cfg.seed != 0, w.dd, &w.defer, (int) z);
         if (st == P7X_OK) st = domaindef_finish_multi(p, subs[z].data(), (int) vw.length, cfg.seed, cfg.seed != 0, w.dd, nullptr, (int) z);
-        t_long_target = nullptr;
         if (st != P7X_OK && st != P7X_ERANGE) jst[z] = st;
         w.active = st == P7X_OK;
         return;
@@ -1096,7 +739,7 @@ static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, cons
         const int L = (int) vj[z].vw.length;
         const uint8_t *dsq = subs[z].data();
         std::vector<Domain> kept;
-        thread_local Workspace hws;
+        thread_local DomainWorkspace hws;
         thread_local Trace tr;
         for (Domain &d : w.dd.dcl) {
           if (d.deferred == -2) { for (Domain &m : w.dd.multi[(size_t) d.multi_slot]) kept.push_back(std::move(m)); continue; }
@@ -1137,13 +780,6 @@ static int lt_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, cons
   return P7X_OK;
 }
 
-} // namespace
-
-// ---- what the device half (p7x_longtarget.hip) needs from here
-// the F3 tie-breaker of p7x_tophits.cpp: Forward parser score in upstream's summation order, and the filter's null score
-int host_forward_parser_exact(const Profile &p, const uint8_t *dsq1, int L, float *sc) { return forward_parser_striped(p, dsq1, L, sc); }
-float host_filter_null_score(const Profile &p, const uint8_t *dsq1, int L, bool do_bias) { return do_bias ? lt_bias_filter(p, dsq1, L) : lt_null1(L); }
-
 int longtarget_setup(const p7x_pipeline_cfg &cfg, const Profile &p, int *max_length, int *sc_thresh, int *xB)
 {
   if (p.abc_type != P7X_DNA && p.abc_type != P7X_RNA) { set_error("long-target pipeline needs a nucleotide model"); return P7X_EINVAL; }
@@ -1155,8 +791,6 @@ int longtarget_setup(const p7x_pipeline_cfg &cfg, const Profile &p, int *max_len
   return P7X_OK;
 }
 
-const uint8_t *longtarget_complement(int abc_type) { return lt_complement_table(abc_type); }
-
 void LongTargetUnits::count(const p7x_pipeline_cfg &cfg, int max_length, const int64_t *lengths, size_t n)
 {
   W = cfg.block_length; C = max_length; strands = cfg.strands == P7X_STRAND_BOTH ? 2 : 1;
@@ -1165,51 +799,116 @@ void LongTargetUnits::count(const p7x_pipeline_cfg &cfg, int max_length, const i
   for (size_t t = 0; t < n; ++t) for (int64_t i = 0; i < lengths[t]; i += W - C) total += (uint64_t) strands;
 }
 
-void longtarget_finalize(p7x_tophits *th, int evalue_window, double res_count) { lt_finalize(th, evalue_window, res_count); }
-double longtarget_res_count(const p7x_pipeline_cfg &cfg, uint64_t nres) { return lt_res_count(cfg, nres); }
-
-void longtarget_seeds_from_rows(const Profile &p, const uint8_t *block_dsq, int64_t L, const LongTargetRow *rows, size_t nrows,
-                                int sc_thresh, int xB, std::vector<int64_t> &seeds3)
-{
-  std::vector<LtRow> r(nrows);
-  for (size_t i = 0; i < nrows; ++i) r[i] = LtRow{ rows[i].pos, rows[i].k, rows[i].sc };
-  std::vector<LtWindow> w;
-  lt_seeds_from_rows(p, block_dsq, L, r, sc_thresh, xB, w);
-  for (const LtWindow &x : w) { seeds3.push_back(x.n); seeds3.push_back(x.k); seeds3.push_back(x.length); }
+const uint8_t *longtarget_complement(int abc_type)
+{ // Easel's complement of every DNA / RNA residue code: ACGT-RYMKSWHBVDN*~
+  static const uint8_t comp[18] = { 3, 2, 1, 0, 4, 6, 5, 8, 7, 9, 10, 14, 13, 12, 11, 15, 16, 17 };
+  (void) abc_type;
+  return comp;
 }
 
-int longtarget_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, const uint8_t *dsq, const int64_t *offsets, const int64_t *lengths,
-                        size_t n, const char *const *names, const char *const *accs, const char *const *descs,
-                        const std::vector<LongTargetSeed> &seeds, p7x_tophits **out, LongTargetWindowScorer *filters)
+// E-values, duplicates, order and thresholds of a long-target hit list whose hits still carry per-window P-values
+void longtarget_finalize(p7x_tophits *th, int max_length, double res_count)
 {
-  std::vector<LtSeedIn> in(seeds.size());
-  for (size_t s = 0; s < seeds.size(); ++s) in[s] = LtSeedIn{ seeds[s].target, seeds[s].block_start, seeds[s].strand, LtWindow{ seeds[s].n, seeds[s].k, seeds[s].length } };
-  return lt_run_host(cfg, om, dsq, offsets, lengths, n, names, accs, descs, in, out, filters);
+  std::vector<Hit> &hits = th->hits;
+  // p7_tophits_ComputeNhmmerEvalues: the P-value of a hit refers to one window of max_length; scale by the windows searched
+  for (Hit &h : hits) {
+    h.lnP += std::log((double) ((float) res_count / (float) max_length));
+    h.dcl[0].lnP = h.lnP;
+    h.sortkey = -1.0 * h.lnP;
+  }
+  // p7_tophits_SortBySeqidxAndAlipos + p7_tophits_RemoveDuplicates: the same region found in two overlapping blocks or
+  // windows; the hit with the better E-value stays
+  std::vector<size_t> ord(hits.size());
+  for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
+  auto lo = [&](const Hit &h) { return std::min(h.dcl[0].iali, h.dcl[0].jali); };
+  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
+    if (hits[a].seqidx != hits[b].seqidx) return hits[a].seqidx < hits[b].seqidx;
+    const bool ca = hits[a].dcl[0].iali > hits[a].dcl[0].jali, cb = hits[b].dcl[0].iali > hits[b].dcl[0].jali;
+    if (ca != cb) return !ca;
+    if (lo(hits[a]) != lo(hits[b])) return lo(hits[a]) < lo(hits[b]);
+    return a < b;
+  });
+  size_t j = 0;
+  for (size_t q = 1; q < ord.size(); ++q) {
+    Hit &hj = hits[ord[j]], &hi = hits[ord[q]];
+    const bool cj = hj.dcl[0].iali > hj.dcl[0].jali, ci = hi.dcl[0].iali > hi.dcl[0].jali;
+    bool dup = false;
+    if (hj.seqidx == hi.seqidx && cj == ci) {
+      const int64_t sj = std::min(hj.dcl[0].iali, hj.dcl[0].jali), ej = std::max(hj.dcl[0].iali, hj.dcl[0].jali);
+      const int64_t si = std::min(hi.dcl[0].iali, hi.dcl[0].jali), ei = std::max(hi.dcl[0].iali, hi.dcl[0].jali);
+      const int64_t inter = std::min(ei, ej) - std::max(si, sj) + 1;
+      const int64_t li = ei - si + 1, lj = ej - sj + 1;
+      // upstream: only hits on similar parts of the model (their model ranges intersect) can be duplicates of each
+      // other -- tandem or partial repeat copies with flush ends but different model ranges are both kept
+      const int hmm_inter = std::min(hi.dcl[0].hmmto, hj.dcl[0].hmmto) - std::max(hi.dcl[0].hmmfrom, hj.dcl[0].hmmfrom) + 1;
+      if (hmm_inter > 0 && ((std::llabs(si - sj) <= 3) || (std::llabs(ei - ej) <= 3) || inter >= 0.95 * (double) li || inter >= 0.95 * (double) lj)) dup = true;
+    }
+    if (dup) {
+      const size_t remove = hi.lnP < hj.lnP ? j : q;
+      hits[ord[remove]].flags |= P7X_IS_DUPLICATE;
+      if (remove == j) j = q;
+    } else j = q;
+  }
+  th->order.clear(); th->sorted_by_key = false;
+  tophits_sort_by_key(*th);
+  tophits_threshold(*th);
+  th->ctr.n_output = th->ctr.pos_output = 0;
+  for (const Hit &h : th->hits)
+    if (h.flags & (P7X_IS_REPORTED | P7X_IS_INCLUDED)) { th->ctr.n_output++; th->ctr.pos_output += 1 + (uint64_t) std::llabs(h.dcl[0].jali - h.dcl[0].iali); }
+  th->lt_unfinished = false;
+}
+
+double longtarget_res_count(const p7x_pipeline_cfg &cfg, uint64_t nres)
+{
+  double res_count = (double) nres;
+  if (cfg.Z_setby != P7X_ZSETBY_NTARGETS) { res_count = 1000000.0 * cfg.Z; if (cfg.strands == P7X_STRAND_BOTH) res_count *= 2; }
+  return res_count;
+}
+
+// Upstream's sequential bookkeeping over the rows the reset-free scan reported for one block of one strand.  Rows are
+// positions inside the block (1..L), ascending.
+void longtarget_seeds_from_rows(const Profile &p, const uint8_t *dsq, int64_t L, const LongTargetRow *rows, size_t nrows,
+                                int sc_thresh, int xB, std::vector<int64_t> &seeds3)
+{
+  const int M = p.M;
+  // The scan restarts (all cells at the begin score) behind every seed and at the block start; rows up to M behind a
+  // restart are its "shadow": a diagonal through them may have begun before the restart, so the reset-free scores of the
+  // device do not apply there.  Outside shadows they are upstream's.
+  int64_t restart = 0;             // the scan restarted at row restart + 1
+  bool shadow = true;              // rows restart + 1 .. restart + M still have to be looked at
+  int64_t skip_to = 0;             // rows up to here are behind us (consumed by a seed's diagonal, or replayed)
+  size_t idx = 0;
+  while (idx < nrows) {
+    const LongTargetRow &r = rows[idx];
+    if (r.pos <= skip_to) { ++idx; continue; }
+    int64_t row = r.pos; int k = r.k, sc = r.sc;
+    if (shadow && r.pos <= restart + M) {
+      // replay the scan from the restart; a true crossing can only be at a row the device reported, so the replay ends at
+      // the last reported row inside the shadow
+      int64_t to = r.pos;
+      for (size_t j = idx; j < nrows && rows[j].pos <= restart + M; ++j) to = rows[j].pos;
+      to = std::min(to, L);
+      if (!lt_replay(p, dsq, restart + 1, to, sc_thresh, xB, &row, &k, &sc)) { skip_to = to; shadow = false; continue; }
+    }
+    LtWindow w;
+    const int64_t end = lt_seed_from_cell(p, dsq, L, row, k, sc, xB, &w);
+    seeds3.push_back(w.n); seeds3.push_back(w.k); seeds3.push_back(w.length);
+    restart = end; shadow = true; skip_to = end;
+  }
 }
 
 } // namespace p7x
 
-using namespace p7x;
-
-extern "C" {
-
-int p7x_forward_parser_exact(const p7x_oprofile *om, const uint8_t *dsq, int32_t L, float *sc)
+extern "C" int p7x_longtarget_from_seeds(const p7x_pipeline_cfg *cfg, const p7x_oprofile *om,
+                                         const uint8_t *dsq, const int64_t *offsets, const int64_t *lengths, size_t n,
+                                         const char *const *names, const char *const *accs, const char *const *descs,
+                                         const int64_t *seed_target, const int64_t *seed_block, const int32_t *seed_strand,
+                                         const int64_t *seeds, size_t nseeds, p7x_tophits **out)
 {
-  if (!om || !sc || L < 0 || (L > 0 && !dsq)) { set_error("p7x_forward_parser_exact: bad arguments"); return P7X_EINVAL; }
-  return forward_parser_striped(om->p, dsq, L, sc);
-}
-
-int p7x_longtarget_from_seeds(const p7x_pipeline_cfg *cfg, const p7x_oprofile *om,
-                              const uint8_t *dsq, const int64_t *offsets, const int64_t *lengths, size_t n,
-                              const char *const *names, const char *const *accs, const char *const *descs,
-                              const int64_t *seed_target, const int64_t *seed_block, const int32_t *seed_strand,
-                              const int64_t *seeds, size_t nseeds, p7x_tophits **out)
-{
+  using namespace p7x;
   if (!cfg || !om || !out || (n && (!dsq || !offsets || !lengths))) { set_error("p7x_longtarget_from_seeds: bad arguments"); return P7X_EINVAL; }
-  std::vector<LtSeedIn> in(nseeds);
+  std::vector<LongTargetSeed> in(nseeds);
   for (size_t s = 0; s < nseeds; ++s)
-    in[s] = LtSeedIn{ seed_target[s], seed_block[s], seed_strand[s], LtWindow{ seeds[3 * s], (int) seeds[3 * s + 1], seeds[3 * s + 2] } };
-  return lt_run_host(*cfg, om, dsq, offsets, lengths, n, names, accs, descs, in, out, nullptr);
+    in[s] = LongTargetSeed{ seed_target[s], seed_block[s], seed_strand[s], seeds[3 * s], (int) seeds[3 * s + 1], seeds[3 * s + 2] };
+  return longtarget_run_host(*cfg, om, dsq, offsets, lengths, n, names, accs, descs, in, out, nullptr);
 }
-
-} // extern "C"

@@ -10,7 +10,7 @@
 // of warm-up so that every diagonal that can reach a row of the chunk is complete.  A reset can only lower scores, so
 // the rows that reach the threshold upstream are a subset of the rows reported here; the host replays upstream's
 // sequential bookkeeping (choice of the seed cell, diagonal recovery and extension, skip-ahead) on the reported rows
-// (p7x_longtarget.inc.hpp).
+// (p7x_longtarget_host.cpp).
 //
 // Layout: the model is split across the 64 lanes, R packed int16 pairs per lane.  Global register g = lane*R + j holds
 // cells (2g-1, 2g) on odd rows and (2g, 2g+1) on even rows (the MSV kernel's parity trick: the diagonal move costs

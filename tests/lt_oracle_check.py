@@ -1,6 +1,6 @@
 """The long-target pipeline's tail checked from OUTSIDE the product: oracle/p7_oracle_lt.c restates window merging, the MSV /
 bias tests, the long-target Viterbi scan, the Forward test and the scoring rule of an envelope apart from the product's
-p7x_longtarget.inc.hpp; this module walks the (block, strand) units of a search as the reference's loop does
+p7x_longtarget_host.cpp; this module walks the (block, strand) units of a search as the reference's loop does
 (plan7.pyx:7541-7664) and compares a product hit list with what the oracle lets through."""
 import numpy as np
 

@@ -442,6 +442,48 @@ def test_forward_parser_in_reference_summation_order_is_bit_identical_to_the_ora
                 assert np.float32(got.value).tobytes() == np.float32(want).tobytes(), (name, s.name, got.value, want)
 
 
+def test_parser_rows_in_reference_summation_order_are_bit_identical_to_the_oracle(models, oracle, proteome):
+    """The rows the region-scan guard scans again (parser_rows_upstream through p7x_debug_parser_rows: the rows-only
+    Forward / Backward engines in upstream's order) are the reference parsers' special-state rows bit for bit: short
+    (M < 100), mid-size and long protein models on short targets and on targets long enough to rescale, and a 1,203-node
+    DNA model on windows of its fixture.  (The full-matrix engines gave these same bytes on these inputs before the
+    rows-only ones replaced them here.)"""
+    import ctypes as C
+    import numpy as np
+    from pyhmmer_amd import _lib, easel, plan7
+    lib = _lib.lib()
+    rng = np.random.default_rng(7)
+    cases = []
+    for name in ("RREFam", "PF02826", "LuxC"):
+        seqs = [proteome[i] for i in rng.choice(len(proteome), size=25, replace=False)]
+        seqs.sort(key=len)
+        cases.append((models[name][0], [np.asarray(s.sequence, dtype=np.uint8) for s in seqs[:6] + seqs[-3:]]))
+    luxc = models["LuxC"][0]
+    with easel.SequenceFile(GOLDEN / "seqs" / "LuxC.faa", digital=True, alphabet=luxc.alphabet) as sf:
+        cases.append((luxc, [np.asarray(s.sequence, dtype=np.uint8) for s in list(sf.read_block())[:4]]))      # homologs: rescaled rows
+    bmyd = load_hmms("bmyD")[0]
+    with easel.SequenceFile(GOLDEN / "seqs" / "bmyD.fna", digital=True, alphabet=bmyd.alphabet) as sf:
+        dna = np.asarray(next(iter(sf.read_block())).sequence, dtype=np.uint8)
+    cases.append((bmyd, [dna[:300], dna[:3000]]))
+    nrescaled = 0
+    for hmm, targets in cases:
+        bg = plan7.Background(hmm.alphabet)
+        op = oracle.OracleProfile(hmm, bg, 400)
+        om = plan7.OptimizedProfile(hmm, bg, 400)
+        for a in targets:
+            L = len(a)
+            st, _, want_f, want_b = op.bck(a)
+            d = np.concatenate([[255], a, [255]]).astype(np.uint8)
+            fx = np.zeros((L + 1, 6), np.float32); bx = np.zeros((L + 1, 6), np.float32)
+            st2 = lib.p7x_debug_parser_rows(om._handle, d.ctypes.data, L, fx.ctypes.data, bx.ctypes.data)
+            assert (st == 0) == (st2 == 0)
+            if st == 0:
+                assert fx.tobytes() == want_f.tobytes(), (hmm.name, L, "forward rows")
+                assert bx.tobytes() == want_b.tobytes(), (hmm.name, L, "backward rows")
+                nrescaled += int((fx[:, 5] > 1).sum())
+    assert nrescaled > 0
+
+
 def test_f3_guard_follows_the_reference_order_on_the_threshold(models, oracle, proteome):
     """A target whose Forward P-value is put exactly on F3 (and one ulp beside it) is kept / dropped as the reference's
     arithmetic says, whatever score the first stage handed over: the first stage lets the guard band through, the host
