@@ -289,6 +289,10 @@ size_t p7x_pending_nqueries(const p7x_pending *pending);
  * residue (a table + series evaluation in double; claimed to round to the same float as the C library's logarithm, which
  * is what the reference's esl_hmm_Forward calls: tests/test_gpu_filters.py checks every float of [2^-7, 2^7)). */
 int  p7x_debug_log_of_float(int device, const float *in, float *out, size_t n);
+/* Test seam of the memory pools (csrc/p7x_devmem.hpp), in bytes: out[0] = device memory obtained from the runtime through the
+ * slab pool of <device> and not yet freed, [1] = of that, parked in the pool; [2] = pinned host memory obtained (process-wide),
+ * [3] = of that, parked.  A workload that runs a second time on pooled objects must leave all four as they were. */
+int  p7x_debug_memory_stats(int device, int64_t out[4]);
 /* Test seams of the stochastic traceback ensembles (p7_domaindef.c region_trace_ensemble; p7_domaindef.pxd:23-59).
  * p7x_debug_choice: one choice point of p7_StochasticTrace with n paths of weights p[], for the generator state x after the
  *   draw: the path taken through the integer thresholds the product uses and through esl_rnd_FChoose as the reference

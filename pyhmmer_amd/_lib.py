@@ -17,7 +17,7 @@ _ROOT = _PKG.parent
 CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libp7x.so"
 
-SOURCES = ["p7x_profile.cpp", "p7x_device.hip", "p7x_devimage.hip", "p7x_msv.hip", "p7x_vitfwd.hip", "p7x_vitpk.hip", "p7x_fwdpk.hip", "p7x_envelope.hip", "p7x_ensemble.hip", "p7x_ssvlong.hip", "p7x_longtarget.hip",
+SOURCES = ["p7x_profile.cpp", "p7x_device.hip", "p7x_devmem.hip", "p7x_devimage.hip", "p7x_msv.hip", "p7x_vitfwd.hip", "p7x_vitpk.hip", "p7x_fwdpk.hip", "p7x_envelope.hip", "p7x_ensemble.hip", "p7x_ssvlong.hip", "p7x_longtarget.hip",
            "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp"]
 
 
@@ -231,6 +231,7 @@ _SIGNATURES = {
     "p7x_search_batch_finish": (C.c_int, [_VP, _VP, _VP, _VP, C.POINTER(_VP)]),
     "p7x_pending_nqueries": (C.c_size_t, [_VP]),
     "p7x_debug_log_of_float": (C.c_int, [C.c_int, _VP, _VP, C.c_size_t]),
+    "p7x_debug_memory_stats": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
     "p7x_debug_choice": (C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
     "p7x_debug_order_spread": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int, _VP]),
     "p7x_debug_parser_rows": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP]),

@@ -219,10 +219,8 @@ int p7x_seqdb_create(int device, int32_t abc_type, const uint8_t *dsq, const int
     auto up = [](size_t v) { return (v + 255) & ~(size_t) 255; };
     const size_t b_dsq = up(db->h_dsq.size()), b_off = up(slot_off.size() * 8), b_len = up(slot_len.size() * 4), b_goff = up(grp_off.size() * 8),
                  b_nblk = up(grp_nblk.size() * 4), b_tiles = up((size_t) std::max<int64_t>(u4, 1) * 16);
-    void *base = nullptr;
-    if ((st = slab_acquire(ctx, b_dsq + b_off + b_len + b_goff + b_nblk + b_tiles, &base, &db->slab_bytes)) != P7X_OK) return st;
-    db->slab = base;
-    unsigned char *q = static_cast<unsigned char *>(base);
+    if ((st = db->slab.reserve(ctx, b_dsq + b_off + b_len + b_goff + b_nblk + b_tiles)) != P7X_OK) return st;
+    unsigned char *q = db->slab.as<unsigned char>();
     db->d_tiles = reinterpret_cast<uint4 *>(q); q += b_tiles;            // 16-byte elements first
     db->d_slot_off = reinterpret_cast<int64_t *>(q); q += b_off;
     db->d_grp_off = reinterpret_cast<int64_t *>(q); q += b_goff;
@@ -230,8 +228,7 @@ int p7x_seqdb_create(int device, int32_t abc_type, const uint8_t *dsq, const int
     db->d_grp_nblk = reinterpret_cast<int32_t *>(q); q += b_nblk;
     db->d_dsq = q;
   }
-  // an upload that fails hands the slab back with the half-built database (it leaked)
-  struct SlabGuard { DeviceCtx *ctx; p7x_seqdb *db; ~SlabGuard() { if (db && db->slab) { slab_release(ctx, db->slab, db->slab_bytes); db->slab = nullptr; } } } guard{ ctx, db.get() };
+  // (an upload that fails hands the slab back with the half-built database)
   P7X_HIP(hipMemcpy(db->d_dsq, db->h_dsq.data(), db->h_dsq.size(), hipMemcpyHostToDevice));
   P7X_HIP(hipMemcpy(db->d_slot_off, slot_off.data(), slot_off.size() * 8, hipMemcpyHostToDevice));
   P7X_HIP(hipMemcpy(db->d_slot_len, slot_len.data(), slot_len.size() * 4, hipMemcpyHostToDevice));
@@ -243,7 +240,6 @@ int p7x_seqdb_create(int device, int32_t abc_type, const uint8_t *dsq, const int
     P7X_HIP(hipGetLastError());
     P7X_HIP(hipStreamSynchronize(ctx->stream));
   }
-  guard.db = nullptr;
   *out = db.release();
   return P7X_OK;
 }
@@ -252,9 +248,7 @@ void p7x_seqdb_destroy(p7x_seqdb *db)
 {
   if (!db) return;
   (void) hipSetDevice(db->device);
-  DeviceCtx *ctx = nullptr;
-  if (db->slab && get_ctx(db->device, &ctx) == P7X_OK) slab_release(ctx, db->slab, db->slab_bytes);      // back to the pool: no device-wide wait
-  delete db;
+  delete db;                          // the slab goes back to the pool: no device-wide wait
 }
 
 int64_t p7x_seqdb_ntargets(const p7x_seqdb *db) { return db ? db->n : -1; }

@@ -1,6 +1,7 @@
 // p7x_device.hpp -- device-side data structures of libp7x (HIP, gfx950 only).
 #pragma once
 #include "p7x_internal.hpp"
+#include "p7x_devmem.hpp"
 #include <hip/hip_runtime.h>
 #include <map>
 #include <memory>
@@ -51,10 +52,11 @@ struct DeviceCtx {
   int msv_last = -1;
   // Device images of query profiles come and go with every query (a scan walks through thousands of models):
   // hipMalloc / hipFree per image would serialise the host against the whole device, so freed slabs are kept here,
-  // by size class, and handed out again.
+  // by size class, and handed out again (p7x_devmem.hip; every owner is a DeviceBuf).
   std::mutex slab_mu;
   std::multimap<size_t, void *> slab_free;
   size_t slab_free_bytes = 0;
+  size_t slab_obtained_bytes = 0;       // from the runtime through the pool and not yet freed: parked or in use
   // The streams of the cascades.  The runtime deals streams onto its hardware queues (GPU_MAX_HW_QUEUES = 8) in the order
   // they are created, and streams that share a queue run one after the other.  A cascade workspace used to create its
   // main stream and seven class streams when it was first needed -- eight streams, so the main streams of the two
@@ -69,17 +71,9 @@ struct DeviceCtx {
   std::vector<hipStream_t> ws_spacers;
   int ws_set_users[kWsSets]{};          // cascades running on every set right now (guarded by mu): a lease takes the least used one
 };
-int slab_acquire(DeviceCtx *ctx, size_t bytes, void **out, size_t *got);
-void slab_release(DeviceCtx *ctx, void *p, size_t bytes);
-// pinned host blocks from a process-wide pool that is never torn down (p7x_devimage.hip)
-int pinned_acquire(size_t bytes, void **out, size_t *got);
-void pinned_release(void *p, size_t bytes);
 int get_ctx(int device, DeviceCtx **out);
 // a stream for the kernels of a search's host stage (envelopes: low priority; ensembles: high)
 int create_tail_stream(DeviceCtx *ctx, bool high_priority, hipStream_t *out);
-
-// A slab of the context's pool that goes back to it when the last owner lets go.
-struct SlabRef { DeviceCtx *ctx = nullptr; void *p = nullptr; size_t bytes = 0; ~SlabRef(); };
 
 // Device image of one query profile.
 struct DevProfile {
@@ -108,8 +102,8 @@ struct DevProfile {
   // bias filter: emission odds [kTabRows][2]
   float *bias_eo = nullptr;
   // all of the tables above live in one device allocation taken from (and returned to) the context's slab pool, shared
-  // by the images that were built in one call (get_dev_profiles)
-  std::shared_ptr<SlabRef> shared;
+  // by the images that were built in one call (get_dev_profiles): it goes back with the last of them
+  std::shared_ptr<DeviceBuf> shared;
 };
 
 // Device image of om for ctx's device, built and uploaded on first use (p7x_devimage.hip); owned by the oprofile.
@@ -158,5 +152,5 @@ struct p7x_seqdb {
   int64_t *d_grp_off = nullptr;    // [ngroups] first uint4 of the group
   int32_t *d_grp_nblk = nullptr;   // [ngroups] number of 16-residue blocks
   int64_t tile_u4 = 0;
-  void *slab = nullptr; size_t slab_bytes = 0;      // the six device arrays are cut from one slab of the context's pool
+  p7x::DeviceBuf slab;             // the six device arrays are cut from one slab of the context's pool
 };

@@ -1,10 +1,9 @@
-// p7x_devimage.hip -- the device image of a query profile, and the pools it is cut from.
+// p7x_devimage.hip -- the device image of a query profile.
 //
 // A query's tables (MSV parity tables, wave-per-target MSV emissions, Viterbi / packed Viterbi / Forward transitions
-// and emissions, bias-filter odds) are laid out back to back in one device slab and uploaded with one copy.  Slabs,
-// staging buffers and pinned blocks come from process-wide pools that are never handed back to the runtime: a scan
-// walks through thousands of short-lived profiles, and hipMalloc / hipFree / hipHostFree per profile (or from a
-// thread that is winding down) would serialise the host against the whole device.
+// and emissions, bias-filter odds) are laid out back to back in one device slab and uploaded with one copy.  The slab
+// and the pinned staging buffer come from the pools of p7x_devmem.hpp: a scan walks through thousands of short-lived
+// profiles.
 #include "p7x_device.hpp"
 #include "p7x_kernels.hpp"
 #include "p7x_host.hpp"
@@ -20,110 +19,16 @@ static void chunk_transpose_fill(int M, int C, std::vector<int> &pos_of_node)
   for (int k = 1; k <= M; ++k) { const int z = (k - 1) / C, c = (k - 1) % C; pos_of_node[k] = c * 64 + z; }
 }
 
-// Pinned host blocks are recycled through a process-wide pool and never handed back to the runtime: hipHostFree from a
-// thread that is winding down (thread_local workspaces) while other threads drive the device is not something the
-// runtime tolerates reliably, and the blocks are small.
-struct PinnedPool { std::mutex mu; std::multimap<size_t, void *> free; };
-static PinnedPool &pinned_pool() { static PinnedPool *p = new PinnedPool(); return *p; }      // never destroyed
-int pinned_acquire(size_t bytes, void **out, size_t *got)
-{
-  size_t want = 256;
-  while (want < bytes) want *= 2;
-  {
-    PinnedPool &pp = pinned_pool();
-    std::lock_guard<std::mutex> lk(pp.mu);
-    auto it = pp.free.find(want);
-    if (it != pp.free.end()) { *out = it->second; *got = want; pp.free.erase(it); return P7X_OK; }
-  }
-  P7X_HIP(hipHostMalloc(out, want, hipHostMallocDefault));
-  *got = want;
-  return P7X_OK;
-}
-void pinned_release(void *p, size_t bytes)
-{
-  if (!p) return;
-  PinnedPool &pp = pinned_pool();
-  std::lock_guard<std::mutex> lk(pp.mu);
-  pp.free.emplace(bytes, p);
-}
-
-int slab_acquire(DeviceCtx *ctx, size_t bytes, void **out, size_t *got)
-{
-  const size_t want = ((bytes + 65535) / 65536) * 65536;
-  {
-    std::lock_guard<std::mutex> lk(ctx->slab_mu);
-    auto it = ctx->slab_free.lower_bound(want);
-    if (it != ctx->slab_free.end() && it->first <= want * 2) {
-      *out = it->second; *got = it->first; ctx->slab_free_bytes -= it->first; ctx->slab_free.erase(it);
-      return P7X_OK;
-    }
-  }
-  if (hipMalloc(out, want) != hipSuccess) {
-    // the device is full while slabs sit parked: hand the parked ones back and try once more (a pool sized for
-    // 288 GiB must not run a smaller device -- or one shared with other processes -- out of memory)
-    (void) hipGetLastError();
-    std::vector<void *> parked;
-    {
-      std::lock_guard<std::mutex> lk(ctx->slab_mu);
-      for (auto &kv : ctx->slab_free) parked.push_back(kv.second);
-      ctx->slab_free.clear(); ctx->slab_free_bytes = 0;
-    }
-    for (void *q : parked) (void) hipFree(q);
-    P7X_HIP(hipMalloc(out, want));
-  }
-  *got = want;
-  return P7X_OK;
-}
-
-void slab_release(DeviceCtx *ctx, void *p, size_t bytes)
-{
-  if (!p) return;
-  std::lock_guard<std::mutex> lk(ctx->slab_mu);
-  // keep at most 32 GiB parked (of 288), and never more than an eighth of the device's memory
-  size_t cap = (size_t) 32 << 30, free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b / 8 < cap) cap = total_b / 8;
-  if (ctx->slab_free_bytes + bytes > cap) { (void) hipFree(p); return; }
-  ctx->slab_free.emplace(bytes, p); ctx->slab_free_bytes += bytes;
-}
-
-SlabRef::~SlabRef() { if (ctx && p) slab_release(ctx, p, bytes); }
-
 void free_dev_profile(DevProfile *d)
 {
-  delete d;          // the slab goes back to the pool with the last image cut from it (SlabRef)
+  delete d;          // the slab goes back to the pool with the last image cut from it
 }
 
 struct DevCache { std::mutex mu; std::vector<DevProfile *> per_device; };
 
 // Host-side staging of a device image: the tables are laid out back to back (256-byte aligned) in one pinned buffer
 // and go up with one copy on a stream of the building thread.
-struct ImageStage {
-  char *pinned = nullptr; size_t cap = 0; hipStream_t stream = nullptr; int device = -1;
-  ~ImageStage() { pinned_release(pinned, cap); if (stream) (void) hipStreamDestroy(stream); }
-  int reserve(size_t bytes)
-  {
-    if (bytes <= cap) return P7X_OK;
-    pinned_release(pinned, cap);
-    pinned = nullptr; cap = 0;
-    void *p = nullptr; size_t got = 0;
-    const int st = pinned_acquire(std::max<size_t>(bytes, (size_t) 1 << 20), &p, &got);
-    if (st != P7X_OK) return st;
-    pinned = static_cast<char *>(p); cap = got;
-    return P7X_OK;
-  }
-};
-struct StagePool { std::mutex mu; std::vector<ImageStage *> idle; };
-static StagePool &stage_pool() { static StagePool *p = new StagePool(); return *p; }      // never destroyed
-struct StageLease {
-  ImageStage *st = nullptr;
-  StageLease()
-  {
-    StagePool &sp = stage_pool();
-    { std::lock_guard<std::mutex> lk(sp.mu); if (!sp.idle.empty()) { st = sp.idle.back(); sp.idle.pop_back(); } }
-    if (!st) st = new ImageStage();
-  }
-  ~StageLease() { std::lock_guard<std::mutex> lk(stage_pool().mu); stage_pool().idle.push_back(st); }
-};
+struct ImageStage { int device = -1; PinnedBuf pinned; hipStream_t stream = nullptr; };      // leased, never destroyed
 
 // Host side of one image: the tables back to back (256-byte aligned) and, for every table, the DevProfile field that
 // will point at it.
@@ -265,26 +170,22 @@ int get_dev_profiles(const p7x_oprofile *const *oms, int n, DeviceCtx *ctx, DevP
   std::vector<size_t> off((size_t) nm + 1, 0);
   for (int z = 0; z < nm; ++z) off[(size_t) z + 1] = off[(size_t) z] + imgs[(size_t) z].bytes.size();
   const size_t total = off[(size_t) nm];
-  StageLease stage_lease;
-  ImageStage &stg = *stage_lease.st;
+  auto stage_lease = LeasePool<ImageStage>::instance().lease(ctx->device, [](const ImageStage &, const ImageStage *b) { return !b; });
+  ImageStage &stg = *stage_lease;
   int st = P7X_OK;
-  if ((st = stg.reserve(total)) != P7X_OK) return st;
-  if (stg.stream == nullptr || stg.device != ctx->device) {
-    if (stg.stream) (void) hipStreamDestroy(stg.stream);
-    P7X_HIP(hipStreamCreateWithFlags(&stg.stream, hipStreamNonBlocking));
-    stg.device = ctx->device;
-  }
-  auto shared = std::make_shared<SlabRef>();
-  shared->ctx = ctx;
-  if ((st = slab_acquire(ctx, total, &shared->p, &shared->bytes)) != P7X_OK) return st;
+  if ((st = stg.pinned.reserve(total, (size_t) 1 << 20)) != P7X_OK) return st;
+  if (stg.stream == nullptr) P7X_HIP(hipStreamCreateWithFlags(&stg.stream, hipStreamNonBlocking));
+  auto shared = std::make_shared<DeviceBuf>();
+  if ((st = shared->reserve(ctx, total)) != P7X_OK) return st;
+  char *const pinned = stg.pinned.as<char>(), *const slab = shared->as<char>();
   auto place = [&](int z) {
     const HostImage &img = imgs[(size_t) z];
-    std::memcpy(stg.pinned + off[(size_t) z], img.bytes.data(), img.bytes.size());
-    for (const auto &f : img.fix) *f.first = static_cast<char *>(shared->p) + off[(size_t) z] + f.second;
+    std::memcpy(pinned + off[(size_t) z], img.bytes.data(), img.bytes.size());
+    for (const auto &f : img.fix) *f.first = slab + off[(size_t) z] + f.second;
     fresh[(size_t) z]->shared = shared;
   };
   if (nm >= 4) host_parallel_for(nm, nthreads, place); else for (int z = 0; z < nm; ++z) place(z);
-  if (hipMemcpyAsync(shared->p, stg.pinned, total, hipMemcpyHostToDevice, stg.stream) != hipSuccess ||
+  if (hipMemcpyAsync(slab, pinned, total, hipMemcpyHostToDevice, stg.stream) != hipSuccess ||
       hipStreamSynchronize(stg.stream) != hipSuccess) {
     set_error("uploading the profiles' device images failed");
     return P7X_EDEVICE;

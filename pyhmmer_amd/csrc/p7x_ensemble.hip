@@ -583,42 +583,11 @@ static int ens_walk_launch(const EnsArgs &a, hipStream_t st)
 namespace {
 struct EnsBuffers {
   int device = -1;
-  unsigned char *work = nullptr; size_t work_bytes = 0;       // cells | md | rows
-  unsigned char *d_in = nullptr; size_t d_in_cap = 0;
-  unsigned char *h_in = nullptr; size_t h_in_cap = 0;
-  unsigned char *d_out = nullptr; size_t d_out_cap = 0;
-  unsigned char *h_out = nullptr; size_t h_out_cap = 0;
+  DeviceBuf work;                     // cells | md | rows
+  DeviceBuf d_in; PinnedBuf h_in;
+  DeviceBuf d_out; PinnedBuf h_out;
   hipStream_t stream = nullptr;
 };
-struct EnsPool { std::mutex mu; std::vector<EnsBuffers *> all; std::vector<char> busy; };
-EnsPool &ens_pool() { static EnsPool *p = new EnsPool(); return *p; }
-void release_ens_buffers(EnsBuffers *eb)
-{
-  if (!eb) return;
-  EnsPool &ep = ens_pool();
-  std::lock_guard<std::mutex> lk(ep.mu);
-  for (size_t i = 0; i < ep.all.size(); ++i) if (ep.all[i] == eb) ep.busy[i] = 0;
-}
-int grow_device(DeviceCtx *ctx, unsigned char *&p, size_t &cap, size_t need, size_t floor_bytes)
-{
-  if (need <= cap) return P7X_OK;
-  slab_release(ctx, p, cap); p = nullptr; cap = 0;
-  void *dp = nullptr; size_t got = 0;
-  const int st = slab_acquire(ctx, std::max(need + need / 4, floor_bytes), &dp, &got);
-  if (st != P7X_OK) return st;
-  p = static_cast<unsigned char *>(dp); cap = got;
-  return P7X_OK;
-}
-int grow_pinned(unsigned char *&p, size_t &cap, size_t need, size_t floor_bytes)
-{
-  if (need <= cap) return P7X_OK;
-  pinned_release(p, cap); p = nullptr; cap = 0;
-  void *hp = nullptr; size_t got = 0;
-  const int st = pinned_acquire(std::max(need + need / 4, floor_bytes), &hp, &got);
-  if (st != P7X_OK) return st;
-  p = static_cast<unsigned char *>(hp); cap = got;
-  return P7X_OK;
-}
 size_t align256(size_t v) { return (v + 255) & ~(size_t) 255; }
 } // namespace
 
@@ -629,7 +598,7 @@ public:
     const double g = (double) guard * 4294967296.0;
     guard_ = g <= 0.0 ? 0u : (g >= 1.0e9 ? 1000000000u : (uint32_t) g);
   }
-  ~DeviceEnsembleRunner() override { if (lease_) { if (lease_->stream) (void) hipStreamSynchronize(lease_->stream); release_ens_buffers(lease_); } }
+  ~DeviceEnsembleRunner() override { sync_and_return(lease_); }
 
   // Any region may be sampled by the host workers instead (EnsembleResult::status != 0): a device-side failure here --
   // the workspace cannot grow because other host stages hold the memory, a launch is refused -- sends every region of
@@ -656,7 +625,7 @@ public:
     if (nlaunched_ == 0) return P7X_OK;
     P7X_HIP(hipSetDevice(db_->device));
     P7X_HIP(hipStreamSynchronize(lease_->stream));
-    const unsigned char *h = lease_->h_out;
+    const unsigned char *h = lease_->h_out.as<unsigned char>();
     const int32_t *ndom = reinterpret_cast<const int32_t *>(h + o_ndom_), *status = reinterpret_cast<const int32_t *>(h + o_status_);
     const int32_t *dom = reinterpret_cast<const int32_t *>(h + o_dom_);
     const float *n2 = reinterpret_cast<const float *>(h + o_n2_);
@@ -683,14 +652,9 @@ private:
     launched_.assign((size_t) nreg, 0);
     if (nreg == 0) return P7X_OK;
     P7X_HIP(hipSetDevice(db_->device));
-    EnsBuffers *eb = nullptr;
-    {
-      EnsPool &ep = ens_pool();
-      std::lock_guard<std::mutex> lk(ep.mu);
-      for (size_t i = 0; i < ep.all.size() && !eb; ++i) if (!ep.busy[i] && ep.all[i]->device == db_->device) { ep.busy[i] = 1; eb = ep.all[i]; }
-      if (!eb) { eb = new EnsBuffers(); eb->device = db_->device; ep.all.push_back(eb); ep.busy.push_back(1); }
-    }
-    lease_ = eb;
+    auto &pool = LeasePool<EnsBuffers>::instance();
+    lease_ = pool.lease(db_->device, [](const EnsBuffers &, const EnsBuffers *b) { return !b; });      // the first idle set
+    EnsBuffers *eb = lease_.get();
     if (!eb->stream) {
       // a few wavefronts, each a long serial chain, and the host stage waits for them: ahead of the filter kernels' queues
       const int cst = create_tail_stream(ctx_, true, &eb->stream); if (cst != P7X_OK) return cst;
@@ -702,16 +666,13 @@ private:
     size_t free_b = 0, total_b = 0;
     size_t budget = (size_t) 16 << 30;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      if (free_b / 4 < budget) budget = std::max(free_b / 4, eb->work_bytes);
+      const size_t mine = eb->work.capacity();
+      if (free_b / 4 < budget) budget = std::max(free_b / 4, mine);
       size_t pooled = 0;
-      {
-        EnsPool &ep = ens_pool();
-        std::lock_guard<std::mutex> lk(ep.mu);
-        for (const EnsBuffers *o : ep.all) if (o != eb && o->device == db_->device) pooled += o->work_bytes;
-      }
+      pool.for_each(db_->device, [&](const EnsBuffers &o) { if (&o != eb) pooled += o.work.capacity(); });
       const size_t cap = total_b / 4;
       const size_t room = pooled < cap ? cap - pooled : 0;
-      if (budget > std::max(room, eb->work_bytes)) budget = std::max(room, eb->work_bytes);
+      if (budget > std::max(room, mine)) budget = std::max(room, mine);
     }
     std::vector<DevProfile *> dps(nj, nullptr);
     std::vector<EnsRegion> regs;
@@ -761,21 +722,24 @@ private:
     // workspace
     const size_t o_cells = 0, o_md = align256(o_cells + (size_t) ncells * 32), o_rows = align256(o_md + (size_t) ncells * 8);
     const size_t work_bytes = align256(o_rows + (size_t) nrows * 32);
-    int st = grow_device(ctx_, eb->work, eb->work_bytes, work_bytes, (size_t) 256 << 20);
+    auto grow = [](size_t need, size_t floor_bytes) { return std::max(need + need / 4, floor_bytes); };
+    int st = eb->work.reserve(ctx_, work_bytes, grow(work_bytes, (size_t) 256 << 20));
     if (st != P7X_OK) return st;
     // inputs: jobs | regions | class lists | rft tables | degeneracy matrices (one per job that has regions)
     const size_t o_jobs = 0, o_regs = align256(o_jobs + nj * sizeof(EnsJob)), o_lists = align256(o_regs + (size_t) nl * sizeof(EnsRegion));
     const size_t o_rft = align256(o_lists + (size_t) nl * 4), o_degen = align256(o_rft + rft_floats * 4);
     const size_t in_bytes = align256(o_degen + nj * 1024);
-    if ((st = grow_pinned(eb->h_in, eb->h_in_cap, in_bytes, (size_t) 1 << 20)) != P7X_OK) return st;
-    if ((st = grow_device(ctx_, eb->d_in, eb->d_in_cap, in_bytes, (size_t) 1 << 20)) != P7X_OK) return st;
+    if ((st = eb->h_in.reserve(in_bytes, grow(in_bytes, (size_t) 1 << 20))) != P7X_OK) return st;
+    if ((st = eb->d_in.reserve(ctx_, in_bytes, grow(in_bytes, (size_t) 1 << 20))) != P7X_OK) return st;
     // outputs: ndom | status | dom records | null2 accumulators
     o_ndom_ = 0; o_status_ = align256((size_t) nl * 4); o_dom_ = align256(o_status_ + (size_t) nl * 4);
     o_n2_ = align256(o_dom_ + (size_t) ndomrec * 5 * 4);
     const size_t out_bytes = align256(o_n2_ + (size_t) nrows * 4);
-    if ((st = grow_device(ctx_, eb->d_out, eb->d_out_cap, out_bytes, (size_t) 4 << 20)) != P7X_OK) return st;
-    if ((st = grow_pinned(eb->h_out, eb->h_out_cap, out_bytes, (size_t) 4 << 20)) != P7X_OK) return st;
-    float *h_rft = reinterpret_cast<float *>(eb->h_in + o_rft);
+    if ((st = eb->d_out.reserve(ctx_, out_bytes, grow(out_bytes, (size_t) 4 << 20))) != P7X_OK) return st;
+    if ((st = eb->h_out.reserve(out_bytes, grow(out_bytes, (size_t) 4 << 20))) != P7X_OK) return st;
+    unsigned char *const h_in = eb->h_in.as<unsigned char>(), *const d_in = eb->d_in.as<unsigned char>();
+    unsigned char *const d_out = eb->d_out.as<unsigned char>(), *const work = eb->work.as<unsigned char>();
+    float *h_rft = reinterpret_cast<float *>(h_in + o_rft);
     for (size_t j = 0; j < nj; ++j) {
       EnsJob &ej = ejobs[j];
       if (ej.nreg <= 0) continue;
@@ -783,31 +747,31 @@ private:
       float *t = h_rft + rft_at[j];
       std::memset(t, 0, (size_t) (p.M + 1) * 32 * 4);
       for (int x = 0; x < p.K; ++x) { const float *r = p.rf_.data() + (size_t) x * (p.M + 1); for (int k = 1; k <= p.M; ++k) t[(size_t) k * 32 + x] = r[k]; }
-      unsigned char *dg = eb->h_in + o_degen + j * 1024;
+      unsigned char *dg = h_in + o_degen + j * 1024;
       std::memset(dg, 0, 1024);
       const Alphabet &abc = Alphabet::get(p.abc_type);
       for (int x = 0; x < p.Kp; ++x) for (int y = 0; y < p.K; ++y) dg[x * 32 + y] = abc.degen[x][y];
-      ej.rft = reinterpret_cast<const float *>(eb->d_in + o_rft) + rft_at[j];
-      ej.degen = eb->d_in + o_degen + j * 1024;
+      ej.rft = reinterpret_cast<const float *>(d_in + o_rft) + rft_at[j];
+      ej.degen = d_in + o_degen + j * 1024;
     }
-    std::memcpy(eb->h_in + o_jobs, ejobs.data(), nj * sizeof(EnsJob));
-    std::memcpy(eb->h_in + o_regs, regs.data(), (size_t) nl * sizeof(EnsRegion));
-    int32_t *h_lists = reinterpret_cast<int32_t *>(eb->h_in + o_lists);
+    std::memcpy(h_in + o_jobs, ejobs.data(), nj * sizeof(EnsJob));
+    std::memcpy(h_in + o_regs, regs.data(), (size_t) nl * sizeof(EnsRegion));
+    int32_t *h_lists = reinterpret_cast<int32_t *>(h_in + o_lists);
     std::vector<std::pair<int, std::pair<int, int>>> runs;       // class, (first, count)
     { int at = 0; for (auto &kv : by_class) { std::copy(kv.second.begin(), kv.second.end(), h_lists + at); runs.push_back({ kv.first, { at, (int) kv.second.size() } }); at += (int) kv.second.size(); } }
     hipStream_t s = eb->stream;
-    P7X_HIP(hipMemcpyAsync(eb->d_in, eb->h_in, in_bytes, hipMemcpyHostToDevice, s));
+    P7X_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
     EnsArgs a{};
-    a.jobs = reinterpret_cast<const EnsJob *>(eb->d_in + o_jobs);
-    a.regions = reinterpret_cast<const EnsRegion *>(eb->d_in + o_regs);
+    a.jobs = reinterpret_cast<const EnsJob *>(d_in + o_jobs);
+    a.regions = reinterpret_cast<const EnsRegion *>(d_in + o_regs);
     a.nregions = nl; a.dsq = db_->d_dsq;
-    a.cells = reinterpret_cast<ChoiceCell *>(eb->work + o_cells);
-    a.md = reinterpret_cast<float2 *>(eb->work + o_md);
-    a.rows = reinterpret_cast<ChoiceRow *>(eb->work + o_rows);
+    a.cells = reinterpret_cast<ChoiceCell *>(work + o_cells);
+    a.md = reinterpret_cast<float2 *>(work + o_md);
+    a.rows = reinterpret_cast<ChoiceRow *>(work + o_rows);
     a.seed_x = seed_state; a.nsamples = nsamples; a.guard = guard_;
-    a.n2acc = reinterpret_cast<float *>(eb->d_out + o_n2_);
-    a.dom = reinterpret_cast<int32_t *>(eb->d_out + o_dom_);
-    a.out_ndom = reinterpret_cast<int32_t *>(eb->d_out + o_ndom_); a.out_status = reinterpret_cast<int32_t *>(eb->d_out + o_status_);
+    a.n2acc = reinterpret_cast<float *>(d_out + o_n2_);
+    a.dom = reinterpret_cast<int32_t *>(d_out + o_dom_);
+    a.out_ndom = reinterpret_cast<int32_t *>(d_out + o_ndom_); a.out_status = reinterpret_cast<int32_t *>(d_out + o_status_);
     {   // LDS of the walk kernel: node counts and the null2 scratch always; then, as far as 128 KiB go, the largest region's row
         // records, residues and accumulators, the longest model's odds table and eight of its Forward rows (each region
         // takes what fits, in that order), and the record caches of the core walk in the rest (48 KiB when there is room,
@@ -823,11 +787,11 @@ private:
       if (debug_opt(OPT_ENS_LDS_KB) > 0) most = (size_t) debug_opt(OPT_ENS_LDS_KB) * 1024;
       a.lds_bytes = (int) std::max(least, std::min(want, most));
     }
-    const int32_t *d_lists = reinterpret_cast<const int32_t *>(eb->d_in + o_lists);
+    const int32_t *d_lists = reinterpret_cast<const int32_t *>(d_in + o_lists);
     for (const auto &run : runs)
       if ((st = ens_forward_launch(run.first, a, d_lists + run.second.first, run.second.second, s)) != P7X_OK) return st;
     if ((st = ens_walk_launch(a, s)) != P7X_OK) return st;
-    P7X_HIP(hipMemcpyAsync(eb->h_out, eb->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    P7X_HIP(hipMemcpyAsync(eb->h_out.as<void>(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
     regs_ = std::move(regs);
     return P7X_OK;
   }
@@ -839,7 +803,7 @@ private:
   std::vector<char> launched_;
   std::vector<EnsRegion> regs_;
   int64_t nreg_ = 0; int nlaunched_ = 0;
-  EnsBuffers *lease_ = nullptr;
+  Lease<EnsBuffers> lease_;
   size_t o_ndom_ = 0, o_status_ = 0, o_dom_ = 0, o_n2_ = 0;
 };
 

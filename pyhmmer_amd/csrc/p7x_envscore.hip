@@ -15,38 +15,16 @@
 namespace p7x {
 
 // ---------------------------------------------------------------------------- envelope rescoring on the device
-// Device and pinned-host buffers are grow-only, like the cascade workspace; a buffer that has to grow goes back to the
-// context's slab pool and the larger one comes from there (hipFree would wait for every stream of the device, i.e. for
-// the cascades of the other searches in flight).
+// Device and pinned-host buffers are grow-only, like the cascade workspace, and leased from a process-wide pool like it
+// (p7x_devmem.hpp).
 struct EnvBuffers {
   int device = -1;
-  float *work = nullptr; size_t work_floats = 0, work_bytes = 0;
-  unsigned char *d_in = nullptr; size_t d_in_cap = 0;        // env_sq | tr_off | env_len | env_L | EnvArgs records
-  unsigned char *h_in = nullptr; size_t h_in_cap = 0;        // pinned mirror of d_in
-  unsigned char *d_out = nullptr; size_t d_out_cap = 0;      // out_sc | out_null2 | out_status | tr_n | tr_a | tr_i | tr_pp
-  unsigned char *h_out = nullptr; size_t h_out_cap = 0;      // pinned mirror of d_out
-  float *lt_dev = nullptr; size_t lt_bytes = 0;              // long-target envelopes: their emission tables
-  hipStream_t stream = nullptr;                               // per host thread: concurrent host stages do not wait on each other
-  ~EnvBuffers() {
-    if (device < 0) return;
-    (void) hipSetDevice(device);
-    if (stream) (void) hipStreamDestroy(stream);
-    DeviceCtx *ctx = nullptr;
-    if (get_ctx(device, &ctx) == P7X_OK) { slab_release(ctx, work, work_bytes); slab_release(ctx, d_in, d_in_cap); slab_release(ctx, d_out, d_out_cap); slab_release(ctx, lt_dev, lt_bytes); }
-    pinned_release(h_out, h_out_cap);
-    pinned_release(h_in, h_in_cap);
-  }
+  DeviceBuf work;                     // floats
+  DeviceBuf d_in; PinnedBuf h_in;     // env_sq | tr_off | env_len | env_L | EnvArgs records, and the pinned mirror
+  DeviceBuf d_out; PinnedBuf h_out;   // out_sc | out_null2 | out_status | tr_n | tr_a | tr_i | tr_pp, and the pinned mirror
+  DeviceBuf lt_dev;                   // long-target envelopes: their emission tables
+  hipStream_t stream = nullptr;       // per host thread: concurrent host stages do not wait on each other
 };
-// leased from a process-wide pool like the cascade workspaces (never destroyed: no device teardown from exiting threads)
-struct EnvPool { std::mutex mu; std::vector<EnvBuffers *> all; std::vector<char> busy; };
-static EnvPool &env_pool() { static EnvPool *p = new EnvPool(); return *p; }
-static void release_env_buffers(EnvBuffers *eb)
-{
-  if (!eb) return;
-  EnvPool &ep = env_pool();
-  std::lock_guard<std::mutex> lk(ep.mu);
-  for (size_t i = 0; i < ep.all.size(); ++i) if (ep.all[i] == eb) ep.busy[i] = 0;
-}
 
 static size_t env_budget_bytes(int option)
 {
@@ -63,7 +41,7 @@ class DeviceEnvelopeScorer final : public EnvelopeScorer {
 public:
   // align: the requests are whole sequences for env_kernel's alignment mode (hmmalign) instead of envelopes
   DeviceEnvelopeScorer(DeviceCtx *ctx, const p7x_seqdb *db, bool align = false) : ctx_(ctx), db_(db), align_(align) {}
-  ~DeviceEnvelopeScorer() override { if (lease_) { if (lease_->stream) (void) hipStreamSynchronize(lease_->stream); release_env_buffers(lease_); } }
+  ~DeviceEnvelopeScorer() override { sync_and_return(lease_); }
 
   int begin(const std::vector<EnvelopeJob> &jobs) override
   {
@@ -83,17 +61,9 @@ public:
     nenv_ = nenv_tot;
     if (nenv_tot == 0) return P7X_OK;
     P7X_HIP(hipSetDevice(db_->device));
-    EnvBuffers *eb = nullptr;
-    {
-      EnvPool &ep = env_pool();
-      std::lock_guard<std::mutex> lk(ep.mu);
-      size_t pick = ep.all.size();       // the idle set with the largest workspace: fewer buffers have to grow
-      for (size_t i = 0; i < ep.all.size(); ++i)
-        if (!ep.busy[i] && ep.all[i]->device == db_->device && (pick == ep.all.size() || ep.all[i]->work_bytes > ep.all[pick]->work_bytes)) pick = i;
-      if (pick < ep.all.size()) { ep.busy[pick] = 1; eb = ep.all[pick]; }
-      if (!eb) { eb = new EnvBuffers(); eb->device = db_->device; ep.all.push_back(eb); ep.busy.push_back(1); }
-    }
-    lease_ = eb;
+    // the idle set with the largest workspace: fewer buffers have to grow
+    lease_ = LeasePool<EnvBuffers>::instance().lease(db_->device, [](const EnvBuffers &a, const EnvBuffers *b) { return !b || a.work.capacity() > b->work.capacity(); });
+    EnvBuffers *eb = lease_.get();
     tick("lease");
     if (!eb->stream) {
       const int cst = create_tail_stream(ctx_, false, &eb->stream); if (cst != P7X_OK) return cst;
@@ -104,30 +74,23 @@ public:
     const size_t o_cursor = (size_t) nenv_tot * (8 + 8 + 4 + 4 + 4);
     const size_t o_args = (o_cursor + nj * 4 + 255) & ~(size_t) 255;
     const size_t in_bytes = o_args + nj * sizeof(EnvArgs);
-    if (in_bytes > eb->h_in_cap) {
-      pinned_release(eb->h_in, eb->h_in_cap); eb->h_in = nullptr; eb->h_in_cap = 0;
-      void *hp = nullptr; size_t got = 0; const int pst = pinned_acquire(std::max<size_t>(in_bytes * 2, (size_t) 1 << 20), &hp, &got); if (pst != P7X_OK) return pst;
-      eb->h_in = static_cast<unsigned char *>(hp); eb->h_in_cap = got;
-    }
-    if (in_bytes > eb->d_in_cap) {
-      slab_release(ctx_, eb->d_in, eb->d_in_cap); eb->d_in = nullptr; eb->d_in_cap = 0;
-      void *dp = nullptr; size_t got = 0; const int sst = slab_acquire(ctx_, std::max<size_t>(in_bytes * 2, (size_t) 1 << 20), &dp, &got); if (sst != P7X_OK) return sst;
-      eb->d_in = static_cast<unsigned char *>(dp); eb->d_in_cap = got;
-    }
+    int st = P7X_OK;
+    const size_t in_grow = std::max<size_t>(in_bytes * 2, (size_t) 1 << 20);
+    if ((st = eb->h_in.reserve(in_bytes, in_grow)) != P7X_OK || (st = eb->d_in.reserve(ctx_, in_bytes, in_grow)) != P7X_OK) return st;
     tick("in_bufs");
-    int64_t *env_sq = reinterpret_cast<int64_t *>(eb->h_in);
+    unsigned char *const h_in = eb->h_in.as<unsigned char>(), *const d_in = eb->d_in.as<unsigned char>();
+    int64_t *env_sq = reinterpret_cast<int64_t *>(h_in);
     int64_t *tr_off = env_sq + nenv_tot;
     int32_t *env_len = reinterpret_cast<int32_t *>(tr_off + nenv_tot);
     int32_t *env_L = env_len + nenv_tot;
     int32_t *env_order = env_L + nenv_tot;
-    int32_t *h_cursor = reinterpret_cast<int32_t *>(eb->h_in + o_cursor);
+    int32_t *h_cursor = reinterpret_cast<int32_t *>(h_in + o_cursor);
     for (size_t j = 0; j < nj; ++j) h_cursor[j] = 0;
-    EnvArgs *h_args = reinterpret_cast<EnvArgs *>(eb->h_in + o_args);
+    EnvArgs *h_args = reinterpret_cast<EnvArgs *>(h_in + o_args);
     int64_t ntr = 0;
     // jobs of one model-length class (nodes per lane C) go into one launch: order them by class
     order_.resize(nj);
     for (size_t j = 0; j < nj; ++j) order_[j] = (int) j;
-    int st = P7X_OK;
     for (size_t j = 0; j < nj; ++j) {
       JobMeta &m = meta_[j];
       if (m.nenv == 0) continue;
@@ -173,17 +136,13 @@ public:
         work_floats += (size_t) m.nblocks * env_waves(m.C) * m.stride;
       }
       // (envelopes: a pooled workspace that is already large enough is used at this occupancy; hmmalign keeps to its budget)
-      if (work_floats * 4 <= budget || (!align_ && work_floats <= eb->work_floats)) break;
+      if (work_floats * 4 <= budget || (!align_ && work_floats * 4 <= eb->work.capacity())) break;
       bool all_one = true;
       for (size_t j = 0; j < nj; ++j) if (meta_[j].nenv && meta_[j].nblocks > 1) all_one = false;
       if (all_one) { set_error("envelope workspace does not fit in device memory"); return P7X_EMEM; }
     }
-    if (work_floats > eb->work_floats) {
-      slab_release(ctx_, eb->work, eb->work_bytes); eb->work = nullptr; eb->work_floats = 0; eb->work_bytes = 0;
-      void *dp = nullptr; size_t got = 0; // 25 % headroom and never less than 1 GiB: a large device allocation stalls this host stage for tens of ms
-      const int sst = slab_acquire(ctx_, std::max<size_t>(work_floats * 4 + work_floats, (size_t) 1 << 30), &dp, &got); if (sst != P7X_OK) return sst;
-      eb->work = static_cast<float *>(dp); eb->work_bytes = got; eb->work_floats = got / 4;
-    }
+    // 25 % headroom and never less than 1 GiB: a large device allocation stalls this host stage for tens of ms
+    if ((st = eb->work.reserve(ctx_, work_floats * 4, std::max<size_t>(work_floats * 4 + work_floats, (size_t) 1 << 30))) != P7X_OK) return st;
     work_bytes_ = work_floats * 4;
     tick("work");
     // outputs: [out_sc 2f][null2 32f][status i][tr_n i][orig f] per envelope, then the three trace arrays
@@ -194,28 +153,19 @@ public:
     // long-target jobs: the envelopes' own emission tables go up next to the requests
     size_t lt_floats = 0;
     for (size_t j = 0; j < nj; ++j) if (jobs[j].lt_tables) lt_floats += (size_t) meta_[j].nenv * jobs[j].lt_stride;
-    if (lt_floats * 4 > eb->lt_bytes) {
-      slab_release(ctx_, eb->lt_dev, eb->lt_bytes); eb->lt_dev = nullptr; eb->lt_bytes = 0;
-      void *dp = nullptr; size_t got = 0; const int sst = slab_acquire(ctx_, lt_floats * 4 + lt_floats, &dp, &got); if (sst != P7X_OK) return sst;
-      eb->lt_dev = static_cast<float *>(dp); eb->lt_bytes = got;
-    }
-    if (out_bytes > eb->d_out_cap) {
-      slab_release(ctx_, eb->d_out, eb->d_out_cap); eb->d_out = nullptr; eb->d_out_cap = 0;
-      pinned_release(eb->h_out, eb->h_out_cap); eb->h_out = nullptr; eb->h_out_cap = 0;
-      size_t cap = std::max<size_t>(out_bytes + out_bytes / 2, (size_t) 16 << 20);     // growing is a stall (pinned allocation): start generous
-      { void *dp = nullptr; size_t got = 0; const int sst = slab_acquire(ctx_, cap, &dp, &got); if (sst != P7X_OK) return sst;
-        eb->d_out = static_cast<unsigned char *>(dp); eb->d_out_cap = cap = got; }
-      { void *hp = nullptr; size_t got = 0; const int pst = pinned_acquire(cap, &hp, &got); if (pst != P7X_OK) return pst;
-        eb->h_out = static_cast<decltype(eb->h_out)>(hp); eb->h_out_cap = got; }
-    }
+    if ((st = eb->lt_dev.reserve(ctx_, lt_floats * 4, lt_floats * 4 + lt_floats)) != P7X_OK) return st;
+    const size_t out_grow = std::max<size_t>(out_bytes + out_bytes / 2, (size_t) 16 << 20);     // growing is a stall (pinned allocation): start generous
+    if ((st = eb->d_out.reserve(ctx_, out_bytes, out_grow)) != P7X_OK || (st = eb->h_out.reserve(out_bytes, out_grow)) != P7X_OK) return st;
     tick("out_bufs");
+    unsigned char *const d_out = eb->d_out.as<unsigned char>();
+    float *const work = eb->work.as<float>(), *const lt_dev = eb->lt_dev.as<float>();
     hipStream_t s = eb->stream;
-    const int64_t *d_env_sq = reinterpret_cast<const int64_t *>(eb->d_in);
+    const int64_t *d_env_sq = reinterpret_cast<const int64_t *>(d_in);
     const int64_t *d_tr_off = d_env_sq + nenv_tot;
     const int32_t *d_env_len = reinterpret_cast<const int32_t *>(d_tr_off + nenv_tot);
     const int32_t *d_env_L = d_env_len + nenv_tot;
     const int32_t *d_env_order = d_env_L + nenv_tot;
-    int *d_cursor = reinterpret_cast<int *>(eb->d_in + o_cursor);
+    int *d_cursor = reinterpret_cast<int *>(d_in + o_cursor);
     // argument records in launch order (class by class)
     size_t slab_floats = 0, lt_at = 0;
     std::vector<std::pair<int, int>> runs;        // first record, count
@@ -233,45 +183,45 @@ public:
       a.env_sq = d_env_sq + m.first; a.tr_off = d_tr_off + m.first; a.env_len = d_env_len + m.first; a.env_L = d_env_L + m.first;
       a.order = d_env_order + m.first; a.cursor = d_cursor + j;
       // slab_base counts slabs of THIS job's stride from the start of its own region of the workspace
-      a.work = eb->work + slab_floats; a.work_stride = (int64_t) m.stride; a.Lmax = class_Lmax[m.C];
+      a.work = work + slab_floats; a.work_stride = (int64_t) m.stride; a.Lmax = class_Lmax[m.C];
       a.nblocks = m.nblocks; a.slab_base = 0;
       slab_floats += (size_t) m.nblocks * env_waves(m.C) * m.stride;
-      a.out_sc = reinterpret_cast<float *>(eb->d_out + o_sc) + 2 * m.first;
-      a.out_null2 = reinterpret_cast<float *>(eb->d_out + o_n2) + 32 * m.first;
-      a.out_status = reinterpret_cast<int32_t *>(eb->d_out + o_st) + m.first;
-      a.out_orig = reinterpret_cast<float *>(eb->d_out + o_orig) + m.first;
+      a.out_sc = reinterpret_cast<float *>(d_out + o_sc) + 2 * m.first;
+      a.out_null2 = reinterpret_cast<float *>(d_out + o_n2) + 32 * m.first;
+      a.out_status = reinterpret_cast<int32_t *>(d_out + o_st) + m.first;
+      a.out_orig = reinterpret_cast<float *>(d_out + o_orig) + m.first;
       if (jobs[(size_t) j].lt_tables) {
         const size_t cnt = (size_t) m.nenv * jobs[(size_t) j].lt_stride;
-        P7X_HIP(hipMemcpyAsync(eb->lt_dev + lt_at, jobs[(size_t) j].lt_tables, cnt * 4, hipMemcpyHostToDevice, s));
-        a.env_emis = eb->lt_dev + lt_at; a.env_emis_stride = (long long) jobs[(size_t) j].lt_stride;
+        P7X_HIP(hipMemcpyAsync(lt_dev + lt_at, jobs[(size_t) j].lt_tables, cnt * 4, hipMemcpyHostToDevice, s));
+        a.env_emis = lt_dev + lt_at; a.env_emis_stride = (long long) jobs[(size_t) j].lt_stride;
         lt_at += cnt;
       }
       a.oa_guard = oa_guard_;
-      a.tr_n = reinterpret_cast<int32_t *>(eb->d_out + o_n) + m.first;
-      a.tr_a = reinterpret_cast<uint32_t *>(eb->d_out + o_ta);
-      a.tr_i = reinterpret_cast<int32_t *>(eb->d_out + o_ti);
-      a.tr_pp = reinterpret_cast<float *>(eb->d_out + o_tp);
+      a.tr_n = reinterpret_cast<int32_t *>(d_out + o_n) + m.first;
+      a.tr_a = reinterpret_cast<uint32_t *>(d_out + o_ta);
+      a.tr_i = reinterpret_cast<int32_t *>(d_out + o_ti);
+      a.tr_pp = reinterpret_cast<float *>(d_out + o_tp);
       if (!runs.empty() && h_args[runs.back().first].C == a.C && h_args[runs.back().first].nrows == a.nrows &&
           (h_args[runs.back().first].env_emis != nullptr) == (a.env_emis != nullptr)) runs.back().second++;
       else runs.emplace_back(nrec, 1);
       h_args[nrec++] = a;
     }
     tick("args");
-    P7X_HIP(hipMemcpyAsync(eb->d_in, eb->h_in, in_bytes, hipMemcpyHostToDevice, s));
+    P7X_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
     tick("h2d");
     for (const auto &run : runs) {
       ArgRun<EnvArgs> ar;
-      ar.host = h_args + run.first; ar.dev = eb->d_in + o_args + (size_t) run.first * sizeof(EnvArgs);
+      ar.host = h_args + run.first; ar.dev = d_in + o_args + (size_t) run.first * sizeof(EnvArgs);
       ar.stride = (uint32_t) sizeof(EnvArgs); ar.n = run.second;
       const EnvMode mode = align_ ? EnvMode::Align : ar.at(0).env_emis ? EnvMode::LongTarget : EnvMode::Envelope;
       if ((st = env_launch(mode, ar, s)) != P7X_OK) return st;
     }
     tick("launches");
-    P7X_HIP(hipMemcpyAsync(eb->h_out, eb->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    P7X_HIP(hipMemcpyAsync(eb->h_out.as<void>(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
     tick("d2h");
     if (debug) std::fprintf(stderr, "[env begin] jobs %zu envelopes %lld runs %zu work %.1f MB out %.1f MB:%s ms\n", nj, (long long) nenv_tot, runs.size(),
                             work_floats * 4 / 1e6, out_bytes / 1e6, dbg.c_str());
-    eb_ = eb; o_sc_ = o_sc; o_n2_ = o_n2; o_st_ = o_st; o_n_ = o_n; o_orig_ = o_orig; o_ta_ = o_ta; o_ti_ = o_ti; o_tp_ = o_tp;
+    o_sc_ = o_sc; o_n2_ = o_n2; o_st_ = o_st; o_n_ = o_n; o_orig_ = o_orig; o_ta_ = o_ta; o_ti_ = o_ti; o_tp_ = o_tp;
     tr_off_.assign(tr_off, tr_off + nenv_tot);
     return P7X_OK;
   }
@@ -281,13 +231,13 @@ public:
     res.assign(jobs_.size(), {});
     if (nenv_ == 0) return P7X_OK;
     P7X_HIP(hipSetDevice(db_->device));
-    EnvBuffers *eb = eb_;
-    P7X_HIP(hipStreamSynchronize(eb->stream));
-    const float *h_sc = reinterpret_cast<const float *>(eb->h_out + o_sc_), *h_n2 = reinterpret_cast<const float *>(eb->h_out + o_n2_);
-    const int32_t *h_st = reinterpret_cast<const int32_t *>(eb->h_out + o_st_), *h_n = reinterpret_cast<const int32_t *>(eb->h_out + o_n_);
-    const uint32_t *h_ta = reinterpret_cast<const uint32_t *>(eb->h_out + o_ta_);
-    const int32_t *h_ti = reinterpret_cast<const int32_t *>(eb->h_out + o_ti_);
-    const float *h_tp = reinterpret_cast<const float *>(eb->h_out + o_tp_);
+    P7X_HIP(hipStreamSynchronize(lease_->stream));
+    const unsigned char *const h_out = lease_->h_out.as<unsigned char>();
+    const float *h_sc = reinterpret_cast<const float *>(h_out + o_sc_), *h_n2 = reinterpret_cast<const float *>(h_out + o_n2_);
+    const int32_t *h_st = reinterpret_cast<const int32_t *>(h_out + o_st_), *h_n = reinterpret_cast<const int32_t *>(h_out + o_n_);
+    const uint32_t *h_ta = reinterpret_cast<const uint32_t *>(h_out + o_ta_);
+    const int32_t *h_ti = reinterpret_cast<const int32_t *>(h_out + o_ti_);
+    const float *h_tp = reinterpret_cast<const float *>(h_out + o_tp_);
     for (size_t j = 0; j < jobs_.size(); ++j) {
       const JobMeta &m = meta_[j];
       res[j].assign((size_t) m.nenv, EnvelopeResult{});
@@ -295,7 +245,7 @@ public:
         const int64_t g = m.first + r;
         EnvelopeResult &e = res[j][(size_t) r];
         e.envsc = h_sc[2 * g]; e.oasc = h_sc[2 * g + 1]; e.status = h_st[g];
-        e.orig = reinterpret_cast<const float *>(eb->h_out + o_orig_)[g];
+        e.orig = reinterpret_cast<const float *>(h_out + o_orig_)[g];
         std::memcpy(e.null2, h_n2 + (size_t) g * 32, sizeof(e.null2));
         e.ntrace = h_n[g]; e.ta = h_ta + tr_off_[(size_t) g]; e.ti = h_ti + tr_off_[(size_t) g]; e.tp = h_tp + tr_off_[(size_t) g];
       }
@@ -317,8 +267,7 @@ private:
   std::vector<int> order_;
   std::vector<int64_t> tr_off_;
   int64_t nenv_ = 0;
-  EnvBuffers *eb_ = nullptr;
-  EnvBuffers *lease_ = nullptr;
+  Lease<EnvBuffers> lease_;
   size_t o_sc_ = 0, o_n2_ = 0, o_st_ = 0, o_n_ = 0, o_orig_ = 0, o_ta_ = 0, o_ti_ = 0, o_tp_ = 0;
 };
 

@@ -18,14 +18,8 @@ namespace p7x {
 
 namespace {
 
-// a device buffer from the context's slab pool (hipMalloc / hipFree wait for every stream of the device: see p7x_seqdb_create)
-struct DevBuf {
-  DeviceCtx *ctx = nullptr; void *p = nullptr; size_t bytes = 0;
-  explicit DevBuf(DeviceCtx *c) : ctx(c) {}
-  DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) slab_release(ctx, p, bytes); }
-  int alloc(size_t want) { if (p) { slab_release(ctx, p, bytes); p = nullptr; bytes = 0; } return slab_acquire(ctx, std::max<size_t>(want, 16), &p, &bytes); }
-};
+// a scratch array of a stage, from the context's slab pool; never empty, whatever the count
+static int alloc(DeviceBuf &b, DeviceCtx *ctx, size_t want) { return b.reserve(ctx, std::max<size_t>(want, 16)); }
 static hipStream_t lt_window_stream(DeviceCtx *ctx)
 {
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -117,17 +111,17 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
     ssvlong_build_tables(p, R, false, tab4q, tab_full, &pair_slack);
   }
   std::lock_guard<std::mutex> scan_turn(ctx->lt_scan_mu);      // one scan at a time per device (see DeviceCtx)
-  DevBuf d_tab4q{ctx}, d_full{ctx}, d_comp{ctx}, d_nrec{ctx}, d_pos{ctx}, d_strand{ctx}, d_k{ctx}, d_sc{ctx};
+  DeviceBuf d_tab4q, d_full, d_comp, d_nrec, d_pos, d_strand, d_k, d_sc;
   int st;
-  if ((st = d_tab4q.alloc(tab4q.size() * 4)) || (st = d_full.alloc(tab_full.size() * 4)) || (st = d_comp.alloc(32)) || (st = d_nrec.alloc(4))) return st;
+  if ((st = alloc(d_tab4q, ctx, tab4q.size() * 4)) || (st = alloc(d_full, ctx, tab_full.size() * 4)) || (st = alloc(d_comp, ctx, 32)) || (st = alloc(d_nrec, ctx, 4))) return st;
   hipStream_t s = ctx->stream;
   std::shared_ptr<ResidentTargets> d_seq;
   bool uploaded = false;
   if ((st = resident_targets(ctx, device, resident_key, seq1, L, d_seq, &uploaded)) != P7X_OK) return st;
   if ((debug_opt(OPT_TRACE_LONGTARGET) > 0)) std::fprintf(stderr, "[lt] targets on the device: %s (%lld bytes, key %llu)\n", uploaded ? "uploaded" : "resident", (long long) L, (unsigned long long) resident_key);
-  P7X_HIP(hipMemcpyAsync(d_tab4q.p, tab4q.data(), tab4q.size() * 4, hipMemcpyHostToDevice, s));
-  P7X_HIP(hipMemcpyAsync(d_full.p, tab_full.data(), tab_full.size() * 4, hipMemcpyHostToDevice, s));
-  P7X_HIP(hipMemcpyAsync(d_comp.p, longtarget_complement(p.abc_type), 18, hipMemcpyHostToDevice, s));
+  P7X_HIP(hipMemcpyAsync(d_tab4q.as<void>(), tab4q.data(), tab4q.size() * 4, hipMemcpyHostToDevice, s));
+  P7X_HIP(hipMemcpyAsync(d_full.as<void>(), tab_full.data(), tab_full.size() * 4, hipMemcpyHostToDevice, s));
+  P7X_HIP(hipMemcpyAsync(d_comp.as<void>(), longtarget_complement(p.abc_type), 18, hipMemcpyHostToDevice, s));
   // chunks: long enough that the M warm-up rows are a small overhead.  The kernel's wavefronts all stay on the device and
   // take the chunks in turn, so the number of chunks is made a multiple of the wavefronts (a last round that only some
   // of them take is paid in full: 16,384 chunks on 3,072 wavefronts were six rounds, the last a third full)
@@ -140,15 +134,15 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
   chunk_len = ((chunk_len + 63) / 64) * 64;
   const int nstrands = strands_mask == 3 ? 2 : 1;
   SsvLongArgs a{};
-  a.tab4q = static_cast<const uint32_t *>(d_tab4q.p); a.tab_full = static_cast<const uint32_t *>(d_full.p);
-  a.dsq = static_cast<const uint8_t *>(d_seq->p); a.comp = static_cast<const uint8_t *>(d_comp.p);
+  a.tab4q = d_tab4q.as<const uint32_t>(); a.tab_full = d_full.as<const uint32_t>();
+  a.dsq = static_cast<const uint8_t *>(d_seq->p); a.comp = d_comp.as<const uint8_t>();
   a.L = L; a.M = p.M; a.Kp = p.Kp; a.chunk_len = chunk_len;
   a.chunks_per_strand = (L + chunk_len - 1) / chunk_len; a.nchunks = a.chunks_per_strand * nstrands;
   a.thresh_s = sc_thresh - xB - 32768; a.xB = xB; a.Q16 = p.Q16();
-  a.nrec = static_cast<int *>(d_nrec.p);
+  a.nrec = d_nrec.as<int>();
   a.strand0 = strands_mask == 2 ? 1 : 0;
   a.pair_slack = pair_slack;
-  DevBuf d_chunks{ctx};
+  DeviceBuf d_chunks;
   if (ranges) {
     std::vector<long long> list;
     for (const ScanRange &r : *ranges) {
@@ -159,10 +153,10 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
     list.erase(std::unique(list.begin(), list.end()), list.end());
     rows.clear();
     if (list.empty()) { if (ms) *ms = 0.0; return P7X_OK; }
-    if ((st = d_chunks.alloc(list.size() * 8)) != P7X_OK) return st;
-    P7X_HIP(hipMemcpyAsync(d_chunks.p, list.data(), list.size() * 8, hipMemcpyHostToDevice, s));
+    if ((st = alloc(d_chunks, ctx, list.size() * 8)) != P7X_OK) return st;
+    P7X_HIP(hipMemcpyAsync(d_chunks.as<void>(), list.data(), list.size() * 8, hipMemcpyHostToDevice, s));
     P7X_HIP(hipStreamSynchronize(s));                       // <list> leaves scope
-    a.chunk_list = static_cast<const long long *>(d_chunks.p); a.nchunks = (long long) list.size();
+    a.chunk_list = d_chunks.as<const long long>(); a.nchunks = (long long) list.size();
   }
   struct Events {                     // destroyed on every way out
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -172,25 +166,25 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
   hipEvent_t e0 = ev.e0, e1 = ev.e1;
   int cap = (int) std::min<int64_t>(std::max<int64_t>(1 << 16, L / 64), 1 << 28);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if ((st = d_pos.alloc((size_t) cap * 8)) || (st = d_strand.alloc((size_t) cap)) || (st = d_k.alloc((size_t) cap * 4)) || (st = d_sc.alloc((size_t) cap * 4))) return st;
-    a.rec_pos = static_cast<long long *>(d_pos.p); a.rec_strand = static_cast<uint8_t *>(d_strand.p);
-    a.rec_k = static_cast<int *>(d_k.p); a.rec_sc = static_cast<int *>(d_sc.p); a.rec_cap = cap;
-    P7X_HIP(hipMemsetAsync(d_nrec.p, 0, 4, s));
+    if ((st = alloc(d_pos, ctx, (size_t) cap * 8)) || (st = alloc(d_strand, ctx, (size_t) cap)) || (st = alloc(d_k, ctx, (size_t) cap * 4)) || (st = alloc(d_sc, ctx, (size_t) cap * 4))) return st;
+    a.rec_pos = d_pos.as<long long>(); a.rec_strand = d_strand.as<uint8_t>();
+    a.rec_k = d_k.as<int>(); a.rec_sc = d_sc.as<int>(); a.rec_cap = cap;
+    P7X_HIP(hipMemsetAsync(d_nrec.as<void>(), 0, 4, s));
     P7X_HIP(hipEventRecord(e0, s));
     if ((st = ssvlong_launch(R, pair, half, a, ctx->num_cu, s)) != P7X_OK) return st;
     P7X_HIP(hipEventRecord(e1, s));
     int nrec = 0;
-    P7X_HIP(hipMemcpyAsync(&nrec, d_nrec.p, 4, hipMemcpyDeviceToHost, s));
+    P7X_HIP(hipMemcpyAsync(&nrec, d_nrec.as<void>(), 4, hipMemcpyDeviceToHost, s));
     P7X_HIP(hipStreamSynchronize(s));
     float t = 0; (void) hipEventElapsedTime(&t, e0, e1);
     if (ms) *ms = t;
     if (nrec <= cap) {
       std::vector<long long> pos((size_t) nrec); std::vector<uint8_t> strand((size_t) nrec); std::vector<int> k((size_t) nrec), sc((size_t) nrec);
       if (nrec) {
-        P7X_HIP(hipMemcpy(pos.data(), d_pos.p, (size_t) nrec * 8, hipMemcpyDeviceToHost));
-        P7X_HIP(hipMemcpy(strand.data(), d_strand.p, (size_t) nrec, hipMemcpyDeviceToHost));
-        P7X_HIP(hipMemcpy(k.data(), d_k.p, (size_t) nrec * 4, hipMemcpyDeviceToHost));
-        P7X_HIP(hipMemcpy(sc.data(), d_sc.p, (size_t) nrec * 4, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(pos.data(), d_pos.as<void>(), (size_t) nrec * 8, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(strand.data(), d_strand.as<void>(), (size_t) nrec, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(k.data(), d_k.as<void>(), (size_t) nrec * 4, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(sc.data(), d_sc.as<void>(), (size_t) nrec * 4, hipMemcpyDeviceToHost));
       }
       rows.resize((size_t) nrec);
       for (int i = 0; i < nrec; ++i) rows[(size_t) i] = ScanRow{ pos[(size_t) i], strand[(size_t) i], k[(size_t) i], sc[(size_t) i] };
@@ -377,31 +371,31 @@ struct DeviceWindowScorer final : LongTargetWindowScorer {
     std::vector<int32_t> list(n);
     for (size_t i = 0; i < n; ++i) list[i] = slot_of[(size_t) which[i]];
     hipStream_t s = stream ? stream : (stream = lt_window_stream(ctx));
-    DevBuf d_list{ctx}, d_thr{ctx}, d_xc{ctx}, d_nrec{ctx}, d_rec{ctx}, d_args{ctx};
-    if ((st = d_list.alloc(n * 4)) || (st = d_thr.alloc(n * 4)) || (st = d_xc.alloc(n * 4)) || (st = d_nrec.alloc(4)) || (st = d_args.alloc(sizeof(WaveSeqArgs)))) return st;
-    P7X_HIP(hipMemcpyAsync(d_list.p, list.data(), n * 4, hipMemcpyHostToDevice, s));
-    P7X_HIP(hipMemcpyAsync(d_thr.p, thresh, n * 4, hipMemcpyHostToDevice, s));
+    DeviceBuf d_list, d_thr, d_xc, d_nrec, d_rec, d_args;
+    if ((st = alloc(d_list, ctx, n * 4)) || (st = alloc(d_thr, ctx, n * 4)) || (st = alloc(d_xc, ctx, n * 4)) || (st = alloc(d_nrec, ctx, 4)) || (st = alloc(d_args, ctx, sizeof(WaveSeqArgs)))) return st;
+    P7X_HIP(hipMemcpyAsync(d_list.as<void>(), list.data(), n * 4, hipMemcpyHostToDevice, s));
+    P7X_HIP(hipMemcpyAsync(d_thr.as<void>(), thresh, n * 4, hipMemcpyHostToDevice, s));
     int cap = (int) std::max<size_t>(1 << 16, 64 * n);
     for (int attempt = 0; attempt < 2; ++attempt) {
-      if ((st = d_rec.alloc((size_t) cap * 12)) != P7X_OK) return st;
+      if ((st = alloc(d_rec, ctx, (size_t) cap * 12)) != P7X_OK) return st;
       WaveSeqArgs a{};
       a.M = p.M; a.C = dp->vitC; a.nrows = p.Kp + 1;
       a.trans = dp->vit_trans; a.emis = dp->vit_emis;
       a.dsq = db->d_dsq; a.slot_off = db->d_slot_off; a.slot_len = db->d_slot_len;
-      a.list = static_cast<const int32_t *>(d_list.p); a.nlist = (int) n;
+      a.list = d_list.as<const int32_t>(); a.nlist = (int) n;
       a.xwmove_tab = ctx->lt.xwmove; a.base_w = p.base_w; a.xw_e = p.xw[XE][MOVE]; a.ddbound = p.ddbound_w;
-      a.out_xC = static_cast<int32_t *>(d_xc.p);
-      a.lt_thresh = static_cast<const int *>(d_thr.p); a.lt_nrec = static_cast<int *>(d_nrec.p); a.lt_rec = static_cast<int *>(d_rec.p); a.lt_cap = cap;
-      P7X_HIP(hipMemcpyAsync(d_args.p, &a, sizeof(a), hipMemcpyHostToDevice, s));
-      P7X_HIP(hipMemsetAsync(d_nrec.p, 0, 4, s));
-      ArgRun<WaveSeqArgs> run; run.host = &a; run.dev = d_args.p; run.stride = (uint32_t) sizeof(WaveSeqArgs); run.n = 1;
+      a.out_xC = d_xc.as<int32_t>();
+      a.lt_thresh = d_thr.as<const int>(); a.lt_nrec = d_nrec.as<int>(); a.lt_rec = d_rec.as<int>(); a.lt_cap = cap;
+      P7X_HIP(hipMemcpyAsync(d_args.as<void>(), &a, sizeof(a), hipMemcpyHostToDevice, s));
+      P7X_HIP(hipMemsetAsync(d_nrec.as<void>(), 0, 4, s));
+      ArgRun<WaveSeqArgs> run; run.host = &a; run.dev = d_args.as<void>(); run.stride = (uint32_t) sizeof(WaveSeqArgs); run.n = 1;
       if ((st = vit_launch(run, ctx->num_cu, s)) != P7X_OK) return st;
       int nrec = 0;
-      P7X_HIP(hipMemcpyAsync(&nrec, d_nrec.p, 4, hipMemcpyDeviceToHost, s));
+      P7X_HIP(hipMemcpyAsync(&nrec, d_nrec.as<void>(), 4, hipMemcpyDeviceToHost, s));
       P7X_HIP(hipStreamSynchronize(s));
       if (nrec <= cap) {
         rec.resize((size_t) nrec * 3);
-        if (nrec) P7X_HIP(hipMemcpy(rec.data(), d_rec.p, (size_t) nrec * 12, hipMemcpyDeviceToHost));
+        if (nrec) P7X_HIP(hipMemcpy(rec.data(), d_rec.as<void>(), (size_t) nrec * 12, hipMemcpyDeviceToHost));
         // (item, row, node) ascending, as the host scan emits them
         std::vector<int> ord((size_t) nrec);
         for (int i = 0; i < nrec; ++i) ord[(size_t) i] = i;

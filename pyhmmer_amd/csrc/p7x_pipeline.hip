@@ -527,21 +527,20 @@ constexpr int kLaneCounters = 16;
 // A workspace serves a batch of up to <nlanes> queries against a block of up to <cap_slots> targets: per-lane
 // score / list arrays, one row arena shared by the lanes, the lanes' argument records, one stream.
 struct Workspace {
-  int device = -1; int64_t cap_slots = 0; int nlanes = 0;
+  int device = -1; DeviceCtx *ctx = nullptr; int64_t cap_slots = 0; int nlanes = 0;      // cap_slots > 0: complete
   // per lane, lane-major: lane l's part starts at l * cap_slots elements
-  int16_t *xJ = nullptr; float *usc = nullptr, *filtersc = nullptr, *vfsc = nullptr, *fwdsc = nullptr;
-  int32_t *xC = nullptr; float *fwd_by_item = nullptr;
-  int32_t *list_bias = nullptr, *list_vit = nullptr, *list_fwd = nullptr, *list_fin = nullptr;
-  uint8_t *stage = nullptr;
-  int *chunk_cnt = nullptr; int64_t chunks_per_lane = 0;      // [nlanes][chunks_per_lane] marked slots per compaction chunk
-  int *counters = nullptr;                  // [nlanes][kLaneCounters] then the arena cursor (64 bit)
-  LaneArgs *d_args = nullptr, *h_args = nullptr; size_t h_args_bytes = 0;     // [nlanes], device / pinned host
+  DeviceBuf xJ /* int16 */, usc, filtersc, vfsc, fwdsc /* float */, xC /* int32 */, fwd_by_item /* float */;
+  DeviceBuf list_bias, list_vit, list_fwd, list_fin;      // int32
+  DeviceBuf stage;                                        // uint8
+  DeviceBuf chunk_cnt; int64_t chunks_per_lane = 0;       // int [nlanes][chunks_per_lane] marked slots per compaction chunk
+  DeviceBuf counters;                                     // int [nlanes][kLaneCounters] then the arena cursor (64 bit)
+  DeviceBuf d_args; PinnedBuf h_args;                     // LaneArgs [nlanes], device / pinned host
   // Forward survivors: row arena (Forward rows, Backward rows, region-scan scratch) and per-lane, per-survivor arrays
-  float *xmx_f = nullptr, *xmx_b = nullptr, *xmx_s = nullptr; int64_t xmx_cap = 0; size_t xmx_bytes[3] = { 0, 0, 0 };   // slabs of the context's pool
-  int64_t *xmx_off = nullptr; int32_t *reg_out = nullptr; float *bck_sc = nullptr;   // [nlanes][fin_cap (* kRegionCap*3+2)]
+  DeviceBuf xmx_f, xmx_b, xmx_s; int64_t xmx_cap = 0;     // floats
+  DeviceBuf xmx_off /* int64 */, reg_out /* int32 */, bck_sc /* float */;   // [nlanes][fin_cap (* kRegionCap*3+2)]
   int64_t fin_cap = 0;
   // one lane at a time, when the shared buffers were too small for it (rare)
-  int64_t *rt_xmx_off = nullptr; int32_t *rt_reg_out = nullptr; float *rt_bck_sc = nullptr; int64_t rt_cap = 0;
+  DeviceBuf rt_xmx_off, rt_reg_out, rt_bck_sc; int64_t rt_cap = 0;
   hipEvent_t ev[8]{};
   hipEvent_t ev_sync = nullptr;
   hipStream_t stream = nullptr;     // one stream per cascade in flight: concurrent searches overlap on the device
@@ -553,134 +552,96 @@ struct Workspace {
   static constexpr int kTierRuns = 8;      // MSV tier launches of a batch (p7x_msv.hip: five tiers; runs of lanes that share one)
   hipEvent_t ev_tier[kTierRuns]{}, ev_tier0[kTierRuns]{};     // end / begin of every tier launch (timed: the bench's roofline is the largest one's)
   int ntier_runs = 0, tier_lanes[kTierRuns]{}; int64_t tier_nodes[kTierRuns]{};     // of the cascade in flight
-  int *h_counts = nullptr; size_t h_counts_bytes = 0;   // pinned mirror of counters
+  PinnedBuf h_counts;               // pinned mirror of counters
   // results of the Forward survivors of all lanes, packed by pack_survivors_kernel for one copy to the host
-  unsigned char *pack_dev = nullptr; size_t pack_dev_bytes = 0;      // slab of the context's pool
-  unsigned char *pack_host = nullptr; size_t pack_host_bytes = 0;    // pinned
+  DeviceBuf pack_dev; PinnedBuf pack_host;
   int64_t early_T_cap = 0;          // > 0: the enqueue half packed and copied the survivors' results itself, for up to this many
   int64_t last_T = 2048;            // survivors of the last batch collected on this workspace (sizes the next early pack)
-  bool busy = false;                // between the enqueue and the collect half of a cascade
-  int set = -1;                     // the context's stream set this lease runs on (taken when leased, given back on release)
+  int set = -1;                     // the context's stream set this lease runs on (taken when leased, given back with the lease)
   size_t counters_bytes() const { return (size_t) nlanes * kLaneCounters * 4 + 8; }
-  unsigned long long *cursor() const { return reinterpret_cast<unsigned long long *>(counters + (size_t) nlanes * kLaneCounters); }
-  ~Workspace() {
+  unsigned long long *cursor() const { return reinterpret_cast<unsigned long long *>(counters.as<int>() + (size_t) nlanes * kLaneCounters); }
+  ~Workspace() {      // (a workspace that could not be completed; the pooled ones are never destroyed)
     if (device < 0) return;
     (void) hipSetDevice(device);
-    (void) hipFree(xJ); (void) hipFree(usc); (void) hipFree(filtersc); (void) hipFree(vfsc); (void) hipFree(fwdsc);
-    (void) hipFree(xC); (void) hipFree(fwd_by_item); (void) hipFree(list_bias); (void) hipFree(list_vit);
-    (void) hipFree(list_fwd); (void) hipFree(list_fin); (void) hipFree(counters); (void) hipFree(stage); (void) hipFree(d_args);
-    (void) hipFree(chunk_cnt);
-    (void) hipFree(xmx_f); (void) hipFree(xmx_b); (void) hipFree(xmx_s); (void) hipFree(xmx_off); (void) hipFree(reg_out); (void) hipFree(bck_sc);
-    (void) hipFree(rt_xmx_off); (void) hipFree(rt_reg_out); (void) hipFree(rt_bck_sc);
     for (auto &e : ev) if (e) (void) hipEventDestroy(e);
     if (ev_sync) (void) hipEventDestroy(ev_sync);
     if (ev_fork) (void) hipEventDestroy(ev_fork);
     for (auto &e : ev_join) if (e) (void) hipEventDestroy(e);
     for (auto &e : ev_tier) if (e) (void) hipEventDestroy(e);
     for (auto &e : ev_tier0) if (e) (void) hipEventDestroy(e);
-    pinned_release(h_counts, h_counts_bytes);
-    pinned_release(pack_host, pack_host_bytes); (void) hipFree(pack_dev);
-    pinned_release(h_args, h_args_bytes);
   }
   StageBufs lane_bufs(int l) const
   {
     const size_t o = (size_t) l * (size_t) cap_slots;
     StageBufs b{};
-    b.xJ = xJ + o; b.usc = usc + o; b.filtersc = filtersc + o; b.vfsc = vfsc + o; b.fwdsc = fwdsc + o;
-    b.xC = xC + o; b.fwd_by_item = fwd_by_item + o;
-    b.list_bias = list_bias + o; b.list_vit = list_vit + o; b.list_fwd = list_fwd + o; b.list_fin = list_fin + o;
-    b.stage = stage + o; b.counters = counters + (size_t) l * kLaneCounters;
+    b.xJ = xJ.as<int16_t>() + o; b.usc = usc.as<float>() + o; b.filtersc = filtersc.as<float>() + o; b.vfsc = vfsc.as<float>() + o; b.fwdsc = fwdsc.as<float>() + o;
+    b.xC = xC.as<int32_t>() + o; b.fwd_by_item = fwd_by_item.as<float>() + o;
+    b.list_bias = list_bias.as<int32_t>() + o; b.list_vit = list_vit.as<int32_t>() + o; b.list_fwd = list_fwd.as<int32_t>() + o; b.list_fin = list_fin.as<int32_t>() + o;
+    b.stage = stage.as<uint8_t>() + o; b.counters = counters.as<int>() + (size_t) l * kLaneCounters;
     return b;
   }
+  // The stream sets are the context's (created once, placed apart on the hardware queues); a lease runs on the set that the
+  // fewest cascades are using right now.  (Until round 5 a workspace kept the set it was created with, handed out by a
+  // creation counter: a workspace that was replaced by a larger one, or more than four live workspaces, could put two
+  // running cascades on the same eight streams while another set sat idle.)
+  void take_stream_set()
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    set = 0;
+    for (int k = 1; k < DeviceCtx::kWsSets; ++k) if (ctx->ws_set_users[k] < ctx->ws_set_users[set]) set = k;
+    ctx->ws_set_users[set]++;
+    stream = ctx->ws_main[set];
+    for (int k = 0; k < kSide; ++k) side[k] = ctx->ws_side[set][k];
+  }
+  void on_return()      // the end of a lease (LeasePool)
+  {
+    if (set < 0) return;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->ws_set_users[set] > 0) ctx->ws_set_users[set]--;
+    set = -1;
+  }
 };
 
-// Workspaces are leased from a process-wide pool and returned to it (release_workspace); the pool is never torn down,
-// so no device memory, stream or event is destroyed from a thread that is exiting or at process exit.
-struct WorkspacePool { std::mutex mu; std::vector<Workspace *> all; };
-static WorkspacePool &ws_pool() { static WorkspacePool *p = new WorkspacePool(); return *p; }
-
-// The stream sets are the context's (created once, placed apart on the hardware queues); a lease runs on the set that the
-// fewest cascades are using right now.  (Until round 5 a workspace kept the set it was created with, handed out by a
-// creation counter: a workspace that was replaced by a larger one, or more than four live workspaces, could put two
-// running cascades on the same eight streams while another set sat idle.)
-static int lease_stream_set(Workspace *w)
+// The arrays and events of a new workspace for up to <nslots> targets and <nlanes> queries.
+static int build_workspace(Workspace *w, DeviceCtx *ctx, int64_t nslots, int nlanes)
 {
-  DeviceCtx *ctx = nullptr;
-  const int cst = get_ctx(w->device, &ctx);
-  if (cst != P7X_OK) return cst;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  int set = 0;
-  for (int k = 1; k < DeviceCtx::kWsSets; ++k) if (ctx->ws_set_users[k] < ctx->ws_set_users[set]) set = k;
-  ctx->ws_set_users[set]++;
-  w->set = set;
-  w->stream = ctx->ws_main[set];
-  for (int k = 0; k < Workspace::kSide; ++k) w->side[k] = ctx->ws_side[set][k];
-  return P7X_OK;
-}
-
-static void release_workspace(Workspace *w)
-{
-  if (!w) return;
-  if (w->set >= 0) {
-    DeviceCtx *ctx = nullptr;
-    if (get_ctx(w->device, &ctx) == P7X_OK) { std::lock_guard<std::mutex> lk(ctx->mu); if (ctx->ws_set_users[w->set] > 0) ctx->ws_set_users[w->set]--; }
-    w->set = -1;
-  }
-  std::lock_guard<std::mutex> lk(ws_pool().mu);
-  w->busy = false;
-}
-
-static int get_workspace(int device, int64_t nslots, int nlanes, Workspace **out)
-{
-  Workspace *found = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(ws_pool().mu);
-    Workspace *best = nullptr;
-    for (Workspace *w : ws_pool().all)
-      if (!w->busy && w->device == device && w->cap_slots >= nslots && w->nlanes >= nlanes &&
-          (!best || w->cap_slots * w->nlanes < best->cap_slots * best->nlanes)) best = w;
-    if (best) { best->busy = true; found = best; }
-  }
-  if (found) { *out = found; return lease_stream_set(found); }
-  auto w = std::make_unique<Workspace>();
-  w->device = device;
+  w->ctx = ctx; w->nlanes = nlanes;
   const int64_t cap = std::max<int64_t>(64, ((nslots + 63) / 64) * 64);
-  w->cap_slots = cap; w->nlanes = nlanes;
   const size_t tot = (size_t) cap * (size_t) nlanes;
-  P7X_HIP(hipMalloc(&w->xJ, tot * 2));
-  P7X_HIP(hipMalloc(&w->usc, tot * 4)); P7X_HIP(hipMalloc(&w->filtersc, tot * 4));
-  P7X_HIP(hipMalloc(&w->vfsc, tot * 4)); P7X_HIP(hipMalloc(&w->fwdsc, tot * 4));
-  P7X_HIP(hipMalloc(&w->xC, tot * 4)); P7X_HIP(hipMalloc(&w->fwd_by_item, tot * 4));
-  P7X_HIP(hipMalloc(&w->list_bias, tot * 4)); P7X_HIP(hipMalloc(&w->list_vit, tot * 4));
-  P7X_HIP(hipMalloc(&w->list_fwd, tot * 4)); P7X_HIP(hipMalloc(&w->list_fin, tot * 4));
-  P7X_HIP(hipMalloc(&w->counters, w->counters_bytes()));
-  P7X_HIP(hipMalloc(&w->d_args, (size_t) nlanes * sizeof(LaneArgs)));
-  { void *hp = nullptr; const int pst = pinned_acquire(w->counters_bytes(), &hp, &w->h_counts_bytes); if (pst != P7X_OK) return pst; w->h_counts = static_cast<int *>(hp); }
-  { void *hp = nullptr; const int pst = pinned_acquire((size_t) nlanes * sizeof(LaneArgs), &hp, &w->h_args_bytes); if (pst != P7X_OK) return pst; w->h_args = static_cast<LaneArgs *>(hp); }
-  P7X_HIP(hipMalloc(&w->stage, tot));
   w->chunks_per_lane = (cap + kCompactChunk - 1) / kCompactChunk;
-  P7X_HIP(hipMalloc(&w->chunk_cnt, (size_t) nlanes * (size_t) w->chunks_per_lane * 4));
+  const std::pair<DeviceBuf *, size_t> dev[] = {
+    { &w->xJ, tot * 2 }, { &w->usc, tot * 4 }, { &w->filtersc, tot * 4 }, { &w->vfsc, tot * 4 }, { &w->fwdsc, tot * 4 }, { &w->xC, tot * 4 },
+    { &w->fwd_by_item, tot * 4 }, { &w->list_bias, tot * 4 }, { &w->list_vit, tot * 4 }, { &w->list_fwd, tot * 4 }, { &w->list_fin, tot * 4 },
+    { &w->counters, w->counters_bytes() }, { &w->d_args, (size_t) nlanes * sizeof(LaneArgs) }, { &w->stage, tot },
+    { &w->chunk_cnt, (size_t) nlanes * (size_t) w->chunks_per_lane * 4 } };
+  int st = P7X_OK;
+  for (const auto &d : dev) if ((st = d.first->reserve(ctx, d.second)) != P7X_OK) return st;
+  if ((st = w->h_counts.reserve(w->counters_bytes())) != P7X_OK || (st = w->h_args.reserve((size_t) nlanes * sizeof(LaneArgs))) != P7X_OK) return st;
   for (auto &e : w->ev) P7X_HIP(hipEventCreate(&e));
   P7X_HIP(hipEventCreateWithFlags(&w->ev_sync, hipEventDisableTiming));
-  {   // the cascade is the critical path of a search (its streams have the highest priority: its wavefronts go first when
-      // the envelope kernel of the previous query shares the device); the streams are the context's, dealt out in turn
-    const int cst = lease_stream_set(w.get());
-    if (cst != P7X_OK) return cst;
-    P7X_HIP(hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming));
-    for (auto &e : w->ev_join) P7X_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto &e : w->ev_tier) P7X_HIP(hipEventCreate(&e));
-    for (auto &e : w->ev_tier0) P7X_HIP(hipEventCreate(&e));
-  }
-  w->busy = true;
-  *out = w.get();
-  std::lock_guard<std::mutex> lk(ws_pool().mu);
-  ws_pool().all.push_back(w.release());
+  P7X_HIP(hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming));
+  for (auto &e : w->ev_join) P7X_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto &e : w->ev_tier) P7X_HIP(hipEventCreate(&e));
+  for (auto &e : w->ev_tier0) P7X_HIP(hipEventCreate(&e));
+  w->cap_slots = cap;
   return P7X_OK;
 }
-struct WorkspaceLease {      // for the synchronous entry points
-  Workspace *w = nullptr;
-  ~WorkspaceLease() { release_workspace(w); }
-};
+
+// Workspaces are leased from their process-wide pool (p7x_devmem.hpp): the smallest idle one that is large enough, else a
+// new one.  The stream set is taken last, when nothing can fail any more, and goes back with the lease.  (The cascade is
+// the critical path of a search: its streams have the highest priority, its wavefronts go first when the envelope kernel
+// of the previous query shares the device.)
+static int get_workspace(DeviceCtx *ctx, int64_t nslots, int nlanes, Lease<Workspace> &out)
+{
+  out = LeasePool<Workspace>::instance().lease(ctx->device, [&](const Workspace &w, const Workspace *b) {
+    return w.cap_slots >= nslots && w.nlanes >= nlanes && (!b || w.cap_slots * w.nlanes < b->cap_slots * b->nlanes); });
+  if (out->cap_slots == 0) {
+    const int st = build_workspace(out.get(), ctx, nslots, nlanes);
+    if (st != P7X_OK) { out.discard(); return st; }
+  }
+  out->take_stream_set();
+  return P7X_OK;
+}
 
 static StageParams make_params(const Profile &p, const p7x_pipeline_cfg &cfg)
 {
@@ -814,8 +775,8 @@ static void fill_vit_args(LaneArgs &la, const Profile &p, const DevProfile *dp, 
 template <class A> static ArgRun<A> lane_run(const Workspace *ws, A LaneArgs::*member, int first, int n)
 {
   ArgRun<A> r;
-  r.host = &(ws->h_args[first].*member);
-  r.dev = reinterpret_cast<const char *>(ws->d_args + first) + (reinterpret_cast<const char *>(r.host) - reinterpret_cast<const char *>(ws->h_args + first));
+  r.host = &(ws->h_args.as<LaneArgs>()[first].*member);
+  r.dev = reinterpret_cast<const char *>(ws->d_args.as<LaneArgs>() + first) + (reinterpret_cast<const char *>(r.host) - reinterpret_cast<const char *>(ws->h_args.as<LaneArgs>() + first));
   r.stride = (uint32_t) sizeof(LaneArgs); r.n = n;
   return r;
 }
@@ -824,7 +785,7 @@ struct LaneModel { const p7x_oprofile *om = nullptr; DevProfile *dp = nullptr; }
 
 static int upload_args(Workspace *ws, int first, int n, hipStream_t s)
 {
-  P7X_HIP(hipMemcpyAsync(ws->d_args + first, ws->h_args + first, (size_t) n * sizeof(LaneArgs), hipMemcpyHostToDevice, s));
+  P7X_HIP(hipMemcpyAsync(ws->d_args.as<LaneArgs>() + first, ws->h_args.as<LaneArgs>() + first, (size_t) n * sizeof(LaneArgs), hipMemcpyHostToDevice, s));
   return P7X_OK;
 }
 
@@ -926,10 +887,10 @@ struct CascadeRun {
   std::vector<int> query_of;              // lane -> caller index
   const p7x_seqdb *db = nullptr;
   DeviceCtx *ctx = nullptr;
-  Workspace *ws = nullptr;
+  Lease<Workspace> ws;                    // until the results are collected
   int est_bias = 0, est_vit = 0, est_fwd = 0, est_fin = 0;      // expected list lengths (grid sizing)
   bool queued = false, collected = false;
-  ~CascadeRun() { if (ws && queued && !collected) { (void) hipStreamSynchronize(ws->stream); release_workspace(ws); } }
+  ~CascadeRun() { sync_and_return(ws); }
 };
 
 // The Forward survivors of every lane of a batch, gathered for ONE copy to the host: slot, Forward score, row offset,
@@ -1021,7 +982,7 @@ static int64_t longest_rows(const p7x_seqdb *db, int64_t count)
 // [first, first + n), and the buffers behind them.  <retry>: one lane on the retry buffers, sized for its own nfin.
 static int fill_survivor_args(CascadeRun &r, int first, int n, bool retry, int nfin)
 {
-  const p7x_seqdb *db = r.db; Workspace *ws = r.ws; DeviceCtx *ctx = r.ctx;
+  const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get(); DeviceCtx *ctx = r.ctx;
   int64_t want_cap = std::min<int64_t>(db->nslots, std::max<int64_t>(4096, db->nslots / 64));
   if (retry) want_cap = std::min<int64_t>(db->nslots, std::max<int64_t>(want_cap, (int64_t) nfin));
   // The lanes of a batch share the row arena (one cursor).  A batch of many profiles against a small block (the scan
@@ -1029,47 +990,37 @@ static int fill_survivor_args(CascadeRun &r, int first, int n, bool retry, int n
   // longest <want_cap> targets, so that such a batch does not fall back to the one-lane-at-a-time retry below.
   const int64_t share = retry ? 1 : std::max<int64_t>(1, std::min<int64_t>(8, n / 32));
   const int64_t want_floats = longest_rows(db, want_cap) * 6 * share;
+  // (all of them through the slab pool: hipFree would wait for the cascades of the other searches in flight.  The counts
+  // are zero while their arrays grow, so that a failure half way leaves nothing that looks usable.)
+  int st = P7X_OK;
   if (want_floats > ws->xmx_cap) {
-    // through the slab pool: hipFree would wait for the cascades of the other searches in flight
-    slab_release(ctx, ws->xmx_f, ws->xmx_bytes[0]); slab_release(ctx, ws->xmx_b, ws->xmx_bytes[1]); slab_release(ctx, ws->xmx_s, ws->xmx_bytes[2]);
-    ws->xmx_f = ws->xmx_b = ws->xmx_s = nullptr; ws->xmx_cap = 0;
-    float **dst[3] = { &ws->xmx_f, &ws->xmx_b, &ws->xmx_s };
-    for (int z = 0; z < 3; ++z) {
-      void *dp = nullptr;
-      const int sst = slab_acquire(ctx, (size_t) want_floats * 4, &dp, &ws->xmx_bytes[z]); if (sst != P7X_OK) return sst;
-      *dst[z] = static_cast<float *>(dp);
-    }
+    ws->xmx_cap = 0;
+    for (DeviceBuf *x : { &ws->xmx_f, &ws->xmx_b, &ws->xmx_s }) x->reset();      // all three go back before the first comes again
+    for (DeviceBuf *x : { &ws->xmx_f, &ws->xmx_b, &ws->xmx_s }) if ((st = x->reserve(ctx, (size_t) want_floats * 4)) != P7X_OK) return st;
     ws->xmx_cap = want_floats;
   }
-  int64_t cap = 0;
-  if (!retry) {
-    if (want_cap > ws->fin_cap) {
-      (void) hipFree(ws->xmx_off); (void) hipFree(ws->reg_out); (void) hipFree(ws->bck_sc);
-      ws->xmx_off = nullptr; ws->reg_out = nullptr; ws->bck_sc = nullptr; ws->fin_cap = 0;
-      P7X_HIP(hipMalloc(&ws->xmx_off, (size_t) ws->nlanes * want_cap * 8));
-      P7X_HIP(hipMalloc(&ws->reg_out, (size_t) ws->nlanes * want_cap * (kRegionCap * 3 + 2) * 4));
-      P7X_HIP(hipMalloc(&ws->bck_sc, (size_t) ws->nlanes * want_cap * 4));
-      ws->fin_cap = want_cap;
-    }
-    cap = ws->fin_cap;
-  } else {
-    if (want_cap > ws->rt_cap) {
-      (void) hipFree(ws->rt_xmx_off); (void) hipFree(ws->rt_reg_out); (void) hipFree(ws->rt_bck_sc);
-      ws->rt_xmx_off = nullptr; ws->rt_reg_out = nullptr; ws->rt_bck_sc = nullptr; ws->rt_cap = 0;
-      P7X_HIP(hipMalloc(&ws->rt_xmx_off, (size_t) want_cap * 8));
-      P7X_HIP(hipMalloc(&ws->rt_reg_out, (size_t) want_cap * (kRegionCap * 3 + 2) * 4));
-      P7X_HIP(hipMalloc(&ws->rt_bck_sc, (size_t) want_cap * 4));
-      ws->rt_cap = want_cap;
-    }
-    cap = ws->rt_cap;
-  }
+  // the per-survivor arrays of <lanes> lanes with room for <want> survivors each
+  auto grow_survivors = [&](DeviceBuf &off, DeviceBuf &reg, DeviceBuf &bck, int64_t &have, size_t lanes, int64_t want) {
+    if (want <= have) return (int) P7X_OK;
+    have = 0;
+    for (DeviceBuf *x : { &off, &reg, &bck }) x->reset();
+    const size_t items = lanes * (size_t) want;
+    if ((st = off.reserve(ctx, items * 8)) != P7X_OK || (st = reg.reserve(ctx, items * (kRegionCap * 3 + 2) * 4)) != P7X_OK ||
+        (st = bck.reserve(ctx, items * 4)) != P7X_OK) return st;
+    have = want;
+    return (int) P7X_OK;
+  };
+  if (!retry) st = grow_survivors(ws->xmx_off, ws->reg_out, ws->bck_sc, ws->fin_cap, (size_t) ws->nlanes, want_cap);
+  else st = grow_survivors(ws->rt_xmx_off, ws->rt_reg_out, ws->rt_bck_sc, ws->rt_cap, 1, want_cap);
+  if (st != P7X_OK) return st;
+  const int64_t cap = retry ? ws->rt_cap : ws->fin_cap;
   for (int l = first; l < first + n; ++l) {
     const Profile &p = r.lm[l].om->p; const DevProfile *dp = r.lm[l].dp;
-    LaneArgs &la = ws->h_args[l];
+    LaneArgs &la = ws->h_args.as<LaneArgs>()[l];
     const StageBufs b = ws->lane_bufs(l);
-    int64_t *xmx_off = retry ? ws->rt_xmx_off : ws->xmx_off + (size_t) l * cap;
-    int32_t *reg_out = retry ? ws->rt_reg_out : ws->reg_out + (size_t) l * cap * (kRegionCap * 3 + 2);
-    float *bck_sc = retry ? ws->rt_bck_sc : ws->bck_sc + (size_t) l * cap;
+    int64_t *xmx_off = retry ? ws->rt_xmx_off.as<int64_t>() : ws->xmx_off.as<int64_t>() + (size_t) l * cap;
+    int32_t *reg_out = retry ? ws->rt_reg_out.as<int32_t>() : ws->reg_out.as<int32_t>() + (size_t) l * cap * (kRegionCap * 3 + 2);
+    float *bck_sc = retry ? ws->rt_bck_sc.as<float>() : ws->bck_sc.as<float>() + (size_t) l * cap;
     LayoutArgs lay{};
     lay.nfin_ptr = &b.counters[4]; lay.list_fin = b.list_fin; lay.slot_len = db->d_slot_len; lay.xmx_off = xmx_off;
     lay.cap_items = (int) std::min<int64_t>(cap, INT_MAX); lay.cap_floats = (long long) ws->xmx_cap; lay.cursor = ws->cursor();
@@ -1078,15 +1029,15 @@ static int fill_survivor_args(CascadeRun &r, int first, int n, bool retry, int n
     WaveSeqArgs a = ws_args(p, dp, db, ctx);
     a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = b.list_fin; a.nlist_ptr = &b.counters[4];
     a.nlist = (int) std::min<int64_t>(cap, retry ? std::max(nfin, 1) : std::max(r.est_fin, 1));          // sizes the grid only
-    a.out_sc = b.fwd_by_item; a.xmx = ws->xmx_f; a.xmx_off = xmx_off;
+    a.out_sc = b.fwd_by_item; a.xmx = ws->xmx_f.as<float>(); a.xmx_off = xmx_off;
     a.abort_flag = &b.counters[12];
     la.rows = a;
-    a.out_sc = bck_sc; a.xmx = ws->xmx_b; a.fwd_xmx = ws->xmx_f;
+    a.out_sc = bck_sc; a.xmx = ws->xmx_b.as<float>(); a.fwd_xmx = ws->xmx_f.as<float>();
     la.bck = a;
     RegionArgs ra{};
     ra.nitems_ptr = &b.counters[4]; ra.abort_flag = &b.counters[12];
-    ra.list = b.list_fin; ra.slot_len = db->d_slot_len; ra.fx = ws->xmx_f; ra.bx = ws->xmx_b;
-    ra.xmx_off = xmx_off; ra.scratch = ws->xmx_s;
+    ra.list = b.list_fin; ra.slot_len = db->d_slot_len; ra.fx = ws->xmx_f.as<float>(); ra.bx = ws->xmx_b.as<float>();
+    ra.xmx_off = xmx_off; ra.scratch = ws->xmx_s.as<float>();
     ra.out_regs = reg_out; ra.out_n = reg_out + (size_t) cap * kRegionCap * 3;
     ra.out_nexpected = reinterpret_cast<float *>(ra.out_n + cap);
     ra.guard = (r.cfg.oa_guard > 0.0f && !r.cfg.long_targets && debug_opt(OPT_HOST_ORDER) <= 0) ? 2.0e-5f : 0.0f;      // (not when the host code is
@@ -1100,7 +1051,7 @@ static int fill_survivor_args(CascadeRun &r, int first, int n, bool retry, int n
 // the survivor passes of one class on stream <s>; the kernels read the survivor counts from device memory
 static int launch_survivor_passes(CascadeRun &r, const LaneClass &c, hipStream_t s, bool retry, bool record_events)
 {
-  Workspace *ws = r.ws; DeviceCtx *ctx = r.ctx;
+  Workspace *ws = r.ws.get(); DeviceCtx *ctx = r.ctx;
   const int64_t cap = retry ? ws->rt_cap : ws->fin_cap;
   int st = P7X_OK;
   hipLaunchKernelGGL(layout_rows_kernel, dim3(1, (unsigned) c.n), dim3(256), 0, s, lane_run(ws, &LaneArgs::lay, c.first, c.n).ref());
@@ -1130,7 +1081,7 @@ static bool fwd_grouped(const p7x_seqdb *db) { return debug_opt(OPT_FWD_GROUPED)
 // every kernel of stage 1 for the lanes of one class, on stream <s>
 static int class_cascade(CascadeRun &r, const LaneClass &c, hipStream_t s, bool record_events, bool chain_msv, bool msv_by_tier = false)
 {
-  const p7x_seqdb *db = r.db; Workspace *ws = r.ws; DeviceCtx *ctx = r.ctx;
+  const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get(); DeviceCtx *ctx = r.ctx;
   int st = P7X_OK;
   if (chain_msv) {
     // MSV launches that fill the device on their own are chained (two of them sharing the CUs only slow each other
@@ -1184,7 +1135,7 @@ static int queue_pack(CascadeRun &r, const PackLayout &lay, int64_t T, const int
 // 28 x 16 of them; stage by stage it is about 28 + 28 + 12 + 24 + 9.
 static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, hipStream_t s, int nside, const std::vector<int> &run_of)
 {
-  const p7x_seqdb *db = r.db; Workspace *ws = r.ws; DeviceCtx *ctx = r.ctx;
+  const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get(); DeviceCtx *ctx = r.ctx;
   const int nq = (int) r.lm.size();
   constexpr int kStreams = Workspace::kSide + 1;
   int st = P7X_OK;
@@ -1315,9 +1266,9 @@ static int cascade_enqueue(CascadeRun &r)
     if (r.lm[l].dp->vitC <= 0) { set_error("model too long for the device kernels: M > 8192 nodes (the reference has no limit, plan7.pyx:6156-6262; the lane-chunk layout of the wave-per-target kernels ends at 128 nodes per lane -- no Pfam-A model comes near it)"); return P7X_EINVAL; }
   std::vector<LaneClass> classes;
   if ((st = lane_classes(r.lm, db, ctx, classes)) != P7X_OK) return st;
-  if ((st = get_workspace(db->device, db->nslots, nq, &r.ws)) != P7X_OK) return st;
+  if ((st = get_workspace(ctx, db->nslots, nq, r.ws)) != P7X_OK) return st;
   tick("classes+workspace");
-  Workspace *ws = r.ws;
+  Workspace *ws = r.ws.get();
   hipStream_t s = ws->stream;
   r.queued = true;
   const ListEstimates est = estimate_lists(cfg, db->nslots);
@@ -1327,7 +1278,7 @@ static int cascade_enqueue(CascadeRun &r)
   for (const LaneClass &c : classes) for (int l = c.first; l < c.first + c.n; ++l) { nlong_of[(size_t) l] = c.nlong; vit_long_of[(size_t) l] = c.vit_long; }
   for (int l = 0; l < nq; ++l) {
     const Profile &p = r.lm[l].om->p; const DevProfile *dp = r.lm[l].dp;
-    LaneArgs &la = ws->h_args[l];
+    LaneArgs &la = ws->h_args.as<LaneArgs>()[l];
     const StageBufs b = ws->lane_bufs(l);
     DecideArgs d{};
     d.b = b; d.p = make_params(p, cfg);
@@ -1339,7 +1290,7 @@ static int cascade_enqueue(CascadeRun &r)
     fill_vit_args(la, p, dp, db, ctx, b.list_vit, est.vit, &b.counters[2], b.xC,
                   vit_long > 0 ? &b.counters[13] : nullptr, (int) std::min<int64_t>(vit_long, (int64_t) est.vit));
     CompactArgs ca{};
-    ca.stage = b.stage; ca.list = b.list_vit; ca.chunk_cnt = ws->chunk_cnt + (size_t) l * (size_t) ws->chunks_per_lane; ca.counters = b.counters;
+    ca.stage = b.stage; ca.list = b.list_vit; ca.chunk_cnt = ws->chunk_cnt.as<int>() + (size_t) l * (size_t) ws->chunks_per_lane; ca.counters = b.counters;
     ca.nslots = db->nslots; ca.long_slots = vit_long;
     la.cmp = ca;
     WaveSeqArgs a = ws_args(p, dp, db, ctx);
@@ -1353,7 +1304,7 @@ static int cascade_enqueue(CascadeRun &r)
   tick("survivor_args");
   if ((st = upload_args(ws, 0, nq, s)) != P7X_OK) return st;
   tick("upload");
-  P7X_HIP(hipMemsetAsync(ws->counters, 0, ws->counters_bytes(), s));      // lane counters and the arena cursor
+  P7X_HIP(hipMemsetAsync(ws->counters.as<int>(), 0, ws->counters_bytes(), s));      // lane counters and the arena cursor
   ws->ntier_runs = 0;
   if (classes.size() == 1) {
     const bool fills_device = (db->nslots / 64) * (int64_t) nq >= (int64_t) ctx->num_cu * 8;
@@ -1433,7 +1384,7 @@ static int cascade_enqueue(CascadeRun &r)
     if ((st = queue_pack(r, lay, kEarlyPack, nullptr, 2048)) != P7X_OK) return st;
     ws->early_T_cap = kEarlyPack;
   }
-  P7X_HIP(hipMemcpyAsync(ws->h_counts, ws->counters, ws->counters_bytes(), hipMemcpyDeviceToHost, s));
+  P7X_HIP(hipMemcpyAsync(ws->h_counts.as<int>(), ws->counters.as<int>(), ws->counters_bytes(), hipMemcpyDeviceToHost, s));
   P7X_HIP(hipEventRecord(ws->ev_sync, s));
   tick("launches");
   if (debug) std::fprintf(stderr, "[enqueue] nq %d classes %zu:%s ms\n", nq, classes.size(), dbg.c_str());
@@ -1443,7 +1394,7 @@ static int cascade_enqueue(CascadeRun &r)
 // one lane again, after its survivors did not fit the shared buffers
 static int retry_survivor_passes(CascadeRun &r, int l, int nfin)
 {
-  Workspace *ws = r.ws; hipStream_t s = ws->stream;
+  Workspace *ws = r.ws.get(); hipStream_t s = ws->stream;
   int st = fill_survivor_args(r, l, 1, true, nfin);
   if (st != P7X_OK) return st;
   if ((st = upload_args(ws, l, 1, s)) != P7X_OK) return st;
@@ -1451,7 +1402,7 @@ static int retry_survivor_passes(CascadeRun &r, int l, int nfin)
   P7X_HIP(hipMemsetAsync(ws->cursor(), 0, 8, s));
   LaneClass c; c.first = l; c.n = 1; c.C = r.lm[l].dp->vitC;
   if ((st = launch_survivor_passes(r, c, s, true, false)) != P7X_OK) return st;
-  P7X_HIP(hipMemcpyAsync(ws->h_counts, ws->counters, ws->counters_bytes(), hipMemcpyDeviceToHost, s));
+  P7X_HIP(hipMemcpyAsync(ws->h_counts.as<int>(), ws->counters.as<int>(), ws->counters_bytes(), hipMemcpyDeviceToHost, s));
   P7X_HIP(hipEventRecord(ws->ev_sync, s));
   return P7X_OK;
 }
@@ -1459,14 +1410,14 @@ static int retry_survivor_passes(CascadeRun &r, int l, int nfin)
 // download one lane's per-survivor results (queued on the workspace's stream; the caller synchronises)
 static int fetch_lane(CascadeRun &r, int l, bool retry, CascadeOut &out)
 {
-  Workspace *ws = r.ws; hipStream_t s = ws->stream;
+  Workspace *ws = r.ws.get(); hipStream_t s = ws->stream;
   const int nfin = out.counts[4];
   out.fin_slots.resize(nfin); out.fwdsc.resize(nfin); out.xmx_off.resize(nfin);
   if (nfin == 0) return P7X_OK;
   const StageBufs b = ws->lane_bufs(l);
   const int64_t cap = retry ? ws->rt_cap : ws->fin_cap;
-  const int64_t *xmx_off = retry ? ws->rt_xmx_off : ws->xmx_off + (size_t) l * cap;
-  const int32_t *reg_out = retry ? ws->rt_reg_out : ws->reg_out + (size_t) l * cap * (kRegionCap * 3 + 2);
+  const int64_t *xmx_off = retry ? ws->rt_xmx_off.as<int64_t>() : ws->xmx_off.as<int64_t>() + (size_t) l * cap;
+  const int32_t *reg_out = retry ? ws->rt_reg_out.as<int32_t>() : ws->reg_out.as<int32_t>() + (size_t) l * cap * (kRegionCap * 3 + 2);
   out.regs.resize((size_t) nfin * kRegionCap * 3); out.reg_n.resize(nfin); out.nexpected.resize(nfin);
   P7X_HIP(hipMemcpyAsync(out.fin_slots.data(), b.list_fin, (size_t) nfin * 4, hipMemcpyDeviceToHost, s));
   P7X_HIP(hipMemcpyAsync(out.xmx_off.data(), xmx_off, (size_t) nfin * 8, hipMemcpyDeviceToHost, s));
@@ -1481,7 +1432,7 @@ static int fetch_lane(CascadeRun &r, int l, bool retry, CascadeOut &out)
 // after the lane's results have arrived: the parsers' rows when the host has to scan them itself
 static int fetch_lane_rows(CascadeRun &r, CascadeOut &out)
 {
-  const p7x_seqdb *db = r.db; Workspace *ws = r.ws;
+  const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get();
   const int nfin = out.counts[4];
   if (nfin == 0) return P7X_OK;
   bool overflow = r.cfg.host_regions != 0;
@@ -1491,8 +1442,8 @@ static int fetch_lane_rows(CascadeRun &r, CascadeOut &out)
   const int64_t lo = out.xmx_off[0];
   const int64_t hi = out.xmx_off[(size_t) nfin - 1] + (int64_t) (db->h_len[db->h_order[out.fin_slots[(size_t) nfin - 1]]] + 1) * 6;
   out.fwd_xmx.resize((size_t) (hi - lo)); out.bck_xmx.resize((size_t) (hi - lo));
-  P7X_HIP(hipMemcpy(out.fwd_xmx.data(), ws->xmx_f + lo, (size_t) (hi - lo) * 4, hipMemcpyDeviceToHost));
-  P7X_HIP(hipMemcpy(out.bck_xmx.data(), ws->xmx_b + lo, (size_t) (hi - lo) * 4, hipMemcpyDeviceToHost));
+  P7X_HIP(hipMemcpy(out.fwd_xmx.data(), ws->xmx_f.as<float>() + lo, (size_t) (hi - lo) * 4, hipMemcpyDeviceToHost));
+  P7X_HIP(hipMemcpy(out.bck_xmx.data(), ws->xmx_b.as<float>() + lo, (size_t) (hi - lo) * 4, hipMemcpyDeviceToHost));
   for (auto &o : out.xmx_off) o -= lo;
   out.have_xmx = true;
   return P7X_OK;
@@ -1503,36 +1454,26 @@ static int fetch_lane_rows(CascadeRun &r, CascadeOut &out)
 // positions are computed on the device (the enqueue half, which does not know the counts yet), else they are the host's.
 static int queue_pack(CascadeRun &r, const PackLayout &lay, int64_t T, const int32_t *lane_base, int max_nfin)
 {
-  Workspace *ws = r.ws; const p7x_seqdb *db = r.db; hipStream_t s = ws->stream;
+  Workspace *ws = r.ws.get(); const p7x_seqdb *db = r.db; hipStream_t s = ws->stream;
   const int nq = (int) r.oms.size();
   const bool scan_mode = r.cfg.mode == P7X_SCAN_MODELS;
   int st = P7X_OK;
-  if (lay.bytes > ws->pack_dev_bytes) {
-    slab_release(r.ctx, ws->pack_dev, ws->pack_dev_bytes); ws->pack_dev = nullptr; ws->pack_dev_bytes = 0;
-    void *dp = nullptr; size_t got = 0;
-    if ((st = slab_acquire(r.ctx, lay.bytes + lay.bytes / 2, &dp, &got)) != P7X_OK) return st;
-    ws->pack_dev = static_cast<unsigned char *>(dp); ws->pack_dev_bytes = got;
-  }
-  if (lay.bytes > ws->pack_host_bytes) {
-    pinned_release(ws->pack_host, ws->pack_host_bytes); ws->pack_host = nullptr; ws->pack_host_bytes = 0;
-    void *hp = nullptr; size_t got = 0;
-    if ((st = pinned_acquire(lay.bytes + lay.bytes / 2, &hp, &got)) != P7X_OK) return st;
-    ws->pack_host = static_cast<unsigned char *>(hp); ws->pack_host_bytes = got;
-  }
-  unsigned char *ph = ws->pack_host, *pdv = ws->pack_dev;
+  if ((st = ws->pack_dev.reserve(r.ctx, lay.bytes, lay.bytes + lay.bytes / 2)) != P7X_OK) return st;
+  if ((st = ws->pack_host.reserve(lay.bytes, lay.bytes + lay.bytes / 2)) != P7X_OK) return st;
+  unsigned char *ph = ws->pack_host.as<unsigned char>(), *pdv = ws->pack_dev.as<unsigned char>();
   if (T > 0) {
     if (lane_base) {
       std::memcpy(ph + lay.o_base, lane_base, (size_t) nq * 4);
       *reinterpret_cast<int32_t *>(ph + lay.o_cursor) = 0;
       P7X_HIP(hipMemcpyAsync(pdv, ph, lay.o_cursor + 4, hipMemcpyHostToDevice, s));
     } else {
-      hipLaunchKernelGGL(lane_base_kernel, dim3(1), dim3(1024), 0, s, ws->counters, nq, reinterpret_cast<int32_t *>(pdv + lay.o_base),
+      hipLaunchKernelGGL(lane_base_kernel, dim3(1), dim3(1024), 0, s, ws->counters.as<int>(), nq, reinterpret_cast<int32_t *>(pdv + lay.o_base),
                          reinterpret_cast<int *>(pdv + lay.o_cursor));
     }
     PackArgs pa{};
-    pa.list_fin = ws->list_fin; pa.fwd_by_item = ws->fwd_by_item; pa.slot_pitch = ws->cap_slots;
-    pa.xmx_off = ws->xmx_off; pa.reg_out = ws->reg_out; pa.cap = ws->fin_cap;
-    pa.counters = ws->counters; pa.lane_base = reinterpret_cast<const int32_t *>(pdv + lay.o_base);
+    pa.list_fin = ws->list_fin.as<int32_t>(); pa.fwd_by_item = ws->fwd_by_item.as<float>(); pa.slot_pitch = ws->cap_slots;
+    pa.xmx_off = ws->xmx_off.as<int64_t>(); pa.reg_out = ws->reg_out.as<int32_t>(); pa.cap = ws->fin_cap;
+    pa.counters = ws->counters.as<int>(); pa.lane_base = reinterpret_cast<const int32_t *>(pdv + lay.o_base);
     pa.fin = reinterpret_cast<int32_t *>(pdv + lay.o_fin); pa.fwd = reinterpret_cast<float *>(pdv + lay.o_fwd);
     pa.off = reinterpret_cast<int64_t *>(pdv + lay.o_off); pa.regn = reinterpret_cast<int32_t *>(pdv + lay.o_regn);
     pa.nexp = reinterpret_cast<float *>(pdv + lay.o_nexp); pa.reg_start = reinterpret_cast<int32_t *>(pdv + lay.o_start);
@@ -1547,7 +1488,7 @@ static int queue_pack(CascadeRun &r, const PackLayout &lay, int64_t T, const int
     P7X_HIP(hipMemcpyAsync(ph + lay.o_regs, pdv + lay.o_regs, (size_t) lay.regs_cap * 12, hipMemcpyDeviceToHost, s));
   }
   if (scan_mode)           // per-target accounting: which filters every (model, sequence) pair passed
-    P7X_HIP(hipMemcpy2DAsync(ph + lay.o_stage, (size_t) db->nslots, ws->stage, (size_t) ws->cap_slots, (size_t) db->nslots, nq, hipMemcpyDeviceToHost, s));
+    P7X_HIP(hipMemcpy2DAsync(ph + lay.o_stage, (size_t) db->nslots, ws->stage.as<uint8_t>(), (size_t) ws->cap_slots, (size_t) db->nslots, nq, hipMemcpyDeviceToHost, s));
   return P7X_OK;
 }
 
@@ -1556,9 +1497,9 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
   const int nq = (int) r.oms.size();
   outs.assign((size_t) nq, CascadeOut{});
   if (!r.queued || r.collected) return P7X_OK;
-  const p7x_pipeline_cfg &cfg = r.cfg; const p7x_seqdb *db = r.db; Workspace *ws = r.ws;
+  const p7x_pipeline_cfg &cfg = r.cfg; const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get();
   hipStream_t s = ws->stream;
-  struct Release { CascadeRun &r; ~Release() { (void) hipStreamSynchronize(r.ws->stream); release_workspace(r.ws); r.collected = true; } } release{ r };
+  struct Release { CascadeRun &r; ~Release() { sync_and_return(r.ws); r.collected = true; } } release{ r };
   int st = P7X_OK;
   P7X_HIP(hipSetDevice(db->device));                      // the collecting thread may have driven another device since
   const bool debug = debug_opt(OPT_TRACE_FINISH) > 0;
@@ -1570,7 +1511,7 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
   int64_t T = 0; int max_nfin = 0;
   for (int l = 0; l < nq; ++l) {
     CascadeOut &out = outs[(size_t) r.query_of[l]];
-    std::memcpy(out.counts, ws->h_counts + (size_t) l * kLaneCounters, kLaneCounters * 4);
+    std::memcpy(out.counts, ws->h_counts.as<int>() + (size_t) l * kLaneCounters, kLaneCounters * 4);
     lane_base[(size_t) l] = (int32_t) T;
     if (out.counts[12] != 0) flagged.push_back(l);
     else { T += out.counts[4]; max_nfin = std::max(max_nfin, out.counts[4]); }
@@ -1590,7 +1531,7 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
     if ((st = queue_pack(r, lay, T, lane_base.data(), max_nfin)) != P7X_OK) return st;
     P7X_HIP(hipEventRecord(ws->ev_sync, s)); P7X_HIP(hipEventSynchronize(ws->ev_sync));
   }
-  unsigned char *ph = ws->pack_host;
+  unsigned char *ph = ws->pack_host.as<unsigned char>();
   const uint8_t *by_slot = ph + o_stage;
   if (T > 0) {
     const int32_t *h_fin = reinterpret_cast<const int32_t *>(ph + o_fin), *h_regn = reinterpret_cast<const int32_t *>(ph + o_regn);
@@ -1618,7 +1559,7 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
         else {        // the packed array was full: this survivor's regions from the lane's own array
           const size_t at = out.regs.size();
           out.regs.resize(at + (size_t) n * 3);
-          const int32_t *src = ws->reg_out + (size_t) l * (size_t) ws->fin_cap * (kRegionCap * 3 + 2) + (size_t) i * kRegionCap * 3;
+          const int32_t *src = ws->reg_out.as<int32_t>() + (size_t) l * (size_t) ws->fin_cap * (kRegionCap * 3 + 2) + (size_t) i * kRegionCap * 3;
           P7X_HIP(hipMemcpy(out.regs.data() + at, src, (size_t) n * 12, hipMemcpyDeviceToHost));
         }
       }
@@ -1634,7 +1575,7 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
     CascadeOut &out = outs[(size_t) r.query_of[l]];
     if ((st = retry_survivor_passes(r, l, out.counts[4])) != P7X_OK) return st;
     P7X_HIP(hipEventSynchronize(ws->ev_sync));
-    std::memcpy(out.counts, ws->h_counts + (size_t) l * kLaneCounters, kLaneCounters * 4);
+    std::memcpy(out.counts, ws->h_counts.as<int>() + (size_t) l * kLaneCounters, kLaneCounters * 4);
     if (out.counts[12] != 0) { set_error("row buffers could not be sized for the Forward survivors"); return P7X_EMEM; }
     if ((st = fetch_lane(r, l, true, out)) != P7X_OK) return st;
     P7X_HIP(hipEventRecord(ws->ev_sync, s)); P7X_HIP(hipEventSynchronize(ws->ev_sync));
@@ -1716,12 +1657,12 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     if (bias_filtersc) bias_filtersc[t] = 0.0f;
   }
   if (ns == 0) return P7X_OK;
-  Workspace *ws = nullptr;
-  if ((st = get_workspace(db->device, ns, 1, &ws)) != P7X_OK) return st;
-  WorkspaceLease lease{ ws };
+  Lease<Workspace> lease;
+  if ((st = get_workspace(ctx, ns, 1, lease)) != P7X_OK) return st;
+  Workspace *ws = lease.get();
   hipStream_t s = ctx->stream;
   const StageBufs b = ws->lane_bufs(0);
-  LaneArgs &la = ws->h_args[0];
+  LaneArgs &la = ws->h_args.as<LaneArgs>()[0];
   p7x_pipeline_cfg cfg; p7x_pipeline_cfg_default(&cfg);
   {
     DecideArgs d{};
@@ -1739,7 +1680,7 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     }
   }
   if ((st = upload_args(ws, 0, 1, s)) != P7X_OK) return st;
-  P7X_HIP(hipMemsetAsync(ws->counters, 0, ws->counters_bytes(), s));
+  P7X_HIP(hipMemsetAsync(ws->counters.as<int>(), 0, ws->counters_bytes(), s));
   if (xJ) {
     if ((st = class_msv(cls, lm, ctx, ws, s)) != P7X_OK) return st;
     std::vector<int16_t> h((size_t) ns);
@@ -1902,11 +1843,11 @@ int p7x_debug_log_of_float(int device, const float *in, float *out, size_t n)
   if (!in || !out) { set_error("p7x_debug_log_of_float: bad arguments"); return P7X_EINVAL; }
   if (n == 0) return P7X_OK;
   DeviceCtx *ctx = nullptr;
-  const int st = get_ctx(device, &ctx);
+  int st = get_ctx(device, &ctx);
   if (st != P7X_OK) return st;
-  struct Dev { void *p = nullptr; ~Dev() { if (p) (void) hipFree(p); } } b_in, b_out;       // released on every return path
-  P7X_HIP(hipMalloc(&b_in.p, n * 4)); P7X_HIP(hipMalloc(&b_out.p, n * 4));
-  float *d_in = static_cast<float *>(b_in.p), *d_out = static_cast<float *>(b_out.p);
+  DeviceBuf b_in, b_out;
+  if ((st = b_in.reserve(ctx, n * 4)) != P7X_OK || (st = b_out.reserve(ctx, n * 4)) != P7X_OK) return st;
+  float *d_in = b_in.as<float>(), *d_out = b_out.as<float>();
   P7X_HIP(hipMemcpy(d_in, in, n * 4, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(log_of_float_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_in, d_out, n, ctx->lt.logtab);
   P7X_HIP(hipGetLastError());
@@ -1928,7 +1869,7 @@ int p7x_search_batch_raw(const p7x_pipeline_cfg *cfg, const p7x_oprofile *const 
   if (xC) std::fill(xC, xC + nq * (size_t) n, INT32_MIN);
   if (stage) std::fill(stage, stage + nq * (size_t) n, (uint8_t) 0);
   if (!r.queued || ns == 0) return P7X_OK;
-  Workspace *ws = r.ws;
+  Workspace *ws = r.ws.get();
   P7X_HIP(hipStreamSynchronize(ws->stream));          // the batch as the search runs it, kernels chosen per class
   std::vector<int16_t> hj((size_t) ns); std::vector<int32_t> hl((size_t) ns), hc((size_t) ns); std::vector<uint8_t> hs((size_t) ns);
   for (size_t q = 0; q < nq; ++q) {

@@ -1,5 +1,7 @@
 """End-to-end parity of Pipeline.search_hmm / hmmsearch with the reference's golden tables
 (real HMMER output: tests/golden/tables, reference tests/test_hmmer.py:51-238) and with the oracle's cascade."""
+import ctypes as C
+import gc
 import itertools
 import sys
 from pathlib import Path
@@ -8,7 +10,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 import pytest
 
-from conftest import golden_table, synthetic_block
+from conftest import GOLDEN, golden_table, load_hmms, synthetic_block
 from golden_checks import check_domtbl as _check_domtbl, check_tbl as _check_tbl
 from pyhmmer_amd import _lib, easel, errors, hmmer, plan7
 from test_oracle_golden import STAGE_COUNTS
@@ -686,3 +688,84 @@ def test_the_shape_of_a_multi_class_batch_does_not_change_its_results(models, pr
             assert scan() == want_scan, (name, value)
         finally:
             _lib.set_debug_option(name, -1)
+
+
+def _memory_stats():
+    """p7x_debug_memory_stats of device 0, bytes: (device obtained through the slab pool, of that parked, pinned obtained,
+    of that parked)."""
+    out = (C.c_int64 * 4)()
+    assert _lib.lib().p7x_debug_memory_stats(0, out) == 0, _lib.last_error()
+    return tuple(out)
+
+
+def test_memory_pools_are_steady_from_the_second_pass_on(models, proteome):
+    """A batched search, a scan and a long-target search, three times over: the second pass runs on pooled objects that
+    the first one sized, so the third finds every buffer it needs and the pools' four byte counts do not move.  Any
+    difference is a leak, or a buffer that is not taken again."""
+    queries = models["RREFam"] + models["PF02826"] + models["Thioesterase"] + models["KR"] + models["LuxC"]
+    assert len(queries) == 14
+    db = plan7.SequenceDatabase(proteome)
+    few = proteome[:200]
+    dna = load_hmms("bmyD")[0]
+    with easel.SequenceFile(GOLDEN / "seqs" / "BGC0001090.gbk", digital=True, alphabet=dna.alphabet) as f:
+        bgc = f.read_block()
+
+    def one_pass():
+        pli = plan7.Pipeline(proteome.alphabet)
+        batch = plan7.Pipeline._search_finish_batch(pli._search_enqueue_batch(queries, db))
+        scans = list(hmmer.hmmscan(few, queries, devices=[0]))
+        long_hits = plan7.LongTargetsPipeline(dna.alphabet).search_hmm(dna, bgc)
+        assert sum(len(h) for h in batch) > 10 and any(len(h) for h in scans) and len(long_hits) >= 1
+
+    stats = []
+    for _ in range(3):
+        one_pass()
+        gc.collect()
+        stats.append(_memory_stats())
+    print("memory stats after passes 1, 2, 3:", stats)
+    assert stats[2] == stats[1]
+
+
+def test_buffers_grow_while_smaller_ones_sit_in_the_pools(models, proteome):
+    """One profile, then four with the filters switched off (the batch of the retry test above: every target of every
+    lane reaches Backward), then the one again, on one Pipeline: the workspace, the envelope buffers and the ensemble
+    buffers of the second batch are larger than what the first left in the pools, and the third finds the first's again.
+    Every batch gives what separate searches give, and the third obtains no device memory."""
+    bg = plan7.Background(proteome.alphabet)
+    db = plan7.SequenceDatabase(proteome)
+    pli = plan7.Pipeline(proteome.alphabet, F1=1.0, F2=1.0, F3=1.0, bias_filter=False)
+    four = [plan7.OptimizedProfile(h, bg, 400) for h in models["RREFam"][:3] + models["PF02826"]]
+    got, stats = [], []
+    for qs in (four[:1], four, four[:1]):
+        got.append(plan7.Pipeline._search_finish_batch(pli._search_enqueue_batch(qs, db)))
+        stats.append(_memory_stats())
+    want = [pli.search_hmm(q, db) for q in four]
+    for batch, ref in zip(got, (want[:1], want, want[:1])):
+        assert [_hit_fields(a) for a in batch] == [_hit_fields(b) for b in ref]
+    assert sum(len(a) for a in got[1]) > 5
+    print("memory stats after batches 1, 2, 3:", stats)
+    assert stats[2][0] <= stats[1][0]
+
+
+def test_a_failed_ensemble_lease_is_returned(models, proteome):
+    """After a search whose device ensembles failed (seam ens_fail) the next one samples its regions on the device again,
+    on the buffers the failed one had leased: neither obtains any memory.  (A lease that was not returned would make the
+    next search build a new set of ensemble buffers.)"""
+    hmm = models["PF02826"][0]
+    fields = lambda hits: [(h.name, h.score, h.nregions, h.nclustered, h.nenvelopes, [(d.env_from, d.env_to, d.score) for d in h.domains]) for h in hits]
+    want = plan7.Pipeline(hmm.alphabet).search_hmm(hmm, proteome)
+    assert want.guard_counts["ens_device"] > 0           # the fixture has multi-domain regions: the ensembles do run
+    before = _memory_stats()
+    _lib.set_debug_option("ens_fail", 1)
+    try:
+        failed = plan7.Pipeline(hmm.alphabet).search_hmm(hmm, proteome)
+    finally:
+        _lib.set_debug_option("ens_fail", -1)
+    after = _memory_stats()
+    again = plan7.Pipeline(hmm.alphabet).search_hmm(hmm, proteome)
+    last = _memory_stats()
+    print("memory stats before the failed search, after it, after the next:", before, after, last)
+    assert failed.guard_counts["ens_device"] == 0 and again.guard_counts["ens_device"] == want.guard_counts["ens_device"]
+    assert fields(failed) == fields(want) and fields(again) == fields(want)
+    assert (after[0], after[2]) == (before[0], before[2])
+    assert (last[0], last[2]) == (before[0], before[2])
