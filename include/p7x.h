@@ -415,6 +415,7 @@ void     p7x_tophits_destroy(p7x_tophits *th);
 void     p7x_tophits_destroy_many(p7x_tophits **th, size_t n);
 p7x_tophits *p7x_tophits_clone(const p7x_tophits *th);   /* TopHits.copy, plan7.pyx:9150-9170 */
 int64_t  p7x_tophits_nhits(const p7x_tophits *th);
+int      p7x_tophits_abc_type(const p7x_tophits *th);     /* alphabet of the query (P7X_AMINO / _DNA / _RNA); 0: not known (the lists of a scan) */
 int      p7x_tophits_get_counters(const p7x_tophits *th, p7x_counters *c);
 int      p7x_tophits_get_cfg(const p7x_tophits *th, p7x_pipeline_cfg *cfg);   /* Z/domZ as finally set */
 int      p7x_tophits_get_hit(const p7x_tophits *th, int64_t i, p7x_hit *hit);
@@ -497,7 +498,8 @@ int     p7x_msa_from_traces(int32_t M, size_t n, const int8_t *st, const int32_t
                             const int32_t *lengths, int32_t abc_type, const char *cs, int flags, const p7x_oprofile *om,
                             p7x_msa **out);
 int64_t p7x_msa_alen(const p7x_msa *msa);
-/* which: 0 row idx, 1 its PP line ("" when none), 2 PP_cons, 3 RF, 4 SS_cons ("" when none): copies at most cap-1
+/* which: 0 row idx, 1 its PP line ("" when none), 2 PP_cons, 3 RF, 4 SS_cons ("" when none); 5 - 8: see
+ * p7x_tophits_to_msa ("" for an alignment made by p7x_msa_from_traces): copies at most cap-1
  * characters and returns the full length, -1 on bad arguments (MSA.alignment / TextMSA, easel.pyx MSA 5790-6400) */
 int64_t p7x_msa_get(const p7x_msa *msa, int64_t idx, int which, char *buf, size_t cap);
 void    p7x_msa_destroy(p7x_msa *msa);
@@ -509,6 +511,45 @@ void    p7x_msa_destroy(p7x_msa *msa);
 int64_t p7x_msa_write_stockholm(size_t n, int64_t alen, const char *const *names, const char *const *accs,
                                 const char *const *descs, const char *const *aseqs, const char *const *pps,
                                 const char *ss_cons, const char *pp_cons, const char *rf, char *buf, size_t cap);
+
+/* p7_alidisplay_Backconvert (upstream p7_alidisplay.c): the alignment display of one domain -- model line, sequence line,
+ * posterior line (or NULL), hmmfrom..hmmto, sqfrom..sqto, target length L -- back to a trace in the arrays
+ * p7x_msa_from_traces takes, filled as p7_trace_AppendWithPP fills them (i and pp 0 where nothing is emitted; a PP character
+ * decoded as p7_alidisplay_DecodePostProb: '*' 1.0, '.' 0, a digit d d/10, the middle of the values printed as d), and to the digital residues of the aligned
+ * subsequence (the display's own text without its gaps).
+ *   whole = 0: upstream's faux trace of the SUBSEQUENCE, S N B <one M / D / I per column> E C T, residues numbered from 1
+ *     (N = columns + 6, the trace's L is the subsequence's length); what p7_tophits_Alignment aligns.  sqfrom > sqto (the
+ *     reverse strand of a long target) is fine: nothing but the text is read.
+ *   whole = 1 (an extension): the trace of the whole TARGET the display was cut from: N emits residues 1..sqfrom-1 and C
+ *     residues sqto+1..L (posterior 1.0), the core steps carry the target's own coordinates.  Needs sqfrom <= sqto.
+ * *N / *subL receive the number of steps and of residues; st / k / i / pp (N entries) and dsq (subL) are written when cap
+ * holds them, cap >= N (N <= columns + 6 + L).  P7X_EINVAL when the display is not one (a character outside the alphabet,
+ * lines of different lengths, coordinates that do not match the columns). */
+int     p7x_alidisplay_backconvert(int32_t abc_type, const char *model, const char *aseq, const char *ppline, int32_t hmmfrom,
+                                   int32_t hmmto, int64_t sqfrom, int64_t sqto, int64_t L, int whole, int32_t *N, int32_t *subL,
+                                   int8_t *st, int32_t *k, int32_t *i, float *pp, uint8_t *dsq, size_t cap);
+/* The alignment of the included domains of a hit list (TopHits.to_msa, plan7.pyx:8966-9069; upstream p7_tophits_Alignment):
+ * first the nextra sequences the caller brings with their traces (as for p7x_msa_from_traces; names / accessions /
+ * descriptions may be NULL), then, for every hit with P7X_IS_INCLUDED in the list's current order, one row per domain with
+ * is_included: the back-converted display (whole = 0), named "<target>/<sqfrom>-<sqto>", with the target's accession and the
+ * description "[subseq from] <description, or name>".  M <= 0: the model length the hits carry.  The rows go through
+ * p7x_msa_from_traces (flags: P7X_MSA_*; no model annotation, so RF marks the consensus columns and there is no SS_cons);
+ * p7x_msa_get gives them back, with which = 5 / 6 / 7 the name / accession / description of row idx and 8 the name of the
+ * alignment (the query's).  P7X_EINVAL: nothing to align (no included domain and no extra sequence), the per-sequence lists
+ * of a scan, an alphabet other than the hits', an M other than theirs. */
+int     p7x_tophits_to_msa(const p7x_tophits *th, int32_t abc_type, int32_t M, size_t nextra, const int8_t *st, const int32_t *k,
+                           const int32_t *i, const float *pp, const int64_t *toff, const uint8_t *origin, const uint8_t *dsq,
+                           const int64_t *offsets, const int32_t *lengths, const char *const *names, const char *const *accs,
+                           const char *const *descs, int flags, p7x_msa **out);
+/* Test seams of the two (host code, no device).  from_displays: a hit list of one query (name, alphabet, M) made of the given
+ * alignment displays -- hit h has ndom[h] domains, doms in hit order; of a p7x_domain the display fields, is_included and
+ * is_reported are read -- with hit flags as given, in the given order.  from_trace: the display p7_alidisplay_Create makes
+ * of the first domain of a trace over dsq1[1..L], as the one domain of a one-hit list named <name>. */
+int     p7x_debug_tophits_from_displays(const char *qname, int32_t abc_type, int32_t M, size_t nhits, const char *const *names,
+                                        const char *const *accs, const char *const *descs, const uint32_t *flags,
+                                        const int32_t *ndom, const p7x_domain *doms, p7x_tophits **out);
+int     p7x_debug_tophits_from_trace(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t N, const int8_t *st,
+                                     const int32_t *k, const int32_t *i, const float *pp, const char *name, p7x_tophits **out);
 
 const char *p7x_last_error(void);
 

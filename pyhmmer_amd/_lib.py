@@ -208,6 +208,7 @@ _SIGNATURES = {
     "p7x_tophits_destroy_many": (None, [_VP, C.c_size_t]),
     "p7x_tophits_clone": (_VP, [_VP]),
     "p7x_tophits_nhits": (C.c_int64, [_VP]),
+    "p7x_tophits_abc_type": (C.c_int, [_VP]),
     "p7x_tophits_get_counters": (C.c_int, [_VP, C.POINTER(Counters)]),
     "p7x_tophits_get_cfg": (C.c_int, [_VP, C.POINTER(PipelineCfg)]),
     "p7x_tophits_get_hit": (C.c_int, [_VP, C.c_int64, C.POINTER(HitRec)]),
@@ -275,6 +276,15 @@ _SIGNATURES = {
     "p7x_msa_write_stockholm": (C.c_int64, [C.c_size_t, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                             C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_char_p,
                                             C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "p7x_alidisplay_backconvert": (C.c_int, [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _VP, _VP, _VP, _VP, _VP,
+                                             C.c_size_t]),
+    "p7x_tophits_to_msa": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int, C.POINTER(_VP)]),
+    "p7x_debug_tophits_from_displays": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_char_p),
+                                                  C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_int32), C.POINTER(DomainRec), C.POINTER(_VP)]),
+    "p7x_debug_tophits_from_trace": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_char_p, C.POINTER(_VP)]),
     "p7x_last_error": (C.c_char_p, []),
 }
 

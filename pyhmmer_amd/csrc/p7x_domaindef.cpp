@@ -1667,3 +1667,38 @@ extern "C" int p7x_debug_parser_rows(const p7x_oprofile *om, const uint8_t *dsq1
   std::memcpy(bx, b.data(), b.size() * sizeof(float));
   return P7X_OK;
 }
+
+// Test seam of p7x_alidisplay_backconvert: the display make_alidisplay renders of a trace's first domain over dsq1[1..L], as the
+// one domain of a one-hit list (which owns the strings)
+extern "C" int p7x_debug_tophits_from_trace(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t N, const int8_t *st,
+                                            const int32_t *k, const int32_t *i, const float *pp, const char *name, p7x_tophits **out)
+{
+  using namespace p7x;
+  if (!om || !dsq1 || L < 1 || N < 3 || !st || !k || !i || !out) { set_error("p7x_debug_tophits_from_trace: bad arguments"); return P7X_EINVAL; }
+  *out = nullptr;
+  const Profile &p = om->p;
+  Trace tr;
+  int zb = -1, ze = -1;
+  for (int z = 0; z < N; ++z) {
+    const bool core = st[z] == sM || st[z] == sD || st[z] == sI, emits = st[z] == sM || st[z] == sI;
+    if ((core && (k[z] < 1 || k[z] > p.M)) || (emits && (i[z] < 1 || i[z] > L || dsq1[i[z]] >= p.Kp))) { set_error("p7x_debug_tophits_from_trace: trace out of range"); return P7X_EINVAL; }
+    if (st[z] == sB && zb < 0) zb = z;
+    if (st[z] == sE && zb >= 0 && ze < 0) ze = z;
+    tr.st.push_back(st[z]); tr.k.push_back(k[z]); tr.i.push_back(i[z]); tr.pp.push_back(pp ? pp[z] : 0.0f);
+  }
+  if (zb < 0 || ze < zb + 2) { set_error("p7x_debug_tophits_from_trace: the trace has no domain"); return P7X_EINVAL; }
+  for (int z = zb + 1; z < ze; ++z)
+    if (st[z] != sM && st[z] != sD && st[z] != sI) { set_error("p7x_debug_tophits_from_trace: the trace has no domain"); return P7X_EINVAL; }
+  auto th = std::make_unique<p7x_tophits>();
+  p7x_pipeline_cfg_default(&th->cfg);
+  th->qname = p.name; th->qacc = p.acc; th->qdesc = p.desc; th->q_has_acc = p.has_acc; th->q_has_desc = p.has_desc;
+  th->M = p.M; th->abc_type = p.abc_type;
+  Hit hit;
+  hit.name = name ? name : "";
+  hit.ndom = 1;
+  hit.dcl.resize(1);
+  make_alidisplay(p, tr, dsq1, L, hit.dcl[0]);
+  th->hits.push_back(std::move(hit));
+  *out = th.release();
+  return P7X_OK;
+}

@@ -234,6 +234,7 @@ struct p7x_tophits {
   std::string qname, qacc, qdesc;     // the query (model) the alignment displays refer to
   bool q_has_acc = false, q_has_desc = false;
   int M = 0;
+  int abc_type = 0;                   // alphabet of the query (P7X_AMINO / _DNA / _RNA; 0: not known), for TopHits.to_msa
   static constexpr int kMs = 20;
   double ms[kMs]{};           // see TopHits.timings_ms (plan7.py) for the slots
   bool sorted_by_key = false;

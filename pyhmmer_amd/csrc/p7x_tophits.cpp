@@ -289,7 +289,7 @@ int host_finish_batch(const p7x_pipeline_cfg &cfg_in, const std::vector<FinishIt
     th->cfg = cfg_in;
     apply_bit_cutoffs(th->cfg, p);
     th->qname = p.name; th->qacc = p.acc; th->qdesc = p.desc; th->q_has_acc = p.has_acc; th->q_has_desc = p.has_desc;
-    th->M = p.M;
+    th->M = p.M; th->abc_type = p.abc_type;
     th->ctr.nmodels = 1; th->ctr.nnodes = (uint64_t) p.M;
     th->ctr.nseqs = (uint64_t) tg.n; th->ctr.nres = (uint64_t) tg.nres;
     th->ctr.n_past_msv = it.counts[0]; th->ctr.n_past_bias = it.counts[1];
@@ -614,6 +614,7 @@ void p7x_tophits_destroy(p7x_tophits *th) { delete th; }
 void p7x_tophits_destroy_many(p7x_tophits **th, size_t n) { if (th) for (size_t i = 0; i < n; ++i) { delete th[i]; th[i] = nullptr; } }
 p7x_tophits *p7x_tophits_clone(const p7x_tophits *th) { return th ? new p7x_tophits(*th) : nullptr; }
 int64_t p7x_tophits_nhits(const p7x_tophits *th) { return th ? (int64_t) th->hits.size() : -1; }
+int p7x_tophits_abc_type(const p7x_tophits *th) { return th ? th->abc_type : 0; }
 
 int p7x_tophits_get_counters(const p7x_tophits *th, p7x_counters *c)
 {
@@ -803,6 +804,47 @@ int p7x_debug_tophits_set_stages(p7x_tophits *th, const uint8_t *stage, size_t n
 {
   if (!th || (n && !stage)) { set_error("p7x_debug_tophits_set_stages: bad arguments"); return P7X_EINVAL; }
   th->stage.assign(stage, stage + n);
+  return P7X_OK;
+}
+
+// Test seam of TopHits.to_msa: a hit list made of hand-written alignment displays
+int p7x_debug_tophits_from_displays(const char *qname, int32_t abc_type, int32_t M, size_t nhits, const char *const *names,
+                                    const char *const *accs, const char *const *descs, const uint32_t *flags, const int32_t *ndom,
+                                    const p7x_domain *doms, p7x_tophits **out)
+{
+  if (!qname || !out || M < 1 || (nhits && (!names || !flags || !ndom || !doms))) { set_error("p7x_debug_tophits_from_displays: bad arguments"); return P7X_EINVAL; }
+  *out = nullptr;
+  auto th = std::make_unique<p7x_tophits>();
+  p7x_pipeline_cfg_default(&th->cfg);
+  th->qname = qname; th->M = M; th->abc_type = abc_type;
+  th->ctr.nmodels = 1; th->ctr.nnodes = (uint64_t) M;
+  size_t at = 0;
+  for (size_t h = 0; h < nhits; ++h) {
+    if (!names[h] || ndom[h] < 0) { set_error("p7x_debug_tophits_from_displays: bad arguments"); return P7X_EINVAL; }
+    Hit hit;
+    hit.name = names[h];
+    if (accs && accs[h] && accs[h][0]) { hit.acc = accs[h]; hit.has_acc = true; }
+    if (descs && descs[h] && descs[h][0]) { hit.desc = descs[h]; hit.has_desc = true; }
+    hit.seqidx = (int64_t) h; hit.flags = flags[h]; hit.ndom = ndom[h];
+    for (int d = 0; d < ndom[h]; ++d, ++at) {
+      const p7x_domain &s = doms[at];
+      if (!s.model || !s.aseq) { set_error("p7x_debug_tophits_from_displays: a display without model or sequence line"); return P7X_EINVAL; }
+      Domain dom;
+      dom.is_reported = s.is_reported != 0; dom.is_included = s.is_included != 0;
+      dom.model = s.model; dom.aseq = s.aseq;
+      dom.mline = s.mline ? s.mline : std::string(dom.model.size(), ' ');
+      if (s.ppline) dom.ppline = s.ppline;
+      dom.N = (int) dom.model.size(); dom.hmmfrom = s.hmmfrom; dom.hmmto = s.hmmto; dom.M = M;
+      dom.sqfrom = s.sqfrom; dom.sqto = s.sqto; dom.L = s.L;
+      dom.ienv = dom.iali = s.sqfrom; dom.jenv = dom.jali = s.sqto;
+      hit.nreported += dom.is_reported; hit.nincluded += dom.is_included;
+      hit.dcl.push_back(std::move(dom));
+    }
+    th->nreported += (hit.flags & P7X_IS_REPORTED) ? 1 : 0; th->nincluded += (hit.flags & P7X_IS_INCLUDED) ? 1 : 0;
+    th->hits.push_back(std::move(hit));
+  }
+  th->ctr.nseqs = nhits;
+  *out = th.release();
   return P7X_OK;
 }
 
@@ -1006,7 +1048,8 @@ struct Reader {
   template <class T> void pod(T &v) { if (p + sizeof(T) > e) { ok = false; return; } std::memcpy(&v, p, sizeof(T)); p += sizeof(T); }
   void str(std::string &s) { uint32_t n = 0; pod(n); if (!ok || p + n > e) { ok = false; return; } s.assign((const char *) p, n); p += n; }
 };
-constexpr uint32_t kMagic = 0x70377879u;   // "p7xy" (format 6: the ABI version and the size of the configuration record follow the magic)
+constexpr uint32_t kMagic = 0x7037787au;   // "p7xz" (format 7: the ABI version and the size of the configuration record follow the magic; the
+                                           // query's alphabet follows its model length)
 
 template <class IO> void io_domain(IO &io, Domain &d)
 {
@@ -1035,7 +1078,7 @@ int64_t p7x_tophits_serialize(const p7x_tophits *th, void *buf, size_t cap)
   // TopHits, a rank running an older library) is rejected, not mis-parsed
   uint32_t abi = (uint32_t) P7X_ABI_VERSION, cfg_bytes = (uint32_t) sizeof(p7x_pipeline_cfg); w.pod(abi); w.pod(cfg_bytes);
   w.pod(th->cfg); w.pod(th->ctr);
-  w.str(th->qname); w.str(th->qacc); w.str(th->qdesc); w.pod(th->q_has_acc); w.pod(th->q_has_desc); w.pod(th->M); w.pod(th->scan_collected);
+  w.str(th->qname); w.str(th->qacc); w.str(th->qdesc); w.pod(th->q_has_acc); w.pod(th->q_has_desc); w.pod(th->M); w.pod(th->abc_type); w.pod(th->scan_collected);
   for (int i = 0; i < p7x_tophits::kMs; ++i) w.pod(th->ms[i]);
   const uint64_t n = th->hits.size(); w.pod(n);
   for (const Hit &hc : th->hits) {
@@ -1064,7 +1107,7 @@ p7x_tophits *p7x_tophits_deserialize(const void *buf, size_t n)
   }
   auto th = std::make_unique<p7x_tophits>();
   r.pod(th->cfg); r.pod(th->ctr);
-  r.str(th->qname); r.str(th->qacc); r.str(th->qdesc); r.pod(th->q_has_acc); r.pod(th->q_has_desc); r.pod(th->M); r.pod(th->scan_collected);
+  r.str(th->qname); r.str(th->qacc); r.str(th->qdesc); r.pod(th->q_has_acc); r.pod(th->q_has_desc); r.pod(th->M); r.pod(th->abc_type); r.pod(th->scan_collected);
   for (int i = 0; i < p7x_tophits::kMs; ++i) r.pod(th->ms[i]);
   uint64_t nh = 0; r.pod(nh);
   if (!r.ok) { set_error("truncated serialised TopHits"); return nullptr; }

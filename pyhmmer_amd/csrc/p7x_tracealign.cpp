@@ -32,6 +32,8 @@ struct p7x_msa {
   int64_t alen = 0;
   std::vector<std::string> aseq, pp;   // pp[idx] empty: that row has no posterior annotation
   std::string pp_cons, rf, ss_cons;
+  std::vector<std::string> name, acc, desc;   // per row; filled by p7x_tophits_to_msa only
+  std::string msa_name;
 };
 
 namespace {
@@ -74,6 +76,87 @@ int report_host_error(int st, int64_t idx, int L)
     std::snprintf(buf, sizeof buf, "hmmalign: the optimal-accuracy traceback failed on sequence %lld (L = %d)", (long long) idx, L);
   set_error(buf);
   return st;
+}
+
+// esl_abc_DigitizeSymbol over the input map Easel builds for the alphabet: both letter cases, '_' and '.' for the gap, and
+// the nucleic synonyms (T / U for each other, X for N, I for A); 255 = not a symbol
+struct InputMap {
+  uint8_t code[256];
+  explicit InputMap(int abc_type)
+  {
+    const Alphabet &abc = Alphabet::get(abc_type);
+    std::memset(code, 255, sizeof code);
+    for (int x = 0; x < abc.Kp; ++x) {
+      code[(unsigned char) abc.sym[x]] = (uint8_t) x;
+      code[(unsigned char) std::tolower((unsigned char) abc.sym[x])] = (uint8_t) x;
+    }
+    auto equiv = [&](char c, char to) { code[(unsigned char) c] = code[(unsigned char) std::tolower((unsigned char) c)] = code[(unsigned char) to]; };
+    equiv('_', '-'); equiv('.', '-');
+    if (abc_type != P7X_AMINO) { equiv(abc_type == P7X_RNA ? 'T' : 'U', abc_type == P7X_RNA ? 'U' : 'T'); equiv('X', 'N'); equiv('I', 'A'); }
+  }
+  static const InputMap &get(int abc_type)
+  {
+    static const InputMap amino(P7X_AMINO), dna(P7X_DNA), rna(P7X_RNA);
+    return abc_type == P7X_AMINO ? amino : (abc_type == P7X_RNA ? rna : dna);
+  }
+};
+
+float decode_pp(char c)       // p7_alidisplay_DecodePostProb
+{
+  if (c == '*') return 1.0f;
+  if (c == '.') return 0.0f;
+  return (float) ((float) (c - '0') / 10.);
+}
+
+// p7_alidisplay_Backconvert (see include/p7x.h); steps as p7_trace_AppendWithPP stores them
+int backconvert(int abc_type, const char *model, const char *aseq, const char *ppline, int hmmfrom, int hmmto, int64_t sqfrom, int64_t sqto,
+                int64_t L, bool whole, std::vector<int8_t> &st, std::vector<int32_t> &tk, std::vector<int32_t> &ti, std::vector<float> &tpp,
+                std::vector<uint8_t> &dsq)
+{
+  enum { tM = 1, tD = 2, tI = 3, tS = 4, tN = 5, tB = 6, tE = 7, tC = 8, tT = 9 };
+  const Alphabet &abc = Alphabet::get(abc_type);
+  const InputMap &in = InputMap::get(abc_type);
+  const size_t n = std::strlen(model);
+  if (n == 0 || std::strlen(aseq) != n || (ppline && std::strlen(ppline) != n)) { set_error("back-conversion: the lines of the alignment display differ in length"); return P7X_EINVAL; }
+  auto is_residue = [&](uint8_t x) { return x < abc.K || (x > abc.K && x < abc.Kp - 2); };
+  st.clear(); tk.clear(); ti.clear(); tpp.clear(); dsq.clear();
+  auto append = [&](int s, int k, int64_t i, float p) { st.push_back((int8_t) s); tk.push_back(k); ti.push_back((int32_t) i); tpp.push_back(p); };
+  if (whole && !(sqfrom >= 1 && sqfrom <= sqto && sqto <= L && L <= INT32_MAX)) {
+    set_error("back-conversion to a trace of the whole target needs 1 <= sqfrom <= sqto <= L"); return P7X_EINVAL;
+  }
+  const int64_t shift = whole ? sqfrom - 1 : 0;
+  append(tS, 0, 0, 0.0f);
+  append(tN, 0, 0, 0.0f);
+  for (int64_t r = 1; r <= shift; ++r) append(tN, 0, r, 1.0f);
+  append(tB, 0, 0, 0.0f);
+  int k = hmmfrom;
+  int64_t i = 1;
+  for (size_t a = 0; a < n; ++a) {
+    const uint8_t xm = in.code[(unsigned char) model[a]], xa = in.code[(unsigned char) aseq[a]];
+    if (xm == 255 || xa == 255) {
+      set_error(std::string("back-conversion: '") + (xm == 255 ? model[a] : aseq[a]) + "' in column " + std::to_string(a + 1) + " is not a symbol of the alphabet");
+      return P7X_EINVAL;
+    }
+    if (ppline && ppline[a] != '*' && ppline[a] != '.' && !std::isdigit((unsigned char) ppline[a])) { set_error("back-conversion: the posterior line holds something else than digits, '*' and '.'"); return P7X_EINVAL; }
+    const int cur = is_residue(xm) ? (is_residue(xa) ? tM : tD) : tI;
+    const float p = ppline ? decode_pp(ppline[a]) : 0.0f;
+    switch (cur) {
+      case tM: append(tM, k, i + shift, p); dsq.push_back(xa); k++; i++; break;
+      case tI:
+        if (xa == abc.K) { set_error("back-conversion: column " + std::to_string(a + 1) + " of the display has neither a model position nor a residue"); return P7X_EINVAL; }
+        append(tI, k - 1, i + shift, p); dsq.push_back(xa); i++; break;     // the insert state of the node before it (k is the next node's)
+      default: append(tD, k, 0, 0.0f); k++; break;
+    }
+  }
+  append(tE, 0, 0, 0.0f);
+  append(tC, 0, 0, 0.0f);
+  if (whole) for (int64_t r = sqto + 1; r <= L; ++r) append(tC, 0, r, 1.0f);
+  append(tT, 0, 0, 0.0f);
+  size_t nres = 0;                                   // upstream's first pass: what is not a gap is a residue of the subsequence
+  for (size_t a = 0; a < n; ++a) nres += in.code[(unsigned char) aseq[a]] != abc.K ? 1 : 0;
+  if (k != hmmto + 1 || (size_t) (i - 1) != nres) { set_error("back-conversion: the display's coordinates do not match its columns"); return P7X_EINVAL; }
+  if (whole && sqto - sqfrom + 1 != (int64_t) nres) { set_error("back-conversion: sqfrom..sqto does not span the display's residues"); return P7X_EINVAL; }
+  return P7X_OK;
 }
 
 struct SeqdbDeleter { void operator()(p7x_seqdb *db) const { p7x_seqdb_destroy(db); } };
@@ -401,6 +484,14 @@ int64_t p7x_msa_get(const p7x_msa *msa, int64_t idx, int which, char *buf, size_
     case 2: s = &msa->pp_cons; break;
     case 3: s = &msa->rf; break;
     case 4: s = &msa->ss_cons; break;
+    case 5: case 6: case 7: {
+      static const std::string none;
+      const std::vector<std::string> &v = which == 5 ? msa->name : (which == 6 ? msa->acc : msa->desc);
+      if (idx < 0 || idx >= (int64_t) msa->aseq.size()) return -1;
+      s = (size_t) idx < v.size() ? &v[(size_t) idx] : &none;
+      break;
+    }
+    case 8: s = &msa->msa_name; break;
     default: return -1;
   }
   if (buf && cap > 0) { const size_t m = std::min(cap - 1, s->size()); std::memcpy(buf, s->data(), m); buf[m] = '\0'; }
@@ -408,6 +499,97 @@ int64_t p7x_msa_get(const p7x_msa *msa, int64_t idx, int which, char *buf, size_
 }
 
 void p7x_msa_destroy(p7x_msa *msa) { delete msa; }
+
+// p7_alidisplay_Backconvert
+int p7x_alidisplay_backconvert(int32_t abc_type, const char *model, const char *aseq, const char *ppline, int32_t hmmfrom, int32_t hmmto,
+                               int64_t sqfrom, int64_t sqto, int64_t L, int whole, int32_t *N, int32_t *subL, int8_t *st, int32_t *k,
+                               int32_t *i, float *pp, uint8_t *dsq, size_t cap)
+{
+  if (!model || !aseq || !N || !subL || (abc_type != P7X_AMINO && abc_type != P7X_DNA && abc_type != P7X_RNA)) {
+    set_error("p7x_alidisplay_backconvert: bad arguments"); return P7X_EINVAL;
+  }
+  std::vector<int8_t> vst; std::vector<int32_t> vk, vi; std::vector<float> vpp; std::vector<uint8_t> vdsq;
+  const int rc = backconvert(abc_type, model, aseq, ppline, hmmfrom, hmmto, sqfrom, sqto, L, whole != 0, vst, vk, vi, vpp, vdsq);
+  if (rc != P7X_OK) return rc;
+  *N = (int32_t) vst.size(); *subL = (int32_t) vdsq.size();
+  if (cap >= vst.size()) {
+    if (st) std::memcpy(st, vst.data(), vst.size());
+    if (k) std::copy(vk.begin(), vk.end(), k);
+    if (i) std::copy(vi.begin(), vi.end(), i);
+    if (pp) std::copy(vpp.begin(), vpp.end(), pp);
+    if (dsq) std::copy(vdsq.begin(), vdsq.end(), dsq);
+  }
+  return P7X_OK;
+}
+
+// p7_tophits_Alignment
+int p7x_tophits_to_msa(const p7x_tophits *th, int32_t abc_type, int32_t M, size_t nextra, const int8_t *xst, const int32_t *xk,
+                       const int32_t *xi, const float *xpp, const int64_t *xtoff, const uint8_t *xorigin, const uint8_t *xdsq,
+                       const int64_t *xoffsets, const int32_t *xlengths, const char *const *xnames, const char *const *xaccs,
+                       const char *const *xdescs, int flags, p7x_msa **out)
+{
+  if (!th || !out || (nextra && (!xst || !xk || !xi || !xtoff || !xorigin || !xdsq || !xoffsets || !xlengths)) ||
+      (abc_type != P7X_AMINO && abc_type != P7X_DNA && abc_type != P7X_RNA)) {
+    set_error("p7x_tophits_to_msa: bad arguments"); return P7X_EINVAL;
+  }
+  *out = nullptr;
+  if (th->cfg.mode == P7X_SCAN_MODELS && th->scan_collected) { set_error("p7x_tophits_to_msa: the hits of a scan belong to different models"); return P7X_EINVAL; }
+  if (th->abc_type != 0 && th->abc_type != abc_type) { set_error("p7x_tophits_to_msa: alphabet mismatch with the hits' alphabet"); return P7X_EINVAL; }
+  if (M <= 0) M = th->M;
+  if (M < 1 || (th->M > 0 && M != th->M && !th->hits.empty())) { set_error("p7x_tophits_to_msa: the model length of the traces is not the hits'"); return P7X_EINVAL; }
+  // the rows: the caller's first, then the included domains of the included hits in the list's order
+  std::vector<int8_t> st; std::vector<int32_t> tk, ti; std::vector<float> tpp;
+  std::vector<int64_t> toff{ 0 }, offsets;
+  std::vector<int32_t> lengths;
+  std::vector<uint8_t> origin, dsq{ 255 };
+  auto msa_rows = std::make_unique<p7x_msa>();          // carries the row texts until the alignment exists
+  for (size_t y = 0; y < nextra; ++y) {
+    if (xtoff[y + 1] < xtoff[y] || xlengths[y] < 0) { set_error("p7x_tophits_to_msa: bad arguments"); return P7X_EINVAL; }
+    st.insert(st.end(), xst + xtoff[y], xst + xtoff[y + 1]);
+    tk.insert(tk.end(), xk + xtoff[y], xk + xtoff[y + 1]);
+    ti.insert(ti.end(), xi + xtoff[y], xi + xtoff[y + 1]);
+    if (xpp) tpp.insert(tpp.end(), xpp + xtoff[y], xpp + xtoff[y + 1]); else tpp.insert(tpp.end(), (size_t) (xtoff[y + 1] - xtoff[y]), 0.0f);
+    toff.push_back((int64_t) st.size());
+    origin.push_back((uint8_t) (xpp ? (xorigin[y] & P7X_TRACE_HAS_PP) : 0));     // no host-twin averaging: there is no profile here
+    offsets.push_back((int64_t) dsq.size()); lengths.push_back(xlengths[y]);
+    dsq.insert(dsq.end(), xdsq + xoffsets[y], xdsq + xoffsets[y] + xlengths[y]);
+    dsq.push_back(255);
+    msa_rows->name.emplace_back(xnames && xnames[y] ? xnames[y] : "");
+    msa_rows->acc.emplace_back(xaccs && xaccs[y] ? xaccs[y] : "");
+    msa_rows->desc.emplace_back(xdescs && xdescs[y] ? xdescs[y] : "");
+  }
+  std::vector<int8_t> vst; std::vector<int32_t> vk, vi; std::vector<float> vpp; std::vector<uint8_t> vdsq;
+  for (size_t r = 0; r < th->hits.size(); ++r) {
+    const Hit &h = th->hits[th->order.size() == th->hits.size() ? (size_t) th->order[r] : r];
+    if (!(h.flags & P7X_IS_INCLUDED)) continue;
+    for (const Domain &d : h.dcl) {
+      if (!d.is_included) continue;
+      const int rc = backconvert(abc_type, d.model.c_str(), d.aseq.c_str(), d.ppline.empty() ? nullptr : d.ppline.c_str(), d.hmmfrom, d.hmmto,
+                                 d.sqfrom, d.sqto, d.L, false, vst, vk, vi, vpp, vdsq);
+      if (rc != P7X_OK) { set_error(std::string(p7x_last_error()) + " (" + h.name + ")"); return rc; }
+      st.insert(st.end(), vst.begin(), vst.end()); tk.insert(tk.end(), vk.begin(), vk.end());
+      ti.insert(ti.end(), vi.begin(), vi.end()); tpp.insert(tpp.end(), vpp.begin(), vpp.end());
+      toff.push_back((int64_t) st.size());
+      origin.push_back((uint8_t) (d.ppline.empty() ? 0 : P7X_TRACE_HAS_PP));
+      offsets.push_back((int64_t) dsq.size()); lengths.push_back((int32_t) vdsq.size());
+      dsq.insert(dsq.end(), vdsq.begin(), vdsq.end());
+      dsq.push_back(255);
+      msa_rows->name.push_back(h.name + "/" + std::to_string(d.sqfrom) + "-" + std::to_string(d.sqto));
+      msa_rows->acc.push_back(h.has_acc ? h.acc : std::string());
+      msa_rows->desc.push_back("[subseq from] " + (h.has_desc && !h.desc.empty() ? h.desc : h.name));
+    }
+  }
+  const size_t n = lengths.size();
+  if (n == 0) { set_error("No included domains found"); return P7X_EINVAL; }
+  p7x_msa *msa = nullptr;
+  const int rc = p7x_msa_from_traces(M, n, st.data(), tk.data(), ti.data(), tpp.data(), toff.data(), origin.data(), dsq.data(), offsets.data(),
+                                     lengths.data(), abc_type, nullptr, flags, nullptr, &msa);
+  if (rc != P7X_OK) return rc;
+  msa->name = std::move(msa_rows->name); msa->acc = std::move(msa_rows->acc); msa->desc = std::move(msa_rows->desc);
+  msa->msa_name = th->qname;
+  *out = msa;
+  return P7X_OK;
+}
 
 // esl_msafile_stockholm.c stockholm_write, 200 columns per block
 int64_t p7x_msa_write_stockholm(size_t n, int64_t alen, const char *const *names, const char *const *accs, const char *const *descs,

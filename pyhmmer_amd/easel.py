@@ -716,7 +716,11 @@ class MSA:
             raise ValueError(_lib.last_error())
         buf = C.create_string_buffer(int(size) + 1)
         fn(*args, buf, size + 1)
-        return buf.raw[:size].decode()
+        text = buf.raw[:size].decode()
+        # the per-file annotation of a named alignment (`TopHits.to_msa`), where Easel's writer puts it: after the header
+        gf = "".join(f"#=GF {tag} {v}\n" for tag, v in (("ID", self.name), ("AC", self.accession), ("DE", self.description)) if v)
+        head, sep, rest = text.partition("\n")
+        return head + sep + gf + rest
 
 
 class TextMSA(MSA):

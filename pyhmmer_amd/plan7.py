@@ -1898,6 +1898,68 @@ class TopHits:
                 h.description or "-"))
         return "".join(o)
 
+    @property
+    def alphabet(self) -> Optional[Alphabet]:
+        """The alphabet of the query the hits were found with (kept in the list itself, so it survives `to_bytes`, pickling
+        and `merge`); `None` for the per-sequence lists of a scan, whose hits are models."""
+        code = _lib.lib().p7x_tophits_abc_type(self._handle)
+        return Alphabet(code) if code in (eslAMINO, eslDNA, eslRNA) else None
+
+    def to_msa(self, alphabet: Alphabet, sequences: Optional[list] = None, traces: Optional[list] = None, trim: bool = False,
+               digitize: bool = False, all_consensus_cols: bool = False):
+        """The multiple alignment of all included domains (reference ``plan7.pyx:8966-9069``; upstream
+        ``p7_tophits_Alignment``, what ``hmmsearch -A`` writes): one row per included domain of every included hit, in the
+        list's current order, named ``<target>/<from>-<to>`` and holding the aligned residues only; ``sequences`` with
+        their ``traces`` (e.g. from `TraceAligner.compute_traces`) come first.  ``trim``, ``all_consensus_cols`` and
+        ``digitize`` as in `TraceAligner.align_traces`.  Returns a `~pyhmmer_amd.easel.TextMSA`, or a
+        `~pyhmmer_amd.easel.DigitalMSA` with ``digitize``, named after the query.
+
+        Everything the alignment needs -- the alignment displays, the model length, the query's name and alphabet --
+        is part of the hit list and of its serialised image: lists that went through `to_bytes` / `from_bytes`,
+        pickling or `merge` are aligned like the list of the search itself, and ``hits.query`` is not consulted.
+
+        Raises `~pyhmmer_amd.errors.AlphabetMismatch` when ``alphabet`` is not the hits', `ValueError` when
+        ``sequences`` and ``traces`` differ in length or when there is nothing to align ("No included domains found")."""
+        from .easel import DigitalMSA, TextMSA
+        own = self.alphabet
+        if own is not None and own != alphabet:
+            raise AlphabetMismatch(own, alphabet)
+        sequences = [] if sequences is None else list(sequences)
+        traces = [] if traces is None else list(traces)
+        if len(sequences) != len(traces):
+            raise ValueError("`sequences` and `traces` must have the same length")
+        nx = len(sequences)
+        for s in sequences:
+            if not isinstance(s, DigitalSequence):
+                raise TypeError(f"expected DigitalSequence, found {type(s).__name__}")
+            if s.alphabet != alphabet:
+                raise AlphabetMismatch(alphabet, s.alphabet)
+        flags = (1 if trim else 0) | (2 if all_consensus_cols else 0) | (4 if digitize else 0)
+        lib = _lib.lib()
+        h = C.c_void_p()
+        if nx:
+            tr = _cat_traces(traces)
+            pk = DigitalSequenceBlock(alphabet, sequences).packed()
+            arr = lambda xs: (C.c_char_p * nx)(*[(x or "").encode() for x in xs])
+            names, accs, descs = arr(s.name for s in sequences), arr(s.accession for s in sequences), arr(s.description for s in sequences)
+            st = lib.p7x_tophits_to_msa(self._handle, alphabet.type_code, traces[0].M, nx, tr.st.ctypes.data, tr.k.ctypes.data,
+                                        tr.i.ctypes.data, tr.pp.ctypes.data, tr.toff.ctypes.data, tr.origin.ctypes.data,
+                                        pk.dsq.ctypes.data, pk.offsets.ctypes.data, pk.lengths.ctypes.data, names, accs, descs,
+                                        flags, C.byref(h))
+        else:
+            st = lib.p7x_tophits_to_msa(self._handle, alphabet.type_code, 0, 0, None, None, None, None, None, None, None, None,
+                                        None, None, None, None, flags, C.byref(h))
+        if st != 0:
+            detail = _lib.last_error()
+            if st == 11:
+                raise ValueError(detail)
+            raise status_to_exception(st, "p7x_tophits_to_msa", detail)
+        try:
+            msa = _msa_from_handle(h, DigitalMSA if digitize else TextMSA, alphabet if digitize else None)
+        finally:
+            lib.p7x_msa_destroy(h)
+        return msa
+
     def copy(self) -> "TopHits":
         h = _lib.lib().p7x_tophits_clone(self._handle)
         return TopHits(self.query, C.c_void_p(h))
@@ -2468,6 +2530,50 @@ class SequenceDatabase:
 _T_M, _T_D, _T_I, _T_S, _T_N, _T_B, _T_E, _T_C, _T_T, _T_J = range(1, 11)      # p7T_* (p7_trace.pxd)
 
 
+class _TraceArrays:
+    """Traces concatenated into the arrays ``p7x_msa_from_traces`` / ``p7x_tophits_to_msa`` take."""
+
+    __slots__ = ("st", "k", "i", "pp", "toff", "origin")
+
+
+def _cat_traces(traces) -> _TraceArrays:
+    a = _TraceArrays()
+    a.toff = np.zeros(len(traces) + 1, dtype=np.int64)
+    a.toff[1:] = np.cumsum([len(t.st) for t in traces])
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt) for x in xs]) if xs else np.zeros(0, dt))
+    a.st = cat([t.st for t in traces], np.int8)
+    a.k = cat([t.k for t in traces], np.int32)
+    a.i = cat([t.i for t in traces], np.int32)
+    a.pp = cat([t._pp if t._pp is not None else np.zeros(len(t.st), np.float32) for t in traces], np.float32)
+    a.origin = np.array([(1 if t._pp is not None else 0) | (2 if t._device else 0) for t in traces], dtype=np.uint8)
+    return a
+
+
+def _msa_from_handle(h, cls, alphabet):
+    """The alignment ``p7x_tophits_to_msa`` made as an MSA object: rows, annotation, the rows' names, accessions and
+    descriptions, and the alignment's name."""
+    lib = _lib.lib()
+    alen = int(lib.p7x_msa_alen(h))
+
+    def get(idx, which):
+        n = int(lib.p7x_msa_get(h, idx, which, None, 0))
+        buf = C.create_string_buffer(n + 1)
+        lib.p7x_msa_get(h, idx, which, buf, n + 1)
+        return buf.value.decode()
+    nseq = 0
+    while lib.p7x_msa_get(h, nseq, 0, None, 0) >= 0:
+        nseq += 1
+    rows = [get(r, 0) for r in range(nseq)]
+    pps = [get(r, 1) for r in range(nseq)]
+    pp_cons, rf, ss = get(0, 2), get(0, 3), get(0, 4)
+    names, accs, descs = ([get(r, w) for r in range(nseq)] for w in (5, 6, 7))
+    assert all(len(r) == alen for r in rows)
+    msa = cls._from_rows(names, rows, descs, accs, pps if any(pps) else None, pp_cons or None, rf or None, ss or None,
+                         alphabet=alphabet)
+    msa.name = get(0, 8) or None
+    return msa
+
+
 class Trace:
     """A state path of one sequence through a model (reference ``plan7.pyx:9280-9540``, ``P7_TRACE``): states ``st``,
     nodes ``k`` and residue positions ``i`` in forward order, and -- for traces computed by `TraceAligner` -- the
@@ -2492,6 +2598,47 @@ class Trace:
         self.k = np.array([0] + list(range(1, n + 1)) + [0], dtype=np.int32)
         self.i = self.k.copy()
         self._M = self._L = n
+        return self
+
+    @classmethod
+    def from_alignment(cls, alignment, alphabet: Optional[Alphabet] = None, whole: bool = True) -> "Trace":
+        """The trace an `Alignment` (the alignment display of a domain) stands for: upstream's
+        ``p7_alidisplay_Backconvert``, which `TopHits.to_msa` applies to every included domain.  Not in the reference's
+        Python interface (an extension).
+
+        ``whole=True`` gives the trace of the whole target sequence -- N emits the residues before ``target_from``, C
+        those after ``target_to`` (posterior 1.0), ``L`` is the target's length -- so that it can be handed to
+        `TraceAligner.align_traces` together with the target itself.  ``whole=False`` gives upstream's own result, the
+        trace ``S N B ... E C T`` of the aligned subsequence alone, its residues numbered from 1 (``L`` is their
+        number); a reverse-strand domain of a long-target search (``target_from > target_to``) has only this form.
+        Posteriors are decoded from the PP line as ``p7_alidisplay_DecodePostProb`` does ('*' 1.0, '.' 0, a digit d
+        d / 10).  ``alphabet``: the alphabet of the display; by default that of the hits the alignment belongs to."""
+        if alphabet is None:
+            domain = getattr(alignment, "domain", None)
+            alphabet = domain.hit.hits.alphabet if domain is not None else None
+            if alphabet is None:
+                raise ValueError("the alphabet of the alignment is not known: pass `alphabet`")
+        ppline = alignment.posterior_probabilities
+        model, aseq = alignment.hmm_sequence.encode(), alignment.target_sequence.encode()
+        ncol = len(model)
+        cap = ncol + 6 + (max(0, int(alignment.target_length)) if whole else 0)
+        self = cls(posteriors=bool(ppline))
+        st, k, i = np.empty(cap, np.int8), np.empty(cap, np.int32), np.empty(cap, np.int32)
+        pp, dsq = np.empty(cap, np.float32), np.empty(cap, np.uint8)
+        N, subL = C.c_int32(), C.c_int32()
+        rc = _lib.lib().p7x_alidisplay_backconvert(alphabet.type_code, model, aseq, ppline.encode() if ppline else None,
+                                                   alignment.hmm_from, alignment.hmm_to, alignment.target_from, alignment.target_to,
+                                                   alignment.target_length, 1 if whole else 0, C.byref(N), C.byref(subL),
+                                                   st.ctypes.data, k.ctypes.data, i.ctypes.data, pp.ctypes.data, dsq.ctypes.data, cap)
+        if rc != 0:
+            raise status_to_exception(rc, "p7x_alidisplay_backconvert", _lib.last_error())
+        n = N.value
+        assert n <= cap
+        self.st, self.k, self.i = st[:n].copy(), k[:n].copy(), i[:n].copy()
+        if ppline:
+            self._pp = pp[:n].copy()
+        self._M = int(alignment.hmm_length)
+        self._L = int(alignment.target_length) if whole else subL.value
         return self
 
     def __repr__(self) -> str:
@@ -2626,14 +2773,8 @@ class TraceAligner:
             return DigitalMSA(hmm.alphabet) if digitize else TextMSA()
         self._check(hmm, sequences)
         flags = (1 if trim else 0) | (2 if all_consensus_cols else 0) | (4 if digitize else 0)
-        toff = np.zeros(nseq + 1, dtype=np.int64)
-        toff[1:] = np.cumsum([len(t.st) for t in traces])
-        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt) for x in xs]) if xs else np.zeros(0, dt))
-        st = cat([t.st for t in traces], np.int8)
-        k = cat([t.k for t in traces], np.int32)
-        i = cat([t.i for t in traces], np.int32)
-        pp = cat([t._pp if t._pp is not None else np.zeros(len(t.st), np.float32) for t in traces], np.float32)
-        origin = np.array([(1 if t._pp is not None else 0) | (2 if t._device else 0) for t in traces], dtype=np.uint8)
+        tr = _cat_traces(traces)
+        st, k, i, pp, toff, origin = tr.st, tr.k, tr.i, tr.pp, tr.toff, tr.origin
         om = OptimizedProfile(hmm, Background(hmm.alphabet), 400) if origin.any() and (origin & 2).any() else None
         pk = sequences.packed()
         cs = (" " + hmm.consensus_structure + "\0").encode() if hmm.consensus_structure else None
