@@ -151,7 +151,9 @@ int p7x_bck_parser(const p7x_oprofile *om, int device, const uint8_t *dsq, int32
 /* Batched raw filter outputs over a whole database (parity tests and bench).
  * xJ[t]  : integer MSV end state (p7_MSVFilter's xJ), -1 on overflow.
  * xC[t]  : integer Viterbi end state (p7_ViterbiFilter's xC), 32767 on overflow.
- * fwd[t] : Forward score in nats (p7_ForwardParser). Any output pointer may be NULL. */
+ * fwd[t] : Forward score in nats (p7_ForwardParser). Any output pointer may be NULL.
+ * The Viterbi filter is split as in the cascade: where the packed kernel takes the model, the database's longest
+ * targets (its long prefix, option "vit_long_cut") go to the wave-per-target kernel. */
 int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, int32_t *xC,
                       float *fwd, float *bias_filtersc);
 

@@ -1648,6 +1648,7 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     const bool small = small_block(db, ctx, 1);
     cls.first = 0; cls.n = 1; cls.msv_key = msv_key_of(dp, small); cls.vit_key = vit_key_of(dp, small); cls.C = dp->vitC;
     cls.nlong = (!small && cls.msv_key >= 0 && dp->msvw_emis) ? long_groups(db, ctx, 1) : 0;
+    cls.vit_long = cls.vit_key >= 0 ? db->vit_long_slots : 0;      // as in the cascade: the longest targets leave the packed kernel
     if (xJ && cls.msv_key < 0 && !dp->msvw_emis) { set_error("model too long for the MSV kernels (M > 8192)"); return P7X_EINVAL; }
   }
   for (int64_t t = 0; t < db->n; ++t) {
@@ -1673,7 +1674,7 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     la.dec = d;
     fill_msv_args(la, p, dp, db, ctx, b, cls.nlong);
     if (dp->vitC > 0) {
-      fill_vit_args(la, p, dp, db, ctx, nullptr, (int) ns, nullptr, b.xC);
+      fill_vit_args(la, p, dp, db, ctx, nullptr, (int) ns, nullptr, b.xC, cls.vit_long > 0 ? &b.counters[13] : nullptr, (int) cls.vit_long);
       WaveSeqArgs a = ws_args(p, dp, db, ctx);
       a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = nullptr; a.nlist = (int) ns; a.nlist_ptr = nullptr; a.out_sc = b.fwd_by_item;
       la.fwd = a;
@@ -1681,6 +1682,10 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
   }
   if ((st = upload_args(ws, 0, 1, s)) != P7X_OK) return st;
   P7X_HIP(hipMemsetAsync(ws->counters.as<int>(), 0, ws->counters_bytes(), s));
+  if (cls.vit_long > 0) {     // the work list is every slot: its long prefix is the database's (the cascade counts it on the device)
+    const int nlong = (int) cls.vit_long;
+    P7X_HIP(hipMemcpyAsync(&b.counters[13], &nlong, 4, hipMemcpyHostToDevice, s));
+  }
   if (xJ) {
     if ((st = class_msv(cls, lm, ctx, ws, s)) != P7X_OK) return st;
     std::vector<int16_t> h((size_t) ns);

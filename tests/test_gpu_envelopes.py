@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import bench
+import gap_models
 from conftest import load_hmms, random_hmm, synthetic_block
 from pyhmmer_amd import easel, hmmer, plan7
 from test_gpu_filters import _model_block
@@ -96,14 +97,24 @@ def test_device_envelopes_on_planted_workload():
     assert _records(guarded) == _records(hits)
 
 
-@pytest.mark.parametrize("M", [5, 64, 65, 150, 256, 300, 384, 478, 500, 640, 768, 1000, 1024, 1100, 1500, 2048, 2049, 3000, 5000, 8192])
-def test_device_envelopes_for_every_kernel_instantiation(M):
-    """Random models, one per nodes-per-lane instantiation of the envelope kernel."""
-    hmm = random_hmm(M, seed=3000 + M)
-    blk = _model_block(hmm, 300, 40, seed=M)
+@pytest.mark.parametrize("M,gappy", [pytest.param(M, False, id=str(M)) for M in (5, 64, 65, 150, 256, 300, 384, 478, 500, 640, 768, 1000, 1024, 1100,
+                                                                               1500, 2048, 2049, 3000, 5000, 8192)]
+                                    + [pytest.param(M, True, id=f"gap-rich-{M}") for M in (150, 640, 1100)])
+def test_device_envelopes_for_every_kernel_instantiation(M, gappy):
+    """Random models, one per nodes-per-lane instantiation of the envelope kernel.  The gap-rich cases (tests/gap_models.py:
+    deletion corridors longer than three stripes of the Viterbi filter, far longer than the envelope kernel's nodes per
+    lane) add 40 targets that are one domain only through a long D chain: the kernel's D scan across lanes decides them."""
+    if gappy:
+        hmm = gap_models.gappy_hmm(M, seed=5000 + M)
+        blk = _model_block(hmm, 300, 40, seed=M)
+        blk = easel.DigitalSequenceBlock(hmm.alphabet, list(blk) + gap_models.bridge_targets(hmm, 40, seed=M))
+    else:
+        hmm = random_hmm(M, seed=3000 + M)
+        blk = _model_block(hmm, 300, 40, seed=M)
     db = plan7.SequenceDatabase(blk)
     nhits, ndom = _compare(hmm, db, E=1e3, domE=1e3, rtol=ENV_TOL_REL_LONG if M > 2048 else 1e-5)
     assert ndom > 0 or M < 64
+    assert not gappy or ndom >= 40
 
 
 @pytest.mark.parametrize("M", [1100, 2048, 2049, 3000, 5000])

@@ -1,6 +1,8 @@
 """numpy emulation of the algorithm of p7x_vitpk.hip (test infrastructure): T lanes x 2 halves = 2T stripes of P nodes,
 node k = s*P + q + 1, stripe shift at register 0, lazy-F closure to convergence.  tests/test_oracle_golden.py checks it
-against the oracle's xC; it fixed the layout and the closure of the kernel before any device time was spent."""
+against the oracle's xC; it fixed the layout and the closure of the kernel before any device time was spent.
+max_pass stops the closure after that many passes: a wrong algorithm on purpose, the measuring stick with which
+tests/test_host_vit_gaps.py shows that its targets' scores depend on the later passes (not a second reference)."""
 import numpy as np
 import oracle_lib
 
@@ -18,7 +20,7 @@ def unstripe(op):
         rw[:, k] = rwv[:, q * 8 + z]
     return tw, rw
 
-def vit_striped(op, seq, T, P, stats=None):
+def vit_striped(op, seq, T, P, stats=None, max_pass=None):
     p = op.p; M = p.M; L = len(seq)
     oracle_lib.lib().p7o_reconfig_length(op.ptr, L)
     tw, rw = unstripe(op)
@@ -61,7 +63,7 @@ def vit_striped(op, seq, T, P, stats=None):
                 for q in range(1, P):
                     Dn[q] = np.maximum(Dn[q], sat(Dn[q - 1] + DD[q - 1]))
                 c = shift(sat(Dn[P - 1] + DD[P - 1]))
-                if not (c > Dn[0]).any(): break
+                if not (c > Dn[0]).any() or (max_pass is not None and npass >= max_pass): break
                 Dn[0] = np.maximum(Dn[0], c)
             if stats is not None: stats.append(npass)
         Mr, Ir, Dr = Mn, In, Dn
