@@ -553,6 +553,50 @@ int     p7x_debug_tophits_from_displays(const char *qname, int32_t abc_type, int
 int     p7x_debug_tophits_from_trace(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t N, const int8_t *st,
                                      const int32_t *k, const int32_t *i, const float *pp, const char *name, p7x_tophits **out);
 
+/* ------------------------------------------------------------------ sequence queries (phmmer): p7x_builder.cpp, p7x_calibrate.hip
+ * The single-sequence model of a protein (Builder.build, plan7.pyx:911-1016; upstream p7_builder_LoadScoreSystem, p7_Seqmodel,
+ * p7_SingleBuilder): M = L nodes; t[(L+1)*7] MM MI MD IM II DM DD, mat / ins[(L+1)*20], caller-allocated.  dsq[0..L-1]: the
+ * query's digital residues (a degenerate code gets the normalised sum of its residues' rows).  Host code; no device.
+ * P7X_EINVAL: an alphabet other than amino, a score matrix other than "BLOSUM62", a gap or missing-data symbol. */
+int p7x_builder_single(int32_t abc_type, const uint8_t *dsq, int32_t L, const float *bg_f, const char *score_matrix,
+                       double popen, double pextend, float *t, float *mat, float *ins);
+/* The sequences of p7_Calibrate's defaults (upstream evalues.c): P7X_CAL_N samples of 200 residues for the MSV filter, as many
+ * of 200 for the Viterbi filter and of 100 for the Forward parser, drawn in that order from one stream (esl_rsq_xfIID over
+ * bg_f) of one of Easel's two generators, seeded as esl_randomness_Init seeds it.  out[P7X_CAL_RESIDUES]: the samples end to
+ * end, no sentinels.  For one alphabet, background, seed and generator this is a constant. */
+#define P7X_CAL_N 200
+#define P7X_CAL_RESIDUES 100000
+enum { P7X_RNG_MERSENNE = 0, P7X_RNG_FAST = 1 };   /* esl_randomness_Create / esl_randomness_CreateFast */
+#define P7X_CAL_GENERATOR P7X_RNG_FAST              /* the one p7x_calibrate_batch draws with: upstream's builder makes its
+                                                    * generator with esl_randomness_CreateFast and re-seeds it for every model */
+int p7x_calibration_stream(int32_t abc_type, const float *bg_f, uint32_t seed, int generator, uint8_t *out);
+/* The same stream for a model some of whose samples overflowed a filter: upstream draws such a sample again, so every
+ * later sample moves.  skipped[nskipped]: increasing numbers of the DRAWS (kept or not, counted from 0) that are thrown
+ * away; out receives the 600 kept samples.  A model's own stream is found by calling this until no kept sample overflows. */
+int p7x_calibration_redraw(int32_t abc_type, const float *bg_f, uint32_t seed, int generator, const int32_t *skipped,
+                           int nskipped, uint8_t *out);
+/* The number of the draw that kept sample <kept> (0 .. 599) of p7x_calibration_redraw(skipped) is: what the device path adds to
+ * <skipped> (increasing) when that sample overflows in its turn. */
+int32_t p7x_calibration_draw_of(int32_t kept, const int32_t *skipped, int nskipped);
+/* Raw filter results of the MSV and Viterbi samples -> scores in nats as the filters report them under the length model
+ * of 200 residues: sc[2 * P7X_CAL_N], overflow[2 * P7X_CAL_N] (xJ < 0, xC = 32767). */
+int p7x_calibration_scores(const p7x_oprofile *om, const int32_t *xJ, const int32_t *xC, float *sc, uint8_t *overflow);
+/* The fits (p7_Lambda, p7_MSVMu, p7_ViterbiMu, p7_Tau; esl_gumbel_FitCompleteLoc / FitComplete, tail mass 0.04), in double:
+ * sc[3 * P7X_CAL_N] scores in nats (MSV, Viterbi, Forward; they enter as (sc - null1(L)) / ln 2), mh = M times the mean
+ * match relative entropy in bits (p7x_oprofile_match_relent), out_evparam[6] in the order of P7X_MMU...  overflow
+ * [2 * P7X_CAL_N] or NULL: a marked sample makes the call return P7X_ERANGE and fit nothing -- the model must be
+ * calibrated on its own stream (p7x_calibration_redraw). */
+int p7x_calibration_fit(const float *sc, const uint8_t *overflow, double mh, float *out_evparam);
+/* M x p7_MeanMatchRelativeEntropy of the model a profile was made from (0: a pressed profile, which does not carry it) */
+double p7x_oprofile_match_relent(const p7x_oprofile *om);
+/* p7_Calibrate for a batch of profiles on the device: every profile against the 600 resident samples of its alphabet and
+ * background and <seed> (generated once per device and kept; the builder's default seed is 42), one wavefront per (profile, sample), one launch per stage and tier of
+ * nodes per lane, no host synchronisation before the one copy of the raw results; then the fits on the host.  A profile
+ * with an overflowed sample is calibrated again, alone, on its own stream.  out_evparam[nq][6] is also stored in the
+ * profiles.  out_scores (may be NULL): [nq][3][P7X_CAL_N] raw results, xJ and xC as integers, Forward in nats (float
+ * bits).  M <= 8192.  P7X_ENODEVICE without a device; P7X_EINVAL for a profile without p7x_oprofile_match_relent. */
+int p7x_calibrate_batch(p7x_oprofile *const *oms, size_t nq, int device, uint32_t seed, float *out_evparam, int32_t *out_scores);
+
 const char *p7x_last_error(void);
 
 #ifdef __cplusplus

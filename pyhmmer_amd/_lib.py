@@ -18,7 +18,7 @@ CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libp7x.so"
 
 SOURCES = ["p7x_profile.cpp", "p7x_device.hip", "p7x_devmem.hip", "p7x_devimage.hip", "p7x_msv.hip", "p7x_vitfwd.hip", "p7x_vitpk.hip", "p7x_fwdpk.hip", "p7x_envelope.hip", "p7x_ensemble.hip", "p7x_ssvlong.hip", "p7x_longtarget.hip",
-           "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp"]
+           "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp", "p7x_builder.cpp", "p7x_calibrate.hip"]
 
 
 def _hipcc() -> str:
@@ -285,6 +285,14 @@ _SIGNATURES = {
                                                   C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_uint32),
                                                   C.POINTER(C.c_int32), C.POINTER(DomainRec), C.POINTER(_VP)]),
     "p7x_debug_tophits_from_trace": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_char_p, C.POINTER(_VP)]),
+    "p7x_builder_single": (C.c_int, [C.c_int32, _VP, C.c_int32, _VP, C.c_char_p, C.c_double, C.c_double, _VP, _VP, _VP]),
+    "p7x_calibration_stream": (C.c_int, [C.c_int32, _VP, C.c_uint32, C.c_int, _VP]),
+    "p7x_calibration_redraw": (C.c_int, [C.c_int32, _VP, C.c_uint32, C.c_int, _VP, C.c_int, _VP]),
+    "p7x_calibration_draw_of": (C.c_int32, [C.c_int32, _VP, C.c_int]),
+    "p7x_calibration_scores": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "p7x_calibration_fit": (C.c_int, [_VP, _VP, C.c_double, _VP]),
+    "p7x_oprofile_match_relent": (C.c_double, [_VP]),
+    "p7x_calibrate_batch": (C.c_int, [C.POINTER(_VP), C.c_size_t, C.c_int, C.c_uint32, _VP, _VP]),
     "p7x_last_error": (C.c_char_p, []),
 }
 

@@ -33,6 +33,7 @@ struct Alphabet {
 struct Profile {
   int M = 0, K = 0, Kp = 0, abc_type = 0, L = 0, max_length = -1, mode = 0;
   float nj = 1.0f;
+  double relent_mh = 0.0;        // M x mean match relative entropy of the core model (bits): p7_Lambda at calibration; 0 = not known
   std::string name, acc, desc, consensus, rf, mm, cs;
   bool has_acc = false, has_desc = false;
   float evparam[6], cutoff[6], compo[MAXK], bgf[MAXK];
@@ -67,6 +68,7 @@ double gumbel_surv(double x, double mu, double lambda);
 double exp_surv(double x, double mu, double lambda);
 double exp_logsurv(double x, double mu, double lambda);
 float  null1_score(int L);
+double match_relent_sum(const float *mat, const float *bg_f, int M, int K);      // p7x_builder.cpp
 void   flogsum_init();
 float  flogsum(float a, float b);
 

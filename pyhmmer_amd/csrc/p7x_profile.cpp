@@ -344,6 +344,7 @@ int p7x_oprofile_create(const p7x_hmm_view *h, const float *bg_f, int32_t L, p7x
   if (h->compo) std::memcpy(p.compo, h->compo, sizeof(float) * p.K);
   std::memset(p.bgf, 0, sizeof(p.bgf));
   std::memcpy(p.bgf, bg_f, sizeof(float) * p.K);
+  p.relent_mh = match_relent_sum(h->mat, bg_f, p.M, p.K);
   configure_generic(p, *h);
   convert_msv(p);
   convert_viterbi(p);

@@ -19,10 +19,10 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Union
 
 from . import _lib
-from .easel import Alphabet, DigitalSequenceBlock, SequenceFile
-from .plan7 import HMM, LongTargetsPipeline, OptimizedProfile, Pipeline, Profile, SequenceDatabase, TopHits
+from .easel import Alphabet, DigitalSequence, DigitalSequenceBlock, SequenceFile
+from .plan7 import HMM, Builder, LongTargetsPipeline, OptimizedProfile, Pipeline, Profile, SequenceDatabase, TopHits
 
-__all__ = ["hmmsearch", "hmmscan", "nhmmer", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase", "ReplicatedDatabase"]
+__all__ = ["hmmsearch", "phmmer", "hmmscan", "nhmmer", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase", "ReplicatedDatabase"]
 
 
 def make_chunks(block: DigitalSequenceBlock, n: int) -> List[DigitalSequenceBlock]:
@@ -294,6 +294,92 @@ def hmmsearch(queries: Union[HMM, Profile, OptimizedProfile, Iterable], sequence
     for q, hits in _run_queries(db, pipelines, queries, pipeline_depth, feeders, finishers=finishers, batch=batch):
         if callback is not None:
             callback(q, total)
+        yield hits
+
+
+_PHMMER_BATCH = 64       # query sequences whose models are built together and calibrated by one p7x_calibrate_batch
+
+
+def phmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = None, builder: Optional[Builder] = None,
+           devices: Optional[Sequence[int]] = None, pipeline_depth: int = 8, batch: int = 0, **options) -> Iterator[TopHits]:
+    """Search protein SEQUENCES against a sequence database; yields one ``TopHits`` per query, in query order (reference
+    ``_phmmer.py:106``).
+
+    The queries are taken ``_PHMMER_BATCH`` at a time: the single-sequence models of a batch are built on the host workers
+    (``Builder``: BLOSUM62, ``popen`` / ``pextend``), calibrated together by one ``p7x_calibrate_batch`` on the first device --
+    every model against the device's 600 resident random sequences, one set of launches for the batch -- and handed as
+    optimized profiles to the machinery ``hmmsearch`` runs its HMM queries through (batched cascades, overlapped host
+    stages).  ``callback`` receives ``(query sequence, total)``; every other keyword goes to ``Pipeline``.  MSA queries
+    (``Builder.build_msa``) are not offered."""
+    import itertools
+    if isinstance(queries, DigitalSequence):
+        queries = (queries,)
+    if isinstance(sequences, SequenceFile):
+        if not sequences.digital:
+            raise ValueError("target sequences file is not in digital mode")
+        sequences = sequences.read_block()
+    if not isinstance(sequences, (DigitalSequenceBlock, SequenceDatabase, ShardedDatabase)):
+        raise TypeError(f"Expected DigitalSequenceBlock or SequenceFile, found {type(sequences).__name__}")
+    alphabet: Alphabet = sequences.shards[0].alphabet if isinstance(sequences, ShardedDatabase) else sequences.alphabet
+    total = None
+    try:
+        total = len(queries)          # type: ignore[arg-type]
+    except TypeError:
+        pass
+    it = iter(queries)
+    head = list(itertools.islice(it, 1))
+    if not head:
+        return                                   # no query: nothing to yield (and no device needed)
+    if _lib.lib().p7x_device_count() < 1:
+        from .errors import DeviceUnavailable
+        raise DeviceUnavailable("phmmer: no HIP device is usable and there is no CPU fallback")
+    if isinstance(sequences, SequenceDatabase):
+        db = ShardedDatabase.from_database(sequences)
+    elif isinstance(sequences, ShardedDatabase):
+        db = sequences
+    else:
+        db = ShardedDatabase(sequences, list(devices) if devices else default_devices())
+    devs = db.devices
+    pipelines = [Pipeline(alphabet, device=d, host_threads=cpus, **options) for d in devs]
+    background = pipelines[0].background
+    if builder is None:
+        builder = Builder(alphabet, seed=pipelines[0].seed or 0)
+    elif builder.alphabet != alphabet:
+        from .errors import AlphabetMismatch
+        raise AlphabetMismatch(alphabet, builder.alphabet)
+    seed = builder._calibration_seed()
+    usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    workers = max(1, min(cpus if cpus > 0 else usable, 16))
+    source: dict = {}                            # id(profile) -> its query sequence, until the result is handed out
+
+    def one(seq):
+        hmm = builder._model(seq, background)    # type and alphabet errors surface here, at the query's position
+        return OptimizedProfile(hmm, background, Pipeline.L_HINT)
+
+    def profiles():
+        from .plan7 import _calibrate
+        with ThreadPoolExecutor(max_workers=workers, thread_name_prefix="p7x-phmmer-build") as pool:
+            for chunk in _batches(itertools.chain(head, it), _PHMMER_BATCH):
+                good, err = [], None
+                for seq, fut in [(seq, pool.submit(one, seq)) for seq in chunk]:
+                    try:
+                        if err is None:
+                            good.append((seq, fut.result()))
+                    except BaseException as e:       # the queries before it are still searched, then the error surfaces
+                        err = e
+                if good:
+                    _calibrate([om for _, om in good], device=devs[0], seed=seed)
+                for seq, om in good:
+                    source[id(om)] = seq
+                    yield om
+                if err is not None:
+                    raise err
+
+    for om, hits in _run_queries(db, pipelines, profiles(), pipeline_depth, 0, batch=batch):
+        query = source.pop(id(om))
+        hits.query = query
+        if callback is not None:
+            callback(query, total)
         yield hits
 
 

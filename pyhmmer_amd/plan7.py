@@ -28,7 +28,7 @@ from .errors import (AlphabetMismatch, AllocationError, InvalidParameter, Missin
 
 __all__ = [
     "HMM", "HMMFile", "HMMPressedFile", "Background", "Profile", "OptimizedProfile", "OptimizedProfileBlock", "EvalueParameters", "Cutoffs",
-    "Pipeline", "LongTargetsPipeline", "SequenceDatabase", "TopHits", "Hit", "Domain", "Domains", "Alignment",
+    "Builder", "Pipeline", "LongTargetsPipeline", "SequenceDatabase", "TopHits", "Hit", "Domain", "Domains", "Alignment",
     "Trace", "Traces", "TraceAligner",
 ]
 
@@ -2017,6 +2017,121 @@ class TopHits:
         return [TopHits(None if queries is None else queries[q], C.c_void_p(outs[q])) for q in range(nq)]
 
 
+# --------------------------------------------------------------------------- Builder (sequence queries)
+
+def _calibrate(oms: Sequence["OptimizedProfile"], device: int = 0, seed: int = 42, want_scores: bool = False):
+    """``p7_Calibrate`` of a batch of profiles on ``device`` (``p7x_calibrate_batch``: one set of launches for all of them).
+    The parameters are stored in the profiles and, where a profile was made from an HMM, in that HMM; returns them as an
+    ``(n, 6)`` array -- with ``want_scores`` also the raw results ``(n, 3, 200)``: xJ, xC, Forward score (float bits)."""
+    n = len(oms)
+    ev = np.zeros((n, 6), dtype=np.float32)
+    raw = np.zeros((n, 3, 200), dtype=np.int32) if want_scores else None
+    handles = (C.c_void_p * max(n, 1))(*[om._handle for om in oms])
+    st = _lib.lib().p7x_calibrate_batch(handles, n, int(device), int(seed), ev.ctypes.data, None if raw is None else raw.ctypes.data)
+    if st != 0:
+        raise status_to_exception(st, "p7x_calibrate_batch", _lib.last_error())
+    for om, v in zip(oms, ev):
+        _lib.lib().p7x_oprofile_get_info(om._handle, C.byref(om._info))
+        if om._hmm is not None:
+            om._hmm._evparam[:] = v
+    return (ev, raw) if want_scores else ev
+
+
+class Builder:
+    """The HMM builder for single-sequence queries (reference ``plan7.pyx:604-1150``; upstream ``p7_builder.c``): ``build`` turns
+    a protein sequence into the model ``phmmer`` searches with -- one node per residue, match emissions from the score
+    matrix, gap-open / gap-extend transitions -- and calibrates it on the device.  Amino alphabet and BLOSUM62 only (the DNA
+    score system belongs to nhmmer's sequence queries); ``build_msa`` and the architecture, weighting and prior options of
+    the reference are not offered."""
+
+    def __init__(self, alphabet: Alphabet, *, popen: float = 0.02, pextend: float = 0.4, score_matrix: str = "BLOSUM62",
+                 seed: int = 42):
+        if not alphabet.is_amino():
+            raise InvalidParameter("alphabet", alphabet, hint="amino alphabet: there is no DNA score system")
+        self.alphabet = alphabet
+        self.popen, self.pextend, self.score_matrix, self.seed = popen, pextend, score_matrix, seed
+
+    popen = property(lambda self: self._popen)
+    pextend = property(lambda self: self._pextend)
+    score_matrix = property(lambda self: self._score_matrix)
+    seed = property(lambda self: self._seed)
+
+    @popen.setter
+    def popen(self, popen: float) -> None:
+        if not (0.0 <= popen < 0.5):
+            raise InvalidParameter("popen", popen, hint="real number between 0 and 0.5")          # plan7.pyx: Builder.popen
+        self._popen = float(popen)
+
+    @pextend.setter
+    def pextend(self, pextend: float) -> None:
+        if not (0.0 <= pextend < 1.0):
+            raise InvalidParameter("pextend", pextend, hint="real number between 0 and 1")
+        self._pextend = float(pextend)
+
+    @score_matrix.setter
+    def score_matrix(self, score_matrix: str) -> None:
+        if score_matrix != "BLOSUM62":
+            raise InvalidParameter("score_matrix", score_matrix, choices=["BLOSUM62"])
+        self._score_matrix = score_matrix
+
+    @seed.setter
+    def seed(self, seed: int) -> None:
+        if not (0 <= int(seed) < 2 ** 32):
+            raise InvalidParameter("seed", seed, hint="32-bit unsigned integer")
+        self._seed = int(seed)
+
+    def copy(self) -> "Builder":
+        return Builder(self.alphabet, popen=self.popen, pextend=self.pextend, score_matrix=self.score_matrix, seed=self.seed)
+
+    def __copy__(self) -> "Builder":
+        return self.copy()
+
+    def __repr__(self) -> str:
+        return f"<Builder alphabet={self.alphabet!r} popen={self.popen} pextend={self.pextend} score_matrix={self.score_matrix!r} seed={self.seed}>"
+
+    def _calibration_seed(self) -> int:
+        """The seed of the calibration stream; 0 asks for an arbitrary one, as in the reference."""
+        return self._seed if self._seed != 0 else int.from_bytes(os.urandom(4), "little") | 1
+
+    def _model(self, sequence: DigitalSequence, background: Background) -> HMM:
+        """The uncalibrated model of ``sequence`` (upstream ``p7_SingleBuilder`` up to the calibration).  Host code; no device."""
+        if not isinstance(sequence, DigitalSequence):
+            raise TypeError(f"Expected DigitalSequence, found {type(sequence).__name__}")
+        if background.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, background.alphabet)
+        if sequence.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, sequence.alphabet)
+        dsq = np.ascontiguousarray(sequence.sequence, dtype=np.uint8)
+        L, K = int(dsq.shape[0]), self.alphabet.K
+        if L < 1:
+            raise ValueError("Could not build HMM: the query sequence is empty")
+        hmm = HMM(self.alphabet, L, sequence.name or "query")
+        bgf = np.ascontiguousarray(background.residue_frequencies, dtype=np.float32)
+        st = _lib.lib().p7x_builder_single(self.alphabet.type_code, dsq.ctypes.data, L, bgf.ctypes.data, self.score_matrix.encode(),
+                                           self.popen, self.pextend, hmm.transition_probabilities.ctypes.data,
+                                           hmm.match_emissions.ctypes.data, hmm.insert_emissions.ctypes.data)
+        if st == 11:
+            raise ValueError(f"Could not build HMM: {_lib.last_error()}")                  # plan7.pyx:1006-1008
+        if st != 0:
+            raise status_to_exception(st, "p7x_builder_single", _lib.last_error())
+        hmm.accession = sequence.accession or None
+        hmm.description = sequence.description or None
+        hmm.nseq, hmm.nseq_effective, hmm.checksum = 1, 1.0, 0
+        hmm.set_composition()
+        hmm.set_consensus(sequence)
+        hmm.command_line = " ".join(sys.argv)
+        return hmm
+
+    def build(self, sequence: DigitalSequence, background: Background, device: int = 0):
+        """``(HMM, Profile, OptimizedProfile)`` of a query sequence, calibrated (reference ``plan7.pyx:911-1016``)."""
+        hmm = self._model(sequence, background)
+        om = OptimizedProfile(hmm, background, Pipeline.L_HINT)
+        _calibrate([om], device=device, seed=self._calibration_seed())
+        profile = Profile(hmm.M, self.alphabet)
+        profile.configure(hmm, background, Pipeline.L_HINT)
+        return hmm, profile, om
+
+
 # --------------------------------------------------------------------------- Pipeline
 
 class Pipeline:
@@ -2137,6 +2252,21 @@ class Pipeline:
                 self._db_cache = (key, SequenceDatabase(sequences, device=self.device))
             database = self._db_cache[1]
         return self._search_database(om, database, query)
+
+    def search_seq(self, query: DigitalSequence, sequences, builder: Optional["Builder"] = None) -> TopHits:
+        """Run the pipeline with a query SEQUENCE against every target of ``sequences``: ``phmmer`` (reference
+        ``plan7.pyx:6331-6391``).  The model is built by ``builder`` (default: ``Builder(alphabet, seed=self.seed)``) and
+        calibrated on this pipeline's device."""
+        if not isinstance(query, DigitalSequence):
+            raise TypeError(f"Expected DigitalSequence, found {type(query).__name__}")
+        if query.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, query.alphabet)
+        builder = Builder(self.alphabet, seed=self.seed or 0) if builder is None else builder
+        hmm, profile, om = builder.build(query, self.background, device=self.device)
+        hits = self.search_hmm(om, sequences)
+        hits.query = query
+        hits._om = om                       # the alignments refer to the profile: keep it alive with the hits
+        return hits
 
     def scan_seq(self, query: DigitalSequence, optimized_profiles) -> TopHits:
         """Run the pipeline with one query sequence against a collection of profiles (reference
@@ -2272,6 +2402,10 @@ class LongTargetsPipeline(Pipeline):
         c.block_length = self.block_length
         c.window_length = -1 if self.window_length is None else int(self.window_length)
         return c
+
+    def search_seq(self, query, sequences, builder=None):
+        """Not offered: a nucleotide sequence query needs the DNA score system of the builder (reference ``plan7.pyx:7420-7480``)."""
+        raise NotImplementedError("LongTargetsPipeline.search_seq: there is no DNA score system to build a model from a sequence")
 
     def _windowed_om(self, query, L: int, cfg) -> "OptimizedProfile":
         """The optimized profile of ``query`` and the two window lengths of the search (reference ``plan7.pyx:7336-7354``):
