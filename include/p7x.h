@@ -295,6 +295,14 @@ int  p7x_debug_log_of_float(int device, const float *in, float *out, size_t n);
  * slab pool of <device> and not yet freed, [1] = of that, parked in the pool; [2] = pinned host memory obtained (process-wide),
  * [3] = of that, parked.  A workload that runs a second time on pooled objects must leave all four as they were. */
 int  p7x_debug_memory_stats(int device, int64_t out[4]);
+/* Test seam of the cascades' stream layout (csrc/p7x_device.hpp: DeviceCtx), no HIP call: the order in which a device context
+ * creates the streams of its cascade sets.  out[0] = sets, [1] = streams per set (the main stream and its side streams),
+ * [2] = which side stream (0-based) is the partner of the main stream, [3] = spacer streams; then, set by set, the creation
+ * position (0-based, in the context's order of creation) of the set's main stream and of its side streams in their order;
+ * then the positions of the spacers.  Returns the number of values (all of them are written if cap is at least that).
+ * *hw_queues = GPU_MAX_HW_QUEUES as the environment had it when the library was loaded; 0: it was unset and the library
+ * asked for eight (which holds only if the HIP runtime was not initialised yet); -1: set to something that is no number. */
+int64_t p7x_debug_stream_plan(int32_t *out, size_t cap, int32_t *hw_queues);
 /* Test seams of the stochastic traceback ensembles (p7_domaindef.c region_trace_ensemble; p7_domaindef.pxd:23-59).
  * p7x_debug_choice: one choice point of p7_StochasticTrace with n paths of weights p[], for the generator state x after the
  *   draw: the path taken through the integer thresholds the product uses and through esl_rnd_FChoose as the reference

@@ -233,6 +233,7 @@ _SIGNATURES = {
     "p7x_pending_nqueries": (C.c_size_t, [_VP]),
     "p7x_debug_log_of_float": (C.c_int, [C.c_int, _VP, _VP, C.c_size_t]),
     "p7x_debug_memory_stats": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
+    "p7x_debug_stream_plan": (C.c_int64, [C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int32)]),
     "p7x_debug_choice": (C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
     "p7x_debug_order_spread": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int, _VP]),
     "p7x_debug_parser_rows": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP]),

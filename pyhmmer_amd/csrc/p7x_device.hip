@@ -22,9 +22,36 @@ static int device_count_checked()
 }
 
 // The classes of a batch run on up to eight streams of one workspace, and several workspaces are in flight: ask the
-// runtime for more hardware queues than its default of four before it initialises (no effect if the process already
-// made a HIP call, or if the user set the variable).
+// runtime for more hardware queues than its default of four before it initialises.  This is a request, not a fact: a
+// value that the environment already holds stays (a library does not override it), and a process that made a HIP call
+// before this library was loaded runs with the queues it had then -- four, unless it asked for more itself.  The stream
+// layout below is therefore right for four queues as for eight (stream_plan).
+static const char *const g_hw_queues_env = std::getenv("GPU_MAX_HW_QUEUES");
+static const int g_hw_queues_seen = !g_hw_queues_env ? 0 : (std::atoi(g_hw_queues_env) > 0 ? std::atoi(g_hw_queues_env) : -1);    // before the setenv below
 static const int g_hw_queues_set = setenv("GPU_MAX_HW_QUEUES", "8", 0);
+
+// What the runtime does with the streams of one priority, as scripts/ubench/queue_probe measured it with Q = 4 and Q = 8
+// hardware queues (profiles/r10_queues.md): the first Q streams open queues 0 .. Q-1, and from then on the stream at
+// creation position p joins queue Q-1 - (p mod Q) -- the least used queue, the highest-numbered one on a tie.  (Not the
+// round robin p mod Q that the layout assumed until round 10; and every priority has Q queues of its own, so the streams
+// of default and of least priority never share a queue with these.)  From position 8 on the queue is a function of
+// p mod Q for both counts, whatever was created before; so eight spacers come first, and then set n starts at the first free
+// position = n (mod 8).  Mains: different mod 4, so on different queues with four as with eight.  Partner at main + 4: the
+// same mod 4 and another mod 8.  A set's eight streams follow each other: every queue once with eight, twice with four.
+StreamPlan stream_plan(int nsets, int per_set)
+{
+  StreamPlan p;
+  p.nsets = nsets; p.per_set = per_set;
+  p.partner = 4 - 1;                                   // side stream k sits at main + 1 + k
+  int next = 0;
+  while (next < 8) p.spacer_pos.push_back(next++);
+  for (int n = 0; n < nsets; ++n) {
+    while (next % 8 != n % 8) p.spacer_pos.push_back(next++);
+    p.main_pos.push_back(next);
+    next += per_set;
+  }
+  return p;
+}
 
 int create_tail_stream(DeviceCtx *ctx, bool high_priority, hipStream_t *out)
 { // (Round 5 tried these streams on a subset of the CUs, hipExtStreamCreateWithCUMask with 64 or 128 of 256: the headline fell
@@ -46,13 +73,14 @@ int get_ctx(int device, DeviceCtx **out)
   P7X_HIP(hipSetDevice(device));
   auto ctx = std::make_unique<DeviceCtx>();
   ctx->device = device;
-  {   // cascade stream sets first (see DeviceCtx): set n's main stream goes to queue position off[n] of the round robin
+  {   // cascade stream sets first (see DeviceCtx), in the order of stream_plan
     int least = 0, greatest = 0;
     P7X_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const int off[DeviceCtx::kWsSets] = { 0, 4, 2, 6 };
+    const StreamPlan plan = stream_plan(DeviceCtx::kWsSets, DeviceCtx::kWsSide + 1);
+    ctx->ws_partner = plan.partner;
     int created = 0;
     for (int n = 0; n < DeviceCtx::kWsSets; ++n) {
-      while (created % 8 != off[n]) { hipStream_t sp = nullptr; P7X_HIP(hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, greatest)); ctx->ws_spacers.push_back(sp); ++created; }
+      while (created < plan.main_pos[(size_t) n]) { hipStream_t sp = nullptr; P7X_HIP(hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, greatest)); ctx->ws_spacers.push_back(sp); ++created; }
       P7X_HIP(hipStreamCreateWithPriority(&ctx->ws_main[n], hipStreamNonBlocking, greatest)); ++created;
       for (auto &q : ctx->ws_side[n]) { P7X_HIP(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, greatest)); ++created; }
     }
@@ -131,6 +159,17 @@ using namespace p7x;
 extern "C" {
 
 int p7x_device_count(void) { return device_count_checked(); }
+
+int64_t p7x_debug_stream_plan(int32_t *out, size_t cap, int32_t *hw_queues)
+{
+  const StreamPlan p = stream_plan(DeviceCtx::kWsSets, DeviceCtx::kWsSide + 1);
+  std::vector<int32_t> v = { p.nsets, p.per_set, p.partner, (int32_t) p.spacer_pos.size() };
+  for (int n = 0; n < p.nsets; ++n) for (int k = 0; k < p.per_set; ++k) v.push_back(p.main_pos[(size_t) n] + k);
+  v.insert(v.end(), p.spacer_pos.begin(), p.spacer_pos.end());
+  if (out && cap >= v.size()) std::copy(v.begin(), v.end(), out);
+  if (hw_queues) *hw_queues = g_hw_queues_seen;
+  return (int64_t) v.size();
+}
 
 int p7x_device_name(int device, char *buf, size_t n)
 {

@@ -57,21 +57,38 @@ struct DeviceCtx {
   std::multimap<size_t, void *> slab_free;
   size_t slab_free_bytes = 0;
   size_t slab_obtained_bytes = 0;       // from the runtime through the pool and not yet freed: parked or in use
-  // The streams of the cascades.  The runtime deals streams onto its hardware queues (GPU_MAX_HW_QUEUES = 8) in the order
-  // they are created, and streams that share a queue run one after the other.  A cascade workspace used to create its
-  // main stream and seven class streams when it was first needed -- eight streams, so the main streams of the two
+  // The streams of the cascades.  The runtime deals the streams of one priority onto that priority's hardware queues in the
+  // order they are created, and streams that share a queue run one after the other.  A cascade workspace used to create
+  // its main stream and seven class streams when it was first needed -- eight streams, so the main streams of the two
   // workspaces that two feeders drive side by side landed on the SAME queue whenever nothing else was created in between,
   // and the MSV launch of one cascade then waited for the tail of the other instead of running beside it: a search fell
   // into a fast or a slow mode by the timing of its first milliseconds (many-profile stream 29 or 37 s; VERDICT r03 weak
-  // #2).  The sets are now created here, once, main streams four queues apart (then two, then six), before any other
-  // stream of the library; workspaces take them in turn.
+  // #2).  The sets are created here, once, before any other stream of the library; workspaces take them in turn.
+  // How many queues there are the library cannot know: it asks for eight when it is loaded, but a GPU_MAX_HW_QUEUES that
+  // the environment already set stays, and a runtime that was initialised before the library was loaded (any program that
+  // used the device first) keeps its default of FOUR.  So the layout (stream_plan, p7x_device.hip: the measured dealing
+  // order is there) holds for four queues and for eight: the four main streams sit on four different queues either way
+  // (until round 10 the mains of sets 2 and 3 shared a queue when there were four), every set covers all queues, and
+  // every main stream has a partner four positions on -- on the main stream's own queue with four queues, on another
+  // with eight (profiles/r10_queues.md).
   static constexpr int kWsSets = 4, kWsSide = 7;
   hipStream_t ws_main[kWsSets]{};
   hipStream_t ws_side[kWsSets][kWsSide]{};
+  int ws_partner = 0;                   // which side stream of every set is the partner of its main stream
   std::vector<hipStream_t> ws_spacers;
   int ws_set_users[kWsSets]{};          // cascades running on every set right now (guarded by mu): a lease takes the least used one
 };
 int get_ctx(int device, DeviceCtx **out);
+// The order in which get_ctx creates the streams of the cascade sets (pure arithmetic, no HIP call): eight spacer streams,
+// then set n's main stream at the first free creation position = n (mod 8), its side streams at the positions after it,
+// spacer streams in the gaps.
+struct StreamPlan {
+  int nsets = 0, per_set = 0;
+  int partner = 0;                      // side stream (0-based) at main + 4: main's queue with four queues, another with eight
+  std::vector<int> main_pos;            // [nsets] creation position of the main stream; side stream k is at main_pos + 1 + k
+  std::vector<int> spacer_pos;          // creation positions of the streams that are created only to be skipped
+};
+StreamPlan stream_plan(int nsets, int per_set);
 // a stream for the kernels of a search's host stage (envelopes: low priority; ensembles: high)
 int create_tail_stream(DeviceCtx *ctx, bool high_priority, hipStream_t *out);
 

@@ -548,6 +548,7 @@ struct Workspace {
   // own stream (forked from / joined into <stream>), so that the classes' latency-bound launches overlap
   static constexpr int kSide = DeviceCtx::kWsSide;        // the streams belong to the device context (queue placement, see there)
   hipStream_t side[kSide]{};
+  int partner = 0;                  // side[partner]: on the main stream's hardware queue when there are four, on another when eight
   hipEvent_t ev_fork = nullptr, ev_join[kSide]{};
   static constexpr int kTierRuns = 8;      // MSV tier launches of a batch (p7x_msv.hip: five tiers; runs of lanes that share one)
   hipEvent_t ev_tier[kTierRuns]{}, ev_tier0[kTierRuns]{};     // end / begin of every tier launch (timed: the bench's roofline is the largest one's)
@@ -592,6 +593,7 @@ struct Workspace {
     ctx->ws_set_users[set]++;
     stream = ctx->ws_main[set];
     for (int k = 0; k < kSide; ++k) side[k] = ctx->ws_side[set][k];
+    partner = ctx->ws_partner;
   }
   void on_return()      // the end of a lease (LeasePool)
   {
@@ -1229,6 +1231,12 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
   return P7X_OK;
 }
 
+// Streams of a multi-class cascade against a large block, unless option cascade_streams says otherwise (cascade_enqueue).
+// Round 10, 4,000 library profiles x 500,000 targets, three cascades in flight, TCUPS with four / eight hardware queues:
+// 8 streams 23.8 / 24.8, 2 streams 25.8 / 26.5 (all chains on the partner: 25.7 / 26.1), 1 stream 25.2 / 26.1
+// (profiles/r10_queues.md).
+constexpr int kCascadeStreams = 2;
+
 static int cascade_enqueue(CascadeRun &r)
 {
   const p7x_pipeline_cfg &cfg = r.cfg; const p7x_seqdb *db = r.db;
@@ -1310,13 +1318,27 @@ static int cascade_enqueue(CascadeRun &r)
     const bool fills_device = (db->nslots / 64) * (int64_t) nq >= (int64_t) ctx->num_cu * 8;
     if ((st = class_cascade(r, classes[0], s, true, fills_device)) != P7X_OK) return st;
   } else {
-    // the classes in turn over the workspace's stream and its side streams (eight streams = the eight hardware queues:
-    // with the workspace's stream taking only the first class its queue idled through most of a 28-class batch of the
-    // scan orientation, whose device phase is the longest queue's sum of kernel latencies), forked from and joined into
-    // the workspace's stream
+    // the classes in turn over the workspace's stream and its side streams, forked from and joined into the workspace's
+    // stream.  A small block, stage by stage (option stage_merge: 0 never, 1 always, unset: blocks of up to 256 groups), takes
+    // all eight streams: with the workspace's stream taking only the first class its queue idled through most of a 28-class
+    // batch of the scan orientation, whose device phase is the longest queue's sum of kernel latencies.
+    const int sm = debug_opt(OPT_STAGE_MERGE);
+    const bool staged = sm >= 0 ? sm != 0 : db->ngroups <= 256;
+    // Against a large block the launches fill the device, other cascades are in flight, and the concurrency inside one
+    // cascade does not matter (profiles/r06_feeders.txt); what matters is that a cascade stays off the other cascades'
+    // hardware queues.  Over eight streams it is on every queue there is, and a chain that waits for its tier launch
+    // holds up whatever another cascade put behind it on that queue.  Option cascade_streams: 8 all streams, 2 the main
+    // stream and its partner (one queue of four, two of eight), 1 the main stream alone; with two streams the tier launches
+    // run on the main stream and the chains alternate between the two, or (option cascade_split) all run on the partner.
+    const int cs_opt = debug_opt(OPT_CASCADE_STREAMS);
+    const int nstreams = staged ? Workspace::kSide + 1 : (cs_opt == 1 || cs_opt == 2 || cs_opt == 8 ? cs_opt : kCascadeStreams);
+    const bool few = nstreams < Workspace::kSide + 1;
+    const bool split = nstreams == 2 && debug_opt(OPT_CASCADE_SPLIT) > 0;
+    hipStream_t partner = ws->side[ws->partner];
     P7X_HIP(hipEventRecord(ws->ev_fork, s));
     const int nside = std::min<int>((int) classes.size() - 1, Workspace::kSide);
-    for (int k = 0; k < nside; ++k) P7X_HIP(hipStreamWaitEvent(ws->side[k], ws->ev_fork, 0));
+    if (!few) for (int k = 0; k < nside; ++k) P7X_HIP(hipStreamWaitEvent(ws->side[k], ws->ev_fork, 0));
+    else if (nstreams == 2) P7X_HIP(hipStreamWaitEvent(partner, ws->ev_fork, 0));
     // The fast MSV kernel of the whole batch first, as one launch per tier of register tiles (p7x_msv.hip); the classes'
     // chains then wait for their tier and start at the exact kernel over the ambiguous groups.
     constexpr int kStreamsAll = Workspace::kSide + 1;
@@ -1335,7 +1357,7 @@ static int cascade_enqueue(CascadeRun &r)
         size_t b = a; while (b + 1 < classes.size() && run_of[b + 1] == run) ++b;
         const int first = classes[a].first, n = classes[b].first + classes[b].n - first;
         const int turn = (kStreamsAll - 1 - run) % kStreamsAll;       // from the far end: the longest classes' chains are dealt from stream 0
-        hipStream_t ts = turn == 0 ? s : ws->side[std::min(turn, nside) - 1];
+        hipStream_t ts = few ? s : (turn == 0 ? s : ws->side[std::min(turn, nside) - 1]);
         const LaneClass &k = classes[a];
         P7X_HIP(hipEventRecord(ws->ev_tier0[run], ts));
         if ((st = msv_tier_launch(msv_tier(r.lm[k.first].dp->msvR, r.lm[k.first].dp->msvK), lane_run(ws, &LaneArgs::msv, first, n), ctx->num_cu, ts)) != P7X_OK) return st;
@@ -1345,9 +1367,6 @@ static int cascade_enqueue(CascadeRun &r)
       }
       ws->ntier_runs = nruns;
     }
-    // a small block: stage by stage (option stage_merge: 0 never, 1 always, unset: blocks of up to 256 groups)
-    const int sm = debug_opt(OPT_STAGE_MERGE);
-    const bool staged = sm >= 0 ? sm != 0 : db->ngroups <= 256;
     if (staged) {
       if ((st = staged_cascade(r, classes, s, nside, run_of)) != P7X_OK) return st;
     } else
@@ -1359,12 +1378,16 @@ static int cascade_enqueue(CascadeRun &r)
       int turn = (int) (n % (size_t) kStreams);
       if ((n / (size_t) kStreams) & 1) turn = kStreams - 1 - turn;
       hipStream_t cs = turn == 0 ? s : ws->side[turn - 1];
+      if (few) cs = nstreams == 1 ? s : (split || (n & 1) ? partner : s);
       if (run_of[c] >= 0) P7X_HIP(hipStreamWaitEvent(cs, ws->ev_tier[run_of[c]], 0));
       if ((st = class_cascade(r, classes[c], cs, n == 0, false, run_of[c] >= 0)) != P7X_OK) return st;
     }
-    for (int k = 0; k < nside; ++k) {
+    if (!few) for (int k = 0; k < nside; ++k) {
       P7X_HIP(hipEventRecord(ws->ev_join[k], ws->side[k]));
       P7X_HIP(hipStreamWaitEvent(s, ws->ev_join[k], 0));
+    } else if (nstreams == 2) {
+      P7X_HIP(hipEventRecord(ws->ev_join[ws->partner], partner));
+      P7X_HIP(hipStreamWaitEvent(s, ws->ev_join[ws->partner], 0));
     }
   }
   // The survivors' results travel with the cascade: gathered and copied behind its last kernel for up to kEarlyPack of them
