@@ -47,6 +47,11 @@ enum { P7X_BITCUT_NONE = 0, P7X_BITCUT_GA = 1, P7X_BITCUT_NC = 2, P7X_BITCUT_TC 
 
 int p7x_abi_version(void);
 
+/* The longest model (nodes; a sequence query's length) the device kernels take: 64 lanes x the widest tier of nodes per
+ * lane they are instantiated for.  A longer model is refused with P7X_EINVAL by every device entry point, and the message
+ * states this number.  The reference has no limit (plan7.pyx:6156-6262).  nhmmer's SSV scan ends earlier, at 6,141. */
+int p7x_max_model_length(void);
+
 /* expf(-v) exactly as upstream read_asc30hmm parses an HMMER3/f ASCII save file
  * ('*' is passed as +inf and yields 0).  Replaces the C parser behind HMMFile (plan7.pyx:3656-4050). */
 void p7x_expf_neg(const double *in, float *out, size_t n);
@@ -602,7 +607,7 @@ double p7x_oprofile_match_relent(const p7x_oprofile *om);
  * nodes per lane, no host synchronisation before the one copy of the raw results; then the fits on the host.  A profile
  * with an overflowed sample is calibrated again, alone, on its own stream.  out_evparam[nq][6] is also stored in the
  * profiles.  out_scores (may be NULL): [nq][3][P7X_CAL_N] raw results, xJ and xC as integers, Forward in nats (float
- * bits).  M <= 8192.  P7X_ENODEVICE without a device; P7X_EINVAL for a profile without p7x_oprofile_match_relent. */
+ * bits).  M <= p7x_max_model_length.  P7X_ENODEVICE without a device; P7X_EINVAL for a profile without p7x_oprofile_match_relent. */
 int p7x_calibrate_batch(p7x_oprofile *const *oms, size_t nq, int device, uint32_t seed, float *out_evparam, int32_t *out_scores);
 
 const char *p7x_last_error(void);

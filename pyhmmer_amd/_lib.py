@@ -179,6 +179,7 @@ class HitRec(C.Structure):
 _VP = C.c_void_p
 _SIGNATURES = {
     "p7x_abi_version": (C.c_int, []),
+    "p7x_max_model_length": (C.c_int, []),
     "p7x_tophits_merge_longtargets": (C.c_int, [C.POINTER(_VP), C.c_size_t, C.POINTER(_VP)]),
     "p7x_tophits_merge_many": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_int, C.POINTER(_VP)]),
     "p7x_tophits_get_guard_counts": (C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

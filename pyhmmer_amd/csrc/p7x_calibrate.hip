@@ -98,12 +98,17 @@ __global__ void __launch_bounds__(kWsBlock) cal_vit_kernel(const ArgRef ref, con
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int Mpad = 64 * C;
   constexpr bool EG = C > 32;         // M > 2048: only the transitions are staged
+  constexpr bool TG = C > 128;        // M > 8192: the transitions are read through L2 as well (as vit_kernel)
+  static_assert(!TG || EG, "transitions through L2 only where the emissions are");
   const CalArgs a = load_args<CalArgs>(ref);
-  uint4 *tr = reinterpret_cast<uint4 *>(smem);                       // [Mpad]
+  const uint4 *tr = TG ? reinterpret_cast<const uint4 *>(a.vit_trans) : reinterpret_cast<const uint4 *>(smem);      // [Mpad]
   const short *em = EG ? reinterpret_cast<const short *>(a.vit_emis) : reinterpret_cast<const short *>(smem + (size_t) Mpad * 16);
   {
-    const uint4 *gt = reinterpret_cast<const uint4 *>(a.vit_trans);
-    for (int i = threadIdx.x; i < Mpad; i += kWsBlock) tr[i] = gt[i];
+    if constexpr (!TG) {
+      const uint4 *gt = reinterpret_cast<const uint4 *>(a.vit_trans);
+      uint4 *lt = reinterpret_cast<uint4 *>(smem);
+      for (int i = threadIdx.x; i < Mpad; i += kWsBlock) lt[i] = gt[i];
+    }
     if constexpr (!EG) {
       const uint4 *ge = reinterpret_cast<const uint4 *>(a.vit_emis);
       uint4 *le = reinterpret_cast<uint4 *>(smem + (size_t) Mpad * 16);
@@ -278,7 +283,7 @@ __global__ void __launch_bounds__(kWsBlock) cal_fwd_kernel(const ArgRef ref, con
 
 // ---------------------------------------------------------------------------- host side
 static size_t cal_lds_msv(int C, int K) { return C > 32 ? (size_t) 256 : (size_t) 64 * C * K * 2; }
-static size_t cal_lds_vit(int C, int K) { return (size_t) 64 * C * (16 + (C <= 32 ? K * 2 : 0)); }
+static size_t cal_lds_vit(int C, int K) { return C > 128 ? (size_t) 256 : (size_t) 64 * C * (16 + (C <= 32 ? K * 2 : 0)); }
 static size_t cal_lds_fwd(int C, int K) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? K * 4 : 0)); }
 
 template <typename Kern>
@@ -352,7 +357,7 @@ static int cal_run(CalSet &set, int n, const uint8_t *d_stream)
     while (hi < n && ha[hi].C == ha[lo].C) ++hi;
     const ArgRef ref{ set.d_args.as<CalArgs>() + lo, (uint32_t) sizeof(CalArgs) };
     const int K = ha[lo].K, nm = hi - lo;
-    const int st = node_tier_dispatch(ha[lo].C, "model too long for the calibration kernels (M > 8192)", [&](auto tier) {
+    const int st = node_tier_dispatch(ha[lo].C, "model too long for the calibration kernels", [&](auto tier) {
       constexpr int CC = decltype(tier)::value;
       int s1 = cal_launch(cal_msv_kernel<CC>, cal_lds_msv(CC, K), ref, nm, d_stream, set.stream);
       if (s1 == P7X_OK) s1 = cal_launch(cal_vit_kernel<CC>, cal_lds_vit(CC, K), ref, nm, d_stream, set.stream);
@@ -422,7 +427,7 @@ int p7x_calibrate_batch(p7x_oprofile *const *oms, size_t nq, int device, uint32_
     const Profile &p = oms[q]->p, &p0 = oms[0]->p;
     if (!(p.relent_mh > 0.0)) { set_error("calibration needs the relative entropy of the core model: '" + p.name + "' does not carry it"); return P7X_EINVAL; }
     if (p.abc_type != p0.abc_type || std::memcmp(p.bgf, p0.bgf, sizeof(float) * p.K) != 0) { set_error("the profiles of a calibration batch share one alphabet and one background"); return P7X_EINVAL; }
-    if (vit_pick_C(p.M) <= 0) { set_error("model too long for the calibration kernels (M > 8192)"); return P7X_EINVAL; }
+    if (vit_pick_C(p.M) <= 0) { set_error(model_too_long("model too long for the calibration kernels")); return P7X_EINVAL; }
   }
   auto lease = LeasePool<CalSet>::instance().lease(ctx->device, [](const CalSet &, const CalSet *b) { return !b; });
   CalSet &set = *lease;

@@ -1,5 +1,6 @@
 // p7x_kernels.hpp -- launch interfaces of the HIP kernels (one translation unit per kernel family).
 #pragma once
+#include <string>
 #include <type_traits>
 #include "p7x_device.hpp"
 
@@ -88,17 +89,24 @@ int  msv_exact_launch(int R, int K, const ArgRun<MsvArgs> &amb, int num_cu, hipS
 // ---- wave-per-sequence stages (p7x_vitfwd.hip): Viterbi filter, Forward / Backward parsers
 // Node k = z*C + c + 1 lives in lane z, chunk position c; device tables are stored [c*64 + z].
 // The tiers of C, nodes per lane, that the wave-per-sequence kernels, the envelope / alignment kernel and the ensemble
-// fill are instantiated for (M <= 64 C; the last one: M <= 8192): every dispatch on C and vit_pick_C() expand this list.
-#define P7X_NODE_TIERS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(16) X(20) X(24) X(32) X(48) X(64) X(96) X(128)
+// fill are instantiated for (M <= 64 C; the last one bounds the model length: max_model_length()): every dispatch on C and
+// vit_pick_C() expand this list.  Beyond 128 nodes per lane (M > 8192: sequence queries, phmmer) the steps are wide -- such
+// models are a handful per proteome and every tier is another instantiation of every kernel: 192 (M <= 12,288).  The list
+// ends where the runtime still grants env_kernel's scratch memory: tiers of 320 and 576 were refused on the MI355X.
+#define P7X_NODE_TIERS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(16) X(20) X(24) X(32) X(48) X(64) X(96) X(128) X(192)
+// the longest model the device kernels take: 64 x the last tier (p7x_max_model_length() of p7x.h)
+int max_model_length();
+// "<what> (M > max_model_length() nodes)": the text of every refusal of a model for its length
+std::string model_too_long(const char *what);
 // f(std::integral_constant<int, C>()) where C is a tier (f picks and launches its kernel's instantiation for it), else
-// the error <too_long>
+// the error model_too_long(<too_long>)
 template <class F> int node_tier_dispatch(int C, const char *too_long, F &&f)
 {
   switch (C) {
 #define P7X_TIER_CASE(CC) case CC: return f(std::integral_constant<int, CC>());
     P7X_NODE_TIERS(P7X_TIER_CASE)
 #undef P7X_TIER_CASE
-    default: set_error(too_long); return P7X_EINVAL;
+    default: set_error(model_too_long(too_long)); return P7X_EINVAL;
   }
 }
 struct WaveSeqArgs {
@@ -138,7 +146,7 @@ int fwdg_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st);
 void fwdg_build_tables(const Profile &p, int T, int C, std::vector<float> &trans, std::vector<float> &emis);
 int bck_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st);
 
-// ---- MSV for models beyond the register-resident kernels (p7x_vitfwd.hip::msv_wave_kernel), M <= 8192
+// ---- MSV for models beyond the register-resident kernels (p7x_vitfwd.hip::msv_wave_kernel), every tier of P7X_NODE_TIERS
 struct MsvWaveArgs {
   int C, nrows;
   const void *emis;         // int16 [nrows][64*C], (bias - cost) in lane-chunk order, kNegPad outside the model / pad row

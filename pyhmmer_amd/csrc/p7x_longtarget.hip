@@ -325,7 +325,7 @@ struct DeviceWindowScorer final : LongTargetWindowScorer {
     int st;
     if ((st = get_ctx(device, &ctx)) != P7X_OK || (st = get_dev_profile(om, ctx, &dp)) != P7X_OK) return st;
     const int C = dp->vitC, Mpad = 64 * C, nrows = p.Kp + 1;
-    if (C <= 0) { set_error("model too long for the envelope kernel"); return P7X_EINVAL; }
+    if (C <= 0) { set_error(model_too_long("model too long for the envelope kernel")); return P7X_EINVAL; }
     // the envelopes' match odds in the kernel's table layout: [row x][position of node k], node k of lane z, slot c at c * 64 + z
     const size_t stride = (size_t) nrows * Mpad;
     std::vector<float> tables(n * stride, 0.0f);
@@ -364,7 +364,7 @@ struct DeviceWindowScorer final : LongTargetWindowScorer {
     DeviceCtx *ctx = nullptr; DevProfile *dp = nullptr;
     int st;
     if ((st = get_ctx(device, &ctx)) != P7X_OK || (st = get_dev_profile(om, ctx, &dp)) != P7X_OK) return st;
-    if (dp->vitC <= 0) { set_error("model too long for the wave-per-target Viterbi kernel"); return P7X_EINVAL; }
+    if (dp->vitC <= 0) { set_error(model_too_long("model too long for the wave-per-target Viterbi kernel")); return P7X_EINVAL; }
     // caller index -> slot of the window block (slots are sorted by decreasing length)
     std::vector<int32_t> slot_of((size_t) db->n, -1);
     for (int64_t sl = 0; sl < db->nslots; ++sl) slot_of[(size_t) db->h_order[(size_t) sl]] = (int32_t) sl;

@@ -812,7 +812,7 @@ static int lane_classes(const std::vector<LaneModel> &lm, const p7x_seqdb *db, c
   out.clear();
   for (int l = 0; l < nl; ++l) {
     const DevProfile *dp = lm[l].dp;
-    if ((dp->msvR <= 0 || small) && !dp->msvw_emis) { set_error("model too long for the MSV kernels (M > 8192)"); return P7X_EINVAL; }
+    if ((dp->msvR <= 0 || small) && !dp->msvw_emis) { set_error(model_too_long("model too long for the MSV kernels")); return P7X_EINVAL; }
     LaneClass c; c.first = l; c.n = 1; c.msv_key = msv_key_of(dp, small); c.vit_key = vit_key_of(dp, small); c.C = dp->vitC;
     c.nlong = (c.msv_key >= 0 && dp->msvw_emis) ? nlong : 0;
     c.vit_long = c.vit_key >= 0 ? db->vit_long_slots : 0;
@@ -1271,7 +1271,7 @@ static int cascade_enqueue(CascadeRun &r)
   tick("images");
   if (db->nslots == 0 || nq == 0) return P7X_OK;
   for (int l = 0; l < nq; ++l)
-    if (r.lm[l].dp->vitC <= 0) { set_error("model too long for the device kernels: M > 8192 nodes (the reference has no limit, plan7.pyx:6156-6262; the lane-chunk layout of the wave-per-target kernels ends at 128 nodes per lane -- no Pfam-A model comes near it)"); return P7X_EINVAL; }
+    if (r.lm[l].dp->vitC <= 0) { set_error(model_too_long("model too long for the device kernels: the reference has no limit (plan7.pyx:6156-6262), the lane-chunk layout of the wave-per-target kernels ends at its last tier of nodes per lane")); return P7X_EINVAL; }
   std::vector<LaneClass> classes;
   if ((st = lane_classes(r.lm, db, ctx, classes)) != P7X_OK) return st;
   if ((st = get_workspace(ctx, db->nslots, nq, r.ws)) != P7X_OK) return st;
@@ -1672,7 +1672,7 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     cls.first = 0; cls.n = 1; cls.msv_key = msv_key_of(dp, small); cls.vit_key = vit_key_of(dp, small); cls.C = dp->vitC;
     cls.nlong = (!small && cls.msv_key >= 0 && dp->msvw_emis) ? long_groups(db, ctx, 1) : 0;
     cls.vit_long = cls.vit_key >= 0 ? db->vit_long_slots : 0;      // as in the cascade: the longest targets leave the packed kernel
-    if (xJ && cls.msv_key < 0 && !dp->msvw_emis) { set_error("model too long for the MSV kernels (M > 8192)"); return P7X_EINVAL; }
+    if (xJ && cls.msv_key < 0 && !dp->msvw_emis) { set_error(model_too_long("model too long for the MSV kernels")); return P7X_EINVAL; }
   }
   for (int64_t t = 0; t < db->n; ++t) {
     if (xJ) xJ[t] = 0;
@@ -1717,7 +1717,7 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     for (int64_t sl = 0; sl < ns; ++sl) xJ[db->h_order[sl]] = h[sl];
   }
   if (xC || fwd) {
-    if (dp->vitC <= 0) { set_error("model too long for the wave-per-sequence kernels"); return P7X_EINVAL; }
+    if (dp->vitC <= 0) { set_error(model_too_long("model too long for the wave-per-sequence kernels")); return P7X_EINVAL; }
     if (xC) {
       if ((st = class_viterbi(cls, lm, ctx, ws, s)) != P7X_OK) return st;
       std::vector<int32_t> h((size_t) ns);

@@ -177,7 +177,7 @@ int device_traces(const p7x_oprofile *om, int device, const uint8_t *dsq, const 
   for (size_t t = 0; t < n; ++t) if (lengths[t] > 0) order.push_back((int) t);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return lengths[x] > lengths[y]; });
   const int C = vit_pick_C(p.M);
-  if (C <= 0) { set_error("hmmalign: model too long for the alignment kernel"); return P7X_EINVAL; }
+  if (C <= 0) { set_error(model_too_long("hmmalign: model too long for the alignment kernel")); return P7X_EINVAL; }
   const size_t budget = align_budget_bytes();
   std::vector<EnvelopeRequest> req;
   std::vector<int32_t> targets;

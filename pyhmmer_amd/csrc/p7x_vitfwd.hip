@@ -26,11 +26,16 @@ __global__ void __launch_bounds__(kWsBlock) vit_kernel(const ArgRef ref)
   const int nlist = (a.abort_flag && *a.abort_flag) ? 0 : (a.nlist_ptr ? *a.nlist_ptr : a.nlist);
   if ((int) (blockIdx.x * (kWsBlock / 64)) >= nlist) return;         // no item for this block: skip the table load
   constexpr bool EG = C > 32;         // long models (M > 2048): the emission table is read where it lies (L2), only the transitions are staged
-  uint4 *tr = reinterpret_cast<uint4 *>(smem);                       // [Mpad]
+  constexpr bool TG = C > 128;        // M > 8192: 16 bytes per node no longer fit the LDS, the transitions are read through L2 as well
+  static_assert(!TG || EG, "transitions through L2 only where the emissions are");
+  const uint4 *tr = TG ? reinterpret_cast<const uint4 *>(a.trans) : reinterpret_cast<const uint4 *>(smem);      // [Mpad]
   const short *em = EG ? reinterpret_cast<const short *>(a.emis) : reinterpret_cast<const short *>(smem + (size_t) Mpad * 16);  // [kTabRows][Mpad]
   {
-    const uint4 *gt = reinterpret_cast<const uint4 *>(a.trans);
-    for (int i = threadIdx.x; i < Mpad; i += kWsBlock) tr[i] = gt[i];
+    if constexpr (!TG) {
+      const uint4 *gt = reinterpret_cast<const uint4 *>(a.trans);
+      uint4 *lt = reinterpret_cast<uint4 *>(smem);
+      for (int i = threadIdx.x; i < Mpad; i += kWsBlock) lt[i] = gt[i];
+    }
     if constexpr (!EG) {
       const uint4 *ge = reinterpret_cast<const uint4 *>(a.emis);
       uint4 *le = reinterpret_cast<uint4 *>(smem + (size_t) Mpad * 16);
@@ -649,8 +654,11 @@ __global__ void __launch_bounds__(kWsBlock) bck_kernel(const ArgRef ref)
 
 // ---------------------------------------------------------------------------- host side
 #define P7X_TIER_ITEM(CC) CC,
-static const int kCList[] = { P7X_NODE_TIERS(P7X_TIER_ITEM) };      // M <= 8192
+static const int kCList[] = { P7X_NODE_TIERS(P7X_TIER_ITEM) };
 #undef P7X_TIER_ITEM
+
+int max_model_length() { return 64 * kCList[sizeof(kCList) / sizeof(kCList[0]) - 1]; }
+std::string model_too_long(const char *what) { return std::string(what) + " (M > " + std::to_string(max_model_length()) + " nodes)"; }
 
 int vit_pick_C(int M)
 {
@@ -696,6 +704,8 @@ static int launch_ws(K kernel, const ArgRun<WaveSeqArgs> &a, size_t lds_bytes, i
   return P7X_OK;
 }
 
+// Dynamic LDS of the Viterbi filter: the transitions, 16 bytes per node (M > 8192: read through L2), and the emission rows up to M = 2048
+static size_t vit_lds_bytes(int C, int nrows) { return C > 128 ? (size_t) 256 : (size_t) 64 * C * (16 + (C <= 32 ? nrows * 2 : 0)); }
 // Dynamic LDS of the parsers: the transitions, 32 bytes per node (M > 4096: read through L2), and the emission rows while
 // they fit beside them (M <= 1024: the instantiations without EG)
 static size_t fwd_lds_bytes(int C, int nrows) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? nrows * 4 : 0)); }
@@ -704,9 +714,9 @@ int vit_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
-  return node_tier_dispatch(C, "model too long for the wave-per-sequence kernels (M > 8192)", [&](auto tier) {
-    constexpr int CC = decltype(tier)::value;      // transitions 16 bytes per node; the emission rows up to M = 2048
-    return launch_ws(vit_kernel<CC>, a, (size_t) 64 * CC * (16 + (CC <= 32 ? nrows * 2 : 0)), num_cu, st);
+  return node_tier_dispatch(C, "model too long for the wave-per-sequence kernels", [&](auto tier) {
+    constexpr int CC = decltype(tier)::value;
+    return launch_ws(vit_kernel<CC>, a, vit_lds_bytes(CC, nrows), num_cu, st);
   });
 }
 
@@ -751,7 +761,7 @@ int fwd_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
-  return node_tier_dispatch(C, "model too long for the Forward/Backward kernels (M > 8192)", [&](auto tier) {
+  return node_tier_dispatch(C, "model too long for the Forward/Backward kernels", [&](auto tier) {
     constexpr int CC = decltype(tier)::value;
     return launch_ws(fwd_kernel<CC, (CC > 16)>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
   });
@@ -760,10 +770,12 @@ int bck_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
-  return node_tier_dispatch(C, "model too long for the Forward/Backward kernels (M > 8192)", [&](auto tier) {
+  return node_tier_dispatch(C, "model too long for the Forward/Backward kernels", [&](auto tier) {
     constexpr int CC = decltype(tier)::value;
     return launch_ws(bck_kernel<CC, (CC > 16)>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
   });
 }
 
 } // namespace p7x
+
+extern "C" int p7x_max_model_length(void) { return p7x::max_model_length(); }

@@ -352,7 +352,14 @@ def phmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = 
     workers = max(1, min(cpus if cpus > 0 else usable, 16))
     source: dict = {}                            # id(profile) -> its query sequence, until the result is handed out
 
+    max_length = _lib.lib().p7x_max_model_length()
+
     def one(seq):
+        # a query beyond the device kernels' model length (one node per residue) fails here, at its own position: the
+        # calibration of the batch it would travel in refuses a batch as a whole
+        if isinstance(seq, DigitalSequence) and len(seq) > max_length:
+            raise ValueError(f"phmmer: query {seq.name!r} has {len(seq)} residues: model too long for the device kernels "
+                             f"(M > {max_length} nodes)")
         hmm = builder._model(seq, background)    # type and alphabet errors surface here, at the query's position
         return OptimizedProfile(hmm, background, Pipeline.L_HINT)
 
