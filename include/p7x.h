@@ -49,7 +49,8 @@ int p7x_abi_version(void);
 
 /* The longest model (nodes; a sequence query's length) the device kernels take: 64 lanes x the widest tier of nodes per
  * lane they are instantiated for.  A longer model is refused with P7X_EINVAL by every device entry point, and the message
- * states this number.  The reference has no limit (plan7.pyx:6156-6262).  nhmmer's SSV scan ends earlier, at 6,141. */
+ * states this number.  The reference has no limit (plan7.pyx:6156-6262).  nhmmer's SSV scan takes a model beyond
+ * what one launch holds in chained parts (p7x_debug_ssv_plan). */
 int p7x_max_model_length(void);
 
 /* expf(-v) exactly as upstream read_asc30hmm parses an HMMER3/f ASCII save file
@@ -332,13 +333,30 @@ int  p7x_debug_parser_rows(const p7x_oprofile *om, const uint8_t *dsq1, int32_t 
  * M + 1 (emission 0) of the every-second-row flavour.  Returns the number of 32-bit words of the table (written when
  * cap_words is large enough), or a negative status. */
 int64_t p7x_debug_ssv_tables(const p7x_oprofile *om, int pair, int32_t *R, int32_t *pair_slack, uint32_t *tab4q, size_t cap_words);
+/* Test seams of the SSV scan in chained parts (host code, no device).  One launch of the kernel holds the model in
+ * registers; a model beyond that is cut into P consecutive parts that run one after the other, each taking the score of
+ * the node before its first one from the part before, row by row.
+ * p7x_debug_ssv_plan: the parts of a model of M nodes -- nodes lo[q] .. hi[q], R[q] registers per lane, q < min(P, cap) --
+ * with parts_forced = 0 the library's plan, 2 .. 4 that many parts where the model has two nodes for each (what the option
+ * "ssv_parts" does to a scan).  Returns P, or a negative status (M beyond p7x_max_model_length()).
+ * p7x_debug_ssv_part_tables: p7x_debug_ssv_tables for part <part> of that plan: cell c of the layout is node lo - 1 + c,
+ * padding outside lo .. hi (cell 0 included), the virtual node hi + 1 in the last part only.
+ * p7x_debug_ssv_merge_rows: the host's merge of the rows the parts report, n records (position, strand, node, byte score)
+ * in any order -> one record per (strand, position), in that order: the highest score, on a tie the node that comes
+ * first in upstream's striped order, ((k - 1) % Q16) * 16 + (k - 1) / Q16.  Returns the number of rows written (<= n). */
+int     p7x_debug_ssv_plan(int M, int pair, int parts_forced, int32_t *lo, int32_t *hi, int32_t *R, int cap);
+int64_t p7x_debug_ssv_part_tables(const p7x_oprofile *om, int pair, int parts_forced, int part, int32_t *lo, int32_t *hi, int32_t *R,
+                                  uint32_t *tab4q, size_t cap_words);
+int64_t p7x_debug_ssv_merge_rows(int Q16, size_t n, const int64_t *pos, const int32_t *strand, const int32_t *k, const int32_t *sc,
+                                 int64_t *out_pos, int32_t *out_strand, int32_t *out_k, int32_t *out_sc);
 /* Test / diagnostic seam: process-wide knobs, by name; value -1 = not set (the library decides).  The library itself reads no
  * environment variables.  Kernel families for parity tests: "small_block" (0: never the wave-per-target filters for small
  * blocks), "vit_wave" (1: the wave-per-target Viterbi kernel for every model), "msv_exact" (1: no fast MSV pass),
  * "msv_long_groups" (0: the longest groups stay with the lane kernel), "msv_blocks_per_cu" (cap), "device_clustered" (0 / 1:
  * with host ensembles, where their clustered envelopes are rescored), "env_workspace_gb" (cap of the envelope kernel's
  * workspace), "ssv_kernel" (long-target SSV scan: 3 = the row maximum in every row, 4 = in every second row whatever the
- * model).  Traces on stderr: "trace_finish", "trace_longtarget", "trace_envelope", "host_profile" (1: on). */
+ * model), "ssv_parts" (2 / 3 / 4: the scan in that many chained parts, for any model with two nodes for each; 0: the
+ * library's plan).  Traces on stderr: "trace_finish", "trace_longtarget", "trace_envelope", "host_profile" (1: on). */
 int  p7x_debug_set_option(const char *name, int value);
 int  p7x_debug_ensemble(const p7x_oprofile *om, const p7x_seqdb *db, int64_t target, int32_t i, int32_t j, uint32_t seed,
                         int use_device, int32_t *ndom, int32_t *dom, int32_t dom_cap, float *n2, int32_t *status);

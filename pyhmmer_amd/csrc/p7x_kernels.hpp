@@ -281,12 +281,28 @@ struct SsvLongArgs {
   int xB, Q16;                // the begin score in byte units; vectors per row of the reference's striped layout (tie-breaks)
   // rows that reach the threshold: position on the strand, strand, and the cell upstream would pick (node, byte score)
   int *nrec; long long *rec_pos; uint8_t *rec_strand; int *rec_k; int *rec_sc; int rec_cap;
+  // a scan in chained parts (a model of more nodes than one launch holds; read by the boundary instantiations only, M, Q16 and
+  // pair_slack stay the whole model's): the part's nodes are node0 + 1 .. node0 + nloc, its tables are built for them
+  int node0, nloc;
+  int out_lane;               // boundary-out: the part's last node is the top register's cell of this lane (high half on odd rows, low on even ones)
+  unsigned short *bnd;        // [nchunks][bnd_stride] the native 16-bit cell of the cut node after every row of a chunk, warm-up included:
+  long long bnd_stride;       //   written by a part with a successor, read (and overwritten in place) by the next one
+  long long chunk0;           // no chunk_list: the launch scans chunks chunk0 .. chunk0 + nchunks - 1 (a round of a scan in parts)
 };
 // <pair>: the row maximum only on every second row, against a threshold lowered by pair_slack, tables with the virtual node
 int  ssvlong_pick_R(int M, bool pair);
-void ssvlong_build_tables(const Profile &p, int R, bool pair, std::vector<uint32_t> &tab4q, std::vector<uint32_t> &tab_full, int *pair_slack);
+// The parts of a scan: nodes lo .. hi with R packed registers per lane.  A part with a successor ends on node
+// lo + 2 R t - 3 for a lane t - 1 (out_lane): there its last cell is the top register's in both row parities.
+struct SsvPart { int lo, hi, R, out_lane; };
+// The fewest parts that hold M nodes (parts_forced = 2 .. 4: that many, if the model has two nodes for each and they hold
+// it), among those the smallest R, parts as equal as that R allows; one part: { 1, M, ssvlong_pick_R(M, pair) }.  Empty: M is
+// beyond max_model_length().
+std::vector<SsvPart> ssvlong_plan(int M, bool pair, int parts_forced);
+// tables of nodes lo .. hi (hi = 0: the whole model); <pair>: with the virtual node hi + 1
+void ssvlong_build_tables(const Profile &p, int R, bool pair, std::vector<uint32_t> &tab4q, std::vector<uint32_t> &tab_full, int *pair_slack, int lo = 1, int hi = 0);
 int  ssvlong_capacity(int R, bool pair, bool half, int num_cu, long long *waves);      // half: binary16 cells (the default), else int16
-int  ssvlong_launch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st);
+// <bin> / <bout>: the part takes its cell 0 from the boundary buffer / leaves its last cell there
+int  ssvlong_launch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st, bool bin = false, bool bout = false);
 
 // ---- thread-per-sequence small stages (p7x_pipeline.hip)
 } // namespace p7x

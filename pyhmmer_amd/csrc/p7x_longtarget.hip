@@ -30,6 +30,26 @@ static hipStream_t lt_window_stream(DeviceCtx *ctx)
 
 struct ScanRow { int64_t pos; int strand, k, sc; };
 
+// The rows of a scan in order of (strand, position), one per row.  The parts of a scan in parts each report the best of
+// their own cells of a row: the row's cell is the one upstream would pick among them -- the highest byte score, on a tie
+// the first in the order in which p7_SSVFilter_longtarget unstripes the row (the kernel's key, with the whole model's Q16).
+static void merge_scan_rows(std::vector<ScanRow> &rows, int Q16)
+{
+  auto key = [Q16](const ScanRow &r) { return ((r.k - 1) % Q16) * 16 + (r.k - 1) / Q16; };
+  std::sort(rows.begin(), rows.end(), [&](const ScanRow &x, const ScanRow &y) {
+    if (x.strand != y.strand) return x.strand < y.strand;
+    if (x.pos != y.pos) return x.pos < y.pos;
+    if (x.sc != y.sc) return x.sc > y.sc;
+    return key(x) < key(y);
+  });
+  rows.erase(std::unique(rows.begin(), rows.end(), [](const ScanRow &x, const ScanRow &y) { return x.strand == y.strand && x.pos == y.pos; }), rows.end());
+}
+
+// A scan in parts parks one 16-bit cell per row and chunk between two parts (SsvLongArgs.bnd): 2.25 bytes per residue and
+// strand with chunks of 8 M rows and M rows of warm-up.  The buffer is held to this many bytes; a scan that wants more goes
+// in rounds of chunks, every part over the chunks of a round before the next round.
+constexpr size_t kSsvBoundaryBudget = (size_t) 256 << 20;
+
 // The device copy of a target set that its owner promised not to change (cfg.lt_resident_key): one per device, kept
 // until a set with another key arrives.  Searches hold a reference while they run, so replacing the copy never pulls it
 // from under a search still scanning it.
@@ -100,41 +120,51 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
   const bool half = !(opt >= 5 && opt <= 7);       // 5, 6, 7: the int16 flavour of the kernel with the library's choice of rows / every row / every second row
   if (!half) opt = opt == 5 ? -1 : (opt == 6 ? 3 : 4);
   bool pair = opt != 3;
-  int R = ssvlong_pick_R(p.M, pair);
-  if (R < 0) { set_error("model too long for the long-target SSV kernel (M > 6141)"); return P7X_EINVAL; }
-  std::vector<uint32_t> tab4q, tab_full;
+  const int forced = debug_opt(OPT_SSV_PARTS);
+  std::vector<SsvPart> plan = ssvlong_plan(p.M, pair, forced);
+  if (plan.empty()) { set_error(model_too_long("model too long for the long-target SSV kernel")); return P7X_EINVAL; }
   int pair_slack = 0;
-  ssvlong_build_tables(p, R, pair, tab4q, tab_full, &pair_slack);
+  {
+    std::vector<uint32_t> t4, tf;
+    ssvlong_build_tables(p, plan[0].R, false, t4, tf, &pair_slack, 1, 1);       // the loss per row is the whole model's, whatever the part
+  }
   if (pair && opt != 4 && pair_slack > kMaxPairSlack) {
     pair = false;
-    R = ssvlong_pick_R(p.M, false);
-    ssvlong_build_tables(p, R, false, tab4q, tab_full, &pair_slack);
+    plan = ssvlong_plan(p.M, false, forced);
   }
+  const size_t P = plan.size();
   std::lock_guard<std::mutex> scan_turn(ctx->lt_scan_mu);      // one scan at a time per device (see DeviceCtx)
-  DeviceBuf d_tab4q, d_full, d_comp, d_nrec, d_pos, d_strand, d_k, d_sc;
+  DeviceBuf d_comp, d_nrec, d_pos, d_strand, d_k, d_sc, d_bnd;
+  std::vector<DeviceBuf> d_tab4q(P), d_full(P);
   int st;
-  if ((st = alloc(d_tab4q, ctx, tab4q.size() * 4)) || (st = alloc(d_full, ctx, tab_full.size() * 4)) || (st = alloc(d_comp, ctx, 32)) || (st = alloc(d_nrec, ctx, 4))) return st;
+  if ((st = alloc(d_comp, ctx, 32)) || (st = alloc(d_nrec, ctx, 4))) return st;
   hipStream_t s = ctx->stream;
   std::shared_ptr<ResidentTargets> d_seq;
   bool uploaded = false;
   if ((st = resident_targets(ctx, device, resident_key, seq1, L, d_seq, &uploaded)) != P7X_OK) return st;
   if ((debug_opt(OPT_TRACE_LONGTARGET) > 0)) std::fprintf(stderr, "[lt] targets on the device: %s (%lld bytes, key %llu)\n", uploaded ? "uploaded" : "resident", (long long) L, (unsigned long long) resident_key);
-  P7X_HIP(hipMemcpyAsync(d_tab4q.as<void>(), tab4q.data(), tab4q.size() * 4, hipMemcpyHostToDevice, s));
-  P7X_HIP(hipMemcpyAsync(d_full.as<void>(), tab_full.data(), tab_full.size() * 4, hipMemcpyHostToDevice, s));
-  P7X_HIP(hipMemcpyAsync(d_comp.as<void>(), longtarget_complement(p.abc_type), 18, hipMemcpyHostToDevice, s));
+  std::vector<std::vector<uint32_t>> tab4q(P), tab_full(P);
+  {
+    for (size_t q = 0; q < P; ++q) {
+      ssvlong_build_tables(p, plan[q].R, pair && q + 1 == P, tab4q[q], tab_full[q], nullptr, plan[q].lo, plan[q].hi);
+      if ((st = alloc(d_tab4q[q], ctx, tab4q[q].size() * 4)) || (st = alloc(d_full[q], ctx, tab_full[q].size() * 4))) return st;
+      P7X_HIP(hipMemcpyAsync(d_tab4q[q].as<void>(), tab4q[q].data(), tab4q[q].size() * 4, hipMemcpyHostToDevice, s));
+      P7X_HIP(hipMemcpyAsync(d_full[q].as<void>(), tab_full[q].data(), tab_full[q].size() * 4, hipMemcpyHostToDevice, s));
+    }
+    P7X_HIP(hipMemcpyAsync(d_comp.as<void>(), longtarget_complement(p.abc_type), 18, hipMemcpyHostToDevice, s));
+  }
   // chunks: long enough that the M warm-up rows are a small overhead.  The kernel's wavefronts all stay on the device and
   // take the chunks in turn, so the number of chunks is made a multiple of the wavefronts (a last round that only some
   // of them take is paid in full: 16,384 chunks on 3,072 wavefronts were six rounds, the last a third full)
   const int nstrands_plan = strands_mask == 3 ? 2 : 1;
   long long waves = 0;
-  if ((st = ssvlong_capacity(R, pair, half, ctx->num_cu, &waves)) != P7X_OK) return st;
+  if ((st = ssvlong_capacity(plan[0].R, pair, half, ctx->num_cu, &waves)) != P7X_OK) return st;
   const int64_t rounds = std::max<int64_t>(1, (L * nstrands_plan + waves * 49152 - 1) / (waves * 49152));
   const int64_t want_chunks = (waves * rounds + nstrands_plan - 1) / nstrands_plan;             // per strand
   int chunk_len = (int) std::max<int64_t>(8 * (int64_t) p.M, std::min<int64_t>(1 << 16, (L + want_chunks - 1) / want_chunks));
   chunk_len = ((chunk_len + 63) / 64) * 64;
   const int nstrands = strands_mask == 3 ? 2 : 1;
   SsvLongArgs a{};
-  a.tab4q = d_tab4q.as<const uint32_t>(); a.tab_full = d_full.as<const uint32_t>();
   a.dsq = static_cast<const uint8_t *>(d_seq->p); a.comp = d_comp.as<const uint8_t>();
   a.L = L; a.M = p.M; a.Kp = p.Kp; a.chunk_len = chunk_len;
   a.chunks_per_strand = (L + chunk_len - 1) / chunk_len; a.nchunks = a.chunks_per_strand * nstrands;
@@ -158,6 +188,16 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
     P7X_HIP(hipStreamSynchronize(s));                       // <list> leaves scope
     a.chunk_list = d_chunks.as<const long long>(); a.nchunks = (long long) list.size();
   }
+  // a scan in parts: the boundary buffer, and the chunks of a round
+  const long long nchunks_all = a.nchunks;
+  const long long *const list_all = a.chunk_list;
+  long long per_round = nchunks_all;
+  if (P > 1) {
+    a.bnd_stride = (((long long) chunk_len + p.M + 63) / 64) * 64;                  // rows of a chunk: up to M of warm-up, then its own
+    per_round = std::max<long long>(1, std::min<long long>(nchunks_all, (long long) (kSsvBoundaryBudget / ((size_t) a.bnd_stride * 2))));
+    if ((st = alloc(d_bnd, ctx, (size_t) per_round * (size_t) a.bnd_stride * 2)) != P7X_OK) return st;
+    a.bnd = d_bnd.as<unsigned short>();
+  }
   struct Events {                     // destroyed on every way out
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Events() { if (e0) (void) hipEventDestroy(e0); if (e1) (void) hipEventDestroy(e1); }
@@ -171,7 +211,15 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
     a.rec_k = d_k.as<int>(); a.rec_sc = d_sc.as<int>(); a.rec_cap = cap;
     P7X_HIP(hipMemsetAsync(d_nrec.as<void>(), 0, 4, s));
     P7X_HIP(hipEventRecord(e0, s));
-    if ((st = ssvlong_launch(R, pair, half, a, ctx->num_cu, s)) != P7X_OK) return st;
+    for (long long c0 = 0; c0 < nchunks_all; c0 += per_round) {            // one round unless the scan is in parts
+      a.nchunks = std::min(per_round, nchunks_all - c0);
+      a.chunk_list = list_all ? list_all + c0 : nullptr; a.chunk0 = c0;
+      for (size_t q = 0; q < P; ++q) {                                     // the parts of a round in order, on the one stream
+        a.tab4q = d_tab4q[q].as<const uint32_t>(); a.tab_full = d_full[q].as<const uint32_t>();
+        a.node0 = plan[q].lo - 1; a.nloc = plan[q].hi - plan[q].lo + 1; a.out_lane = plan[q].out_lane;
+        if ((st = ssvlong_launch(plan[q].R, pair, half, a, ctx->num_cu, s, q > 0, q + 1 < P)) != P7X_OK) return st;
+      }
+    }
     P7X_HIP(hipEventRecord(e1, s));
     int nrec = 0;
     P7X_HIP(hipMemcpyAsync(&nrec, d_nrec.as<void>(), 4, hipMemcpyDeviceToHost, s));
@@ -188,7 +236,8 @@ static int scan_target(const p7x_pipeline_cfg &cfg, const Profile &p, DeviceCtx 
       }
       rows.resize((size_t) nrec);
       for (int i = 0; i < nrec; ++i) rows[(size_t) i] = ScanRow{ pos[(size_t) i], strand[(size_t) i], k[(size_t) i], sc[(size_t) i] };
-      std::sort(rows.begin(), rows.end(), [](const ScanRow &x, const ScanRow &y) { return x.strand != y.strand ? x.strand < y.strand : x.pos < y.pos; });
+      if (P > 1) merge_scan_rows(rows, p.Q16());
+      else std::sort(rows.begin(), rows.end(), [](const ScanRow &x, const ScanRow &y) { return x.strand != y.strand ? x.strand < y.strand : x.pos < y.pos; });
       return P7X_OK;
     }
     cap = nrec + 1024;              // more rows than the buffer holds: once more with room for all of them
@@ -547,7 +596,8 @@ int64_t p7x_debug_ssv_tables(const p7x_oprofile *om, int pair, int32_t *R, int32
   if (!om) { set_error("p7x_debug_ssv_tables: no profile"); return -P7X_EINVAL; }
   const Profile &p = om->p;
   const int r = ssvlong_pick_R(p.M, pair != 0);
-  if (r < 0) { set_error("model too long for the long-target SSV kernel (M > 6141)"); return -P7X_EINVAL; }
+  if (p.M > max_model_length()) { set_error(model_too_long("model too long for the long-target SSV kernel")); return -P7X_EINVAL; }
+  if (r < 0) { set_error("p7x_debug_ssv_tables: the model is scanned in parts, see p7x_debug_ssv_part_tables"); return -P7X_EINVAL; }
   std::vector<uint32_t> quads, full;
   int slack = 0;
   ssvlong_build_tables(p, r, pair != 0, quads, full, &slack);
@@ -555,6 +605,46 @@ int64_t p7x_debug_ssv_tables(const p7x_oprofile *om, int pair, int32_t *R, int32
   if (pair_slack) *pair_slack = slack;
   if (tab4q && cap_words >= quads.size()) std::copy(quads.begin(), quads.end(), tab4q);
   return (int64_t) quads.size();
+}
+
+int p7x_debug_ssv_plan(int M, int pair, int parts_forced, int32_t *lo, int32_t *hi, int32_t *R, int cap)
+{
+  const std::vector<SsvPart> plan = ssvlong_plan(M, pair != 0, parts_forced);
+  if (plan.empty()) { set_error(model_too_long("model too long for the long-target SSV kernel")); return -P7X_EINVAL; }
+  for (size_t q = 0; q < plan.size() && (int) q < cap; ++q) {
+    if (lo) lo[q] = plan[q].lo;
+    if (hi) hi[q] = plan[q].hi;
+    if (R) R[q] = plan[q].R;
+  }
+  return (int) plan.size();
+}
+
+int64_t p7x_debug_ssv_part_tables(const p7x_oprofile *om, int pair, int parts_forced, int part, int32_t *lo, int32_t *hi, int32_t *R, uint32_t *tab4q, size_t cap_words)
+{
+  if (!om) { set_error("p7x_debug_ssv_part_tables: no profile"); return -P7X_EINVAL; }
+  const Profile &p = om->p;
+  const std::vector<SsvPart> plan = ssvlong_plan(p.M, pair != 0, parts_forced);
+  if (plan.empty()) { set_error(model_too_long("model too long for the long-target SSV kernel")); return -P7X_EINVAL; }
+  if (part < 0 || (size_t) part >= plan.size()) { set_error("p7x_debug_ssv_part_tables: no such part"); return -P7X_EINVAL; }
+  const SsvPart &sp = plan[(size_t) part];
+  std::vector<uint32_t> quads, full;
+  ssvlong_build_tables(p, sp.R, pair != 0 && (size_t) part + 1 == plan.size(), quads, full, nullptr, sp.lo, sp.hi);
+  if (lo) *lo = sp.lo;
+  if (hi) *hi = sp.hi;
+  if (R) *R = sp.R;
+  if (tab4q && cap_words >= quads.size()) std::copy(quads.begin(), quads.end(), tab4q);
+  return (int64_t) quads.size();
+}
+
+int64_t p7x_debug_ssv_merge_rows(int Q16, size_t n, const int64_t *pos, const int32_t *strand, const int32_t *k, const int32_t *sc,
+                                 int64_t *out_pos, int32_t *out_strand, int32_t *out_k, int32_t *out_sc)
+{
+  if (Q16 < 1 || (n && (!pos || !strand || !k || !sc || !out_pos || !out_strand || !out_k || !out_sc))) { set_error("p7x_debug_ssv_merge_rows: bad arguments"); return -P7X_EINVAL; }
+  std::vector<ScanRow> rows(n);
+  for (size_t i = 0; i < n; ++i) rows[i] = ScanRow{ pos[i], strand[i], k[i], sc[i] };
+  merge_scan_rows(rows, Q16);
+  for (size_t i = 0; i < rows.size(); ++i) { out_pos[i] = rows[i].pos; out_strand[i] = rows[i].strand; out_k[i] = rows[i].k; out_sc[i] = rows[i].sc; }
+  return (int64_t) rows.size();
 }
 
 } // extern "C"

@@ -20,6 +20,8 @@
 // scores of A, C, G, T for both parities sit in LDS as quads of registers; degenerate residues (rare in chromosomes)
 // take a slow path through the full table in global memory.  u8 saturation at 255 is not reproduced: it can only keep a
 // cell at or above a threshold it has already reached.
+#include <climits>
+#include <cstdlib>
 #include <map>
 #include "p7x_wave.hpp"
 #include <mutex>
@@ -92,6 +94,18 @@ template <bool H> __device__ __forceinline__ int rel_half(uint32_t w, int h)
 //     node further -- for the last node that is the virtual node M + 1 of the tables, whose emission is 0.  The exact
 //     test of the repeat decides; the virtual node never counts as a cell there.
 //   * chunks are sized by the caller so that their number is a multiple of the resident wavefronts (ssvlong_capacity).
+//   * BIN / BOUT: a part of a model that one launch does not hold (ssvlong_plan).  SSV has no J state and no
+//     cross-diagonal term, so nodes above a cut node K depend on nodes 1 .. K through one number per row, the cell (i, K).
+//     A part with a successor (BOUT) leaves that cell in a.bnd after every row, warm-up rows included: the plan puts K in the
+//     top register of lane a.out_lane (high half on odd rows, low half on even ones), lane r of the wavefront collects
+//     the value of row r of a block (v_readlane and a select per row) and the block's 64 values are stored once.  A
+//     part with a predecessor (BIN) holds K as its cell 0 -- register 0 of lane 0, high half on odd rows, low half on even
+//     ones, padding otherwise -- and after every row puts the predecessor's value there (one v_bfi per row; the block's 64
+//     values are fetched one block ahead, as the residues are).  The buffer is rewritten in place: a wavefront has read
+//     a block's values before it stores that block's own.  Warm-up is the whole model's in every part, so the chain is
+//     the computation of one launch over all nodes.  PAIR across a cut: a cell at the threshold on a skipped row at node
+//     K is cell 1 of the successor one row later, at or above the lowered threshold; the successor repeats the block
+//     and its exact test counts cell 0, the node K itself.
 template <bool H> __device__ __forceinline__ bool ssv_reached(uint32_t acc, int thr_rel)        // thr_rel: above the begin score
 {
   return __any(rel_max<H>(acc) >= thr_rel) != 0;
@@ -141,9 +155,10 @@ __device__ __forceinline__ void ssv_row(uint32_t (&v)[R], const uint32_t (&e)[RE
   }
 }
 
-template <int R, bool PAIR, bool H>
+template <int R, bool PAIR, bool H, bool BIN, bool BOUT>
 __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
 {
+  constexpr bool PART = BIN || BOUT;               // the nodes of this launch are a.node0 + 1 .. a.node0 + a.nloc
   constexpr uint32_t kFloorV = H ? 0u : kFloor2;
   constexpr int R4 = (R + 3) / 4;
   constexpr int RE = 4 * R4;                       // emission registers of a row (the last quad may be partly unused)
@@ -182,9 +197,10 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
       const int g = lane * R + j, c0 = odd ? 2 * g - 1 : 2 * g;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int k = c0 + h;
+        const int kl = c0 + h;
+        const int k = PART ? kl + a.node0 : kl;
         const int sv = rel_half<H>(v[j], h);
-        if (k >= 1 && k <= a.M) {
+        if (PART ? (kl >= (BIN ? 0 : 1) && kl <= a.nloc) : (k >= 1 && k <= a.M)) {      // BIN: cell 0 is the cut node, a cell of the row
           const int val = min(255, sv + a.xB);
           const int key = ((k - 1) % a.Q16) * 16 + (k - 1) / a.Q16;
           if (val > best || (val == best && key < bestkey)) { best = val; bestkey = key; }
@@ -202,8 +218,18 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
       }
     }
   };
+  // the cut nodes after row r of a block.  bsp: the lanes' boundary-in values, one row each, in both halves; coll: lane r
+  // collects row r's boundary-out
+  const uint32_t mask_odd = BIN && lane == 0 ? 0xffff0000u : 0u, mask_even = BIN && lane == 0 ? 0x0000ffffu : 0u;
+  auto cut_cells = [&](uint32_t (&v)[R], uint32_t bsp, uint32_t &coll, int r, bool odd) {
+    if constexpr (BIN) {
+      const uint32_t b = (uint32_t) __builtin_amdgcn_readlane((int) bsp, r), m = odd ? mask_odd : mask_even;
+      v[0] = (v[0] & ~m) | (b & m);
+    }
+    if constexpr (BOUT) { const uint32_t top = (uint32_t) __builtin_amdgcn_readlane((int) v[R - 1], a.out_lane); coll = lane == r ? top : coll; }
+  };
   // 64 canonical rows; xsv = the lanes' residues times XS.  false: some group of 16 rows may have reached the threshold
-  auto fast_block = [&](uint32_t (&v)[R], uint32_t xsv) -> bool {
+  auto fast_block = [&](uint32_t (&v)[R], uint32_t xsv, uint32_t bsp, uint32_t &coll) -> bool {
     uint32_t eA[RE], eB[RE];
     load_quads(eA, (uint32_t) __builtin_amdgcn_readlane((int) xsv, 0), 0);
     for (int r0 = 0; r0 < 64; r0 += 16) {
@@ -214,9 +240,11 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
         // pays for them with half the wavefronts per SIMD (136 VGPRs instead of 77 at R = 10)
         load_quads(eB, (uint32_t) __builtin_amdgcn_readlane((int) xsv, r0 + rr + 1), 1);
         ssv_row<R, true, !PAIR, RE, H>(v, eA, acc0, acc1);
+        if constexpr (PART) cut_cells(v, bsp, coll, r0 + rr, true);
         __builtin_amdgcn_sched_barrier(0);
         load_quads(eA, (uint32_t) __builtin_amdgcn_readlane((int) xsv, (r0 + rr + 2) & 63), 0);      // the last one of a block is not used
         ssv_row<R, false, true, RE, H>(v, eB, acc0, acc1);
+        if constexpr (PART) cut_cells(v, bsp, coll, r0 + rr + 1, false);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (ssv_reached<H>(H ? h_max_u(acc0, acc1) : pk_max_u(acc0, acc1), thr_fast)) return false;
@@ -225,7 +253,7 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
   };
 
   for (long long chi = wave; chi < a.nchunks; chi += nwaves) {
-    const long long ch = a.chunk_list ? a.chunk_list[chi] : chi;
+    const long long ch = a.chunk_list ? a.chunk_list[chi] : (PART ? chi + a.chunk0 : chi);
     const int strand = a.strand0 + (int) (ch / a.chunks_per_strand);
     const long long c0 = (ch % a.chunks_per_strand) * (long long) a.chunk_len;
     const long long first = c0 + 1, last = min(a.L, c0 + a.chunk_len);
@@ -244,7 +272,17 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
     auto on_strand = [&](uint32_t x) -> uint32_t {
       return strand == 0 ? x : (x < 4 ? 3u - x : (x >= (uint32_t) a.Kp ? x : (uint32_t) a.comp[x]));
     };
-    uint32_t raw_next = fetch(warm);
+    // the cut node's cells of 64 rows, one per lane, fetched as the residues are; row i of the chunk is bnd[i - warm]
+    unsigned short *bnd = PART ? a.bnd + chi * a.bnd_stride : nullptr;
+    auto fetch_cut = [&](long long i0) -> uint32_t {
+      if (i0 + lane > last) return 0u;
+      return bnd[i0 - warm + lane];
+    };
+    uint32_t raw_next = fetch(warm), cut_next = 0u, coll = 0u;
+    if constexpr (BIN) cut_next = fetch_cut(warm);
+    auto store_cut = [&](long long i0, int nrow) {      // row r of a block is odd iff r is even
+      if (lane < nrow) bnd[i0 - warm + lane] = (unsigned short) ((lane & 1) ? coll : coll >> 16);
+    };
     for (long long i0 = warm; i0 <= last; i0 += 64) {     // i0 - warm is a multiple of 64: row r of a block is odd iff r is even
       const int nrow = (int) min(64LL, last - i0 + 1);
       // the bytes fetched during the previous block are waited for HERE, before the next fetch is issued: left to the
@@ -252,11 +290,16 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
       __builtin_amdgcn_s_waitcnt(0x0f70);            // vmcnt(0); expcnt and lgkmcnt unconstrained
       const uint32_t res = on_strand(raw_next);
       raw_next = fetch(i0 + 64);
+      uint32_t bsp = 0u;
+      if constexpr (BIN) { bsp = cut_next * 0x10001u; cut_next = fetch_cut(i0 + 64); }
       if (nrow == 64 && __all(res < 4u)) {
         uint32_t saved[R];
 #pragma unroll
         for (int j = 0; j < R; ++j) saved[j] = v[j];
-        if (fast_block(v, res * (uint32_t) XS)) continue;
+        if (fast_block(v, res * (uint32_t) XS, bsp, coll)) {
+          if constexpr (BOUT) store_cut(i0, nrow);
+          continue;
+        }
 #pragma unroll
         for (int j = 0; j < R; ++j) v[j] = saved[j];
       }
@@ -282,9 +325,15 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
             if (h == 0) ssv_row<R, true, true, R, H>(v, e, acc0, acc1); else ssv_row<R, false, true, R, H>(v, e, acc0, acc1);
           }
           const long long i = i0 + r + h;
+          if constexpr (PART) cut_cells(v, bsp, coll, r + h, h == 0);
+          if constexpr (BIN) {          // cell 0 is not among the cells the row folded into its maximum
+            if (i >= first && (rel_half<H>((uint32_t) __builtin_amdgcn_readlane((int) bsp, r + h), 0) >= thr_exact
+                               || ssv_reached<H>(H ? h_max_u(acc0, acc1) : pk_max_u(acc0, acc1), thr_exact))) report(v, h == 0, i, strand);
+          } else
           if (i >= first && ssv_reached<H>(H ? h_max_u(acc0, acc1) : pk_max_u(acc0, acc1), thr_exact)) report(v, h == 0, i, strand);
         }
       }
+      if constexpr (BOUT) store_cut(i0, nrow);
     }
   }
 }
@@ -300,18 +349,64 @@ int ssvlong_pick_R(int M, bool virtual_node)
   return -1;
 }
 
+// The parts of a scan.  One launch holds cells up to 128 R - 2 (ssvlong_pick_R), at most 6,142 with the widest instantiation:
+// its emission quads fill 96 KiB of LDS, and twice as many registers would want 192 KiB of the CU's 160.  A longer model is
+// cut.  A part with a successor must hold its last node in both row parities and in a register known when the kernel is
+// compiled: an even number of nodes n = 2 g puts it in global register g on every row (high half on odd rows, low half on
+// even ones), and g = R t - 1 is the top register of lane t - 1.  So such a part has 2 R t - 2 nodes, t = 1 .. 64; the last
+// part takes the rest, with the virtual node of PAIR, and the smallest R that holds it.
+std::vector<SsvPart> ssvlong_plan(int M, bool pair, int parts_forced)
+{
+  std::vector<SsvPart> out;
+  if (M < 1 || M > max_model_length()) return out;
+  auto with = [&](int P) -> bool {
+    if (P == 1) {
+      const int R = ssvlong_pick_R(M, pair);
+      if (R < 0) return false;
+      out.assign(1, SsvPart{ 1, M, R, 0 });
+      return true;
+    }
+    for (int R : kSsvR) {
+      int best_t = 0, best_d = INT_MAX;
+      for (int t = 1; t <= 64; ++t) {
+        const int n = 2 * R * t - 2, rest = M - (P - 1) * n;
+        if (rest < 1) break;
+        if (rest + (pair ? 1 : 0) > 128 * R - 2) continue;
+        if (std::abs(n - rest) < best_d) { best_d = std::abs(n - rest); best_t = t; }
+      }
+      if (!best_t) continue;
+      const int n = 2 * R * best_t - 2;
+      out.clear();
+      for (int q = 0; q + 1 < P; ++q) out.push_back(SsvPart{ q * n + 1, (q + 1) * n, R, best_t - 1 });
+      out.push_back(SsvPart{ (P - 1) * n + 1, M, ssvlong_pick_R(M - (P - 1) * n, pair), 0 });
+      return true;
+    }
+    return false;
+  };
+  if (parts_forced >= 2 && parts_forced <= 4 && M >= 2 * parts_forced && with(parts_forced)) return out;
+  for (int P = 1; P <= 8; ++P) if (with(P)) return out;
+  out.clear();
+  return out;
+}
+
 // tables: pairs (lo, hi) of signed emission scores s[x][k] = bias - rb[x][k] in byte units, kNegPad outside 1..M.
 // odd rows: register g = cells (2g-1, 2g); even rows: (2g, 2g+1); g = lane*R + j.
 //   tab4q    [parity][x < 4][q][lane] uint4: registers 4q .. 4q+3 of the lane for A, C, G, T (0 beyond R)
 //   tab_full [parity][Kp][R][64] uint32: every residue code (degenerate residues, read from global memory)
 // <virtual_node> (PAIR): node M+1 exists with emission 0 for every residue, so that a score that reached the last node
 // is still there one row later; it never counts as a cell.  pair_slack: the most a cell can lose in one canonical row.
-void ssvlong_build_tables(const Profile &p, int R, bool virtual_node, std::vector<uint32_t> &tab4q, std::vector<uint32_t> &tab_full, int *pair_slack)
+// A part of a scan (nodes lo .. hi; hi = 0: the whole model): cell c of the layout is node lo - 1 + c, kNegPad outside
+// lo .. hi -- cell 0, where the kernel puts the cut node's score, included --, the virtual node is hi + 1, and pair_slack
+// stays the whole model's.
+void ssvlong_build_tables(const Profile &p, int R, bool virtual_node, std::vector<uint32_t> &tab4q, std::vector<uint32_t> &tab_full, int *pair_slack, int lo, int hi)
 {
-  auto sval = [&](int x, int k) -> int {
-    if (virtual_node && k == p.M + 1 && x < p.Kp) return 0;
-    if (x >= p.Kp || k < 1 || k > p.M) return kNegPad;
-    return (int) p.bias_b - (int) p.rb[(size_t) x * (p.M + 1) + k];
+  if (hi <= 0) hi = p.M;
+  auto node = [&](int x, int k) -> int { return (int) p.bias_b - (int) p.rb[(size_t) x * (p.M + 1) + k]; };
+  auto sval = [&](int x, int c) -> int {
+    const int k = lo - 1 + c;
+    if (virtual_node && k == hi + 1 && x < p.Kp) return 0;
+    if (x >= p.Kp || k < lo || k > hi) return kNegPad;
+    return node(x, k);
   };
   auto pack = [](int lo, int hi) -> uint32_t { return ((uint32_t) (uint16_t) (int16_t) lo) | ((uint32_t) (uint16_t) (int16_t) hi << 16); };
   const int R4 = (R + 3) / 4;
@@ -328,17 +423,17 @@ void ssvlong_build_tables(const Profile &p, int R, bool virtual_node, std::vecto
         }
   if (pair_slack) {
     int worst = 0;
-    for (int x = 0; x < 4 && x < p.Kp; ++x) for (int k = 1; k <= p.M; ++k) worst = std::max(worst, -sval(x, k));
+    for (int x = 0; x < 4 && x < p.Kp; ++x) for (int k = 1; k <= p.M; ++k) worst = std::max(worst, -node(x, k));
     *pair_slack = worst;
   }
 }
 
 // cap_waves != NULL: no launch, only the number of wavefronts the device holds at once
-template <int R, bool PAIR, bool H>
+template <int R, bool PAIR, bool H, bool BIN, bool BOUT>
 static int launch_ssv_quad(const SsvLongArgs &a, int num_cu, hipStream_t st, long long *cap_waves)
 {
   const size_t lds = (size_t) 2 * 4 * ((R + 3) / 4) * 64 * 16;
-  auto kern = ssvlong_quad_kernel<R, PAIR, H>;
+  auto kern = ssvlong_quad_kernel<R, PAIR, H, BIN, BOUT>;
   static std::map<int, int> per_cu_by_device;       // the LDS opt-in is a per-device attribute of the kernel: looked up once per device
   static std::mutex mu;
   int per_cu = 0;
@@ -361,14 +456,27 @@ static int launch_ssv_quad(const SsvLongArgs &a, int num_cu, hipStream_t st, lon
   return P7X_OK;
 }
 
-static int ssvlong_quad_dispatch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st, long long *cap_waves)
+// every instantiation of one register count: rows x cells x the part's place in the chain
+template <int R>
+static int ssvlong_flavour_dispatch(bool pair, bool half, bool bin, bool bout, const SsvLongArgs &a, int num_cu, hipStream_t st, long long *cap_waves)
 {
-#define P7X_SQ(RR) case RR: return half ? (pair ? launch_ssv_quad<RR, true, true>(a, num_cu, st, cap_waves) : launch_ssv_quad<RR, false, true>(a, num_cu, st, cap_waves)) \
-                                       : (pair ? launch_ssv_quad<RR, true, false>(a, num_cu, st, cap_waves) : launch_ssv_quad<RR, false, false>(a, num_cu, st, cap_waves));
+#define P7X_SF(P, H) \
+  if (pair == P && half == H) { \
+    if (bin) return bout ? launch_ssv_quad<R, P, H, true, true>(a, num_cu, st, cap_waves) : launch_ssv_quad<R, P, H, true, false>(a, num_cu, st, cap_waves); \
+    return bout ? launch_ssv_quad<R, P, H, false, true>(a, num_cu, st, cap_waves) : launch_ssv_quad<R, P, H, false, false>(a, num_cu, st, cap_waves); \
+  }
+  P7X_SF(true, true) P7X_SF(false, true) P7X_SF(true, false) P7X_SF(false, false)
+#undef P7X_SF
+  return P7X_EINVAL;
+}
+
+static int ssvlong_quad_dispatch(int R, bool pair, bool half, bool bin, bool bout, const SsvLongArgs &a, int num_cu, hipStream_t st, long long *cap_waves)
+{
+#define P7X_SQ(RR) case RR: return ssvlong_flavour_dispatch<RR>(pair, half, bin, bout, a, num_cu, st, cap_waves);
   switch (R) {
     P7X_SQ(2) P7X_SQ(3) P7X_SQ(4) P7X_SQ(5) P7X_SQ(6) P7X_SQ(7) P7X_SQ(8) P7X_SQ(9) P7X_SQ(10) P7X_SQ(11) P7X_SQ(12) P7X_SQ(14) P7X_SQ(16)
     P7X_SQ(20) P7X_SQ(24) P7X_SQ(32) P7X_SQ(48)
-    default: set_error("model too long for the long-target SSV kernel (M > 6141)"); return P7X_EINVAL;
+    default: set_error(model_too_long("model too long for the long-target SSV kernel")); return P7X_EINVAL;
   }
 #undef P7X_SQ
 }
@@ -377,12 +485,12 @@ static int ssvlong_quad_dispatch(int R, bool pair, bool half, const SsvLongArgs 
 int ssvlong_capacity(int R, bool pair, bool half, int num_cu, long long *waves)
 {
   SsvLongArgs none{};
-  return ssvlong_quad_dispatch(R, pair, half, none, num_cu, nullptr, waves);
+  return ssvlong_quad_dispatch(R, pair, half, false, false, none, num_cu, nullptr, waves);
 }
 
-int ssvlong_launch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st)
+int ssvlong_launch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st, bool bin, bool bout)
 {
-  return ssvlong_quad_dispatch(R, pair, half, a, num_cu, st, nullptr);
+  return ssvlong_quad_dispatch(R, pair, half, bin, bout, a, num_cu, st, nullptr);
 }
 
 } // namespace p7x
