@@ -264,6 +264,21 @@ def domains(op, seq, do_null2=True, seed=42, ensembles=True, want_sequence=False
     return out[:n].copy(), tuple(int(c) for c in counts)
 
 
+def dd_unihit_rows(op, seq):
+    """p7o_dd_unihit_rows: Forward, Backward and decoding of the whole sequence in unihit mode under its own length model.
+    Returns (status, fx, bx): status bit 0 = decoding's scale product overflowed, bit 1 = Forward's score is not finite;
+    fx / bx = (L+1) x [E N J B C SCALE].  Backward took its own scale factors iff fx[:, 5] != bx[:, 5] in some row."""
+    l = lib()
+    l.p7o_dd_unihit_rows.restype = C.c_int
+    l.p7o_dd_unihit_rows.argtypes = [C.POINTER(Profile), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    d = op._dsq(seq)
+    fx = np.zeros((len(seq) + 1, 6), dtype=np.float32)
+    bx = np.zeros_like(fx)
+    st = l.p7o_dd_unihit_rows(op.ptr, d.ctypes.data, len(seq), fx.ctypes.data, bx.ctypes.data)
+    assert st >= 0, st
+    return st, fx, bx
+
+
 def domains_single(op, seq, do_null2=True):
     """The regions that hold one domain only: (envelopes, (regions, single-domain envelopes, ensemble regions))."""
     envs, counts = domains(op, seq, do_null2=do_null2, ensembles=False)

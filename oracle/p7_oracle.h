@@ -139,6 +139,12 @@ void  p7o_lt_envelope_background(const P7O_PROFILE *p, const uint8_t *env, int64
 int64_t p7o_domains(P7O_PROFILE *p, const uint8_t *dsq, int L, const float *fx, const float *bx, const uint8_t *degen,
                     int do_null2, uint32_t seed, int ensembles, double *out, int64_t cap, int64_t *counts, float fwdsc, double *seqout);
 
+/* the whole sequence in unihit mode under its own length model (dd_forward, dd_backward, dd_decoding: what hmmalign and an
+ * envelope's rescoring run): fx / bx = (L+1) x [E N J B C SCALE] rows of the two passes.  Returns dd_decoding's status (1: the
+ * scale product overflowed), + 2 when Forward's score is not finite, or -1.  Backward took its own scale factors iff some row
+ * has bx's SCALE != fx's. */
+int p7o_dd_unihit_rows(P7O_PROFILE *p, const uint8_t *dsq, int L, float *fx, float *bx);
+
 /* domain definition of one Forward-passing window of a long target (rescore_isolated_domain with long_target = TRUE: own
  * length model, composition-adjusted emissions, the envelope cut back to its alignment + max_env_extra): rows as p7o_domains,
  * columns 0-8 and 12, window coordinates. */

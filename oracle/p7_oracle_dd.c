@@ -1232,6 +1232,34 @@ int64_t p7o_domains(P7O_PROFILE *p, const uint8_t *dsq, int L, const float *fx, 
   return failed ? -1 : nout;
 }
 
+/* Forward, Backward and decoding of the whole sequence in unihit mode under its own length model, as hmmalign and the
+ * rescoring of an envelope run them.  fx / bx: (L+1) x [E N J B C SCALE], the special-state rows as the two passes left them
+ * (Backward's before decoding overwrites them) with the factor each row was divided by.  Backward took its own scale factors
+ * iff some row's bx scale differs from its fx scale.  Returns dd_decoding's status (1: the scale product is not finite), + 2
+ * when Forward's score is not a finite number, or -1. */
+int p7o_dd_unihit_rows(P7O_PROFILE *p, const uint8_t *dsq, int L, float *fx, float *bx)
+{
+  DDModel uni;
+  if (L < 1 || ddmodel_build(p, L, 0, &uni) != 0) return -1;
+  DDMatrix f, b;
+  int status = -1;
+  memset(&b, 0, sizeof(b));
+  if (ddmx_alloc(&f, L, uni.M) == 0 && ddmx_alloc(&b, L, uni.M) == 0) {
+    float sc;
+    const int bad = dd_forward(&uni, dsq, L, &f, &sc);
+    dd_backward(&uni, dsq, L, &f, &b);
+    for (int i = 0; i <= L; i++) {
+      float *r = fx + (size_t) i * 6, *s = bx + (size_t) i * 6;
+      r[0] = f.xE[i]; r[1] = f.xN[i]; r[2] = f.xJ[i]; r[3] = f.xB[i]; r[4] = f.xC[i]; r[5] = f.scale[i];
+      s[0] = b.xE[i]; s[1] = b.xN[i]; s[2] = b.xJ[i]; s[3] = b.xB[i]; s[4] = b.xC[i]; s[5] = b.scale[i];
+    }
+    status = dd_decoding(&uni, L, &f, &b) | (bad ? 2 : 0);
+  }
+  ddmx_free(&f); ddmx_free(&b);
+  ddmodel_free(&uni);
+  return status;
+}
+
 /* p7_alidisplay_Create (p7_alidisplay.c) for the one domain of an envelope's optimal-accuracy trace: the states between B
  * and E from the first to the last match state, one column each.  model: the consensus letter of the node for match and delete states, '.' for inserts; mline: the
  * model's letter when the residue is the consensus residue, '+' when its emission odds exceed 1, else a blank; aseq: the

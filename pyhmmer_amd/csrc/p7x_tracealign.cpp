@@ -50,7 +50,7 @@ bool pp_near_boundary(double mean, int M)
   return std::fabs(v - std::nearbyint(v)) < (double) align_pp_guard(M) * 10.0;
 }
 
-// the host twin for a set of sequences, in parallel; first error wins (its sequence index in *bad)
+// the host twin for a set of sequences, in parallel; the error of the lowest sequence index wins (that index in *bad)
 int host_traces(const Profile &p, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, const std::vector<int> &which,
                 std::vector<AlignTrace> &out, int64_t *bad, int threads = 0)
 {
@@ -62,9 +62,12 @@ int host_traces(const Profile &p, const uint8_t *dsq, const int64_t *offsets, co
     std::memcpy(seq.data() + 1, dsq + offsets[t], (size_t) lengths[t]);
     st[(size_t) w] = align_trace_upstream(p, seq.data(), lengths[t], out[(size_t) t]);
   });
+  // the failure reported is that of the lowest input index, whatever order <which> lists the sequences in (the device path
+  // lists what it flagged longest first, the test seam in input order: both name the same sequence)
+  int first = P7X_OK;
   for (size_t w = 0; w < which.size(); ++w)
-    if (st[w] != P7X_OK) { *bad = which[w]; return st[w]; }
-  return P7X_OK;
+    if (st[w] != P7X_OK && (first == P7X_OK || which[w] < *bad)) { *bad = which[w]; first = st[w]; }
+  return first;
 }
 
 int report_host_error(int st, int64_t idx, int L)
