@@ -504,9 +504,19 @@ int      p7x_tophits_get_ensemble_counts(const p7x_tophits *th, int64_t *sampled
  * P7X_EMEM when one sequence alone does not fit the workspace budget ("align_workspace_gb").  host_threads: workers of
  * the host twin (hmmalign's cpus; 0: the library's default). */
 typedef struct p7x_traces p7x_traces;
-enum { P7X_TRACE_HAS_PP = 1, P7X_TRACE_DEVICE = 2 };          /* p7x_traces_get origin bits */
+enum { P7X_TRACE_HAS_PP = 1, P7X_TRACE_DEVICE = 2, P7X_TRACE_LOGSPACE = 4 };     /* p7x_traces_get origin bits */
 int     p7x_tracealign_compute(const p7x_oprofile *om, int device, const uint8_t *dsq, const int64_t *offsets,
                                const int32_t *lengths, size_t n, int host_threads, p7x_traces **out);
+/* The same with options (the call above passes flags = 0).  P7X_ALIGN_LOGSPACE: a sequence whose Backward leaves Forward's
+ * scale factors (row sum xB > 1e16: two strong domains of one family), or whose posterior decoding overflows, is aligned
+ * by the float64 log-space path instead -- nothing scaled, exact log-sums, optimal accuracy in float64 on the float64
+ * posteriors; on the device (p7x_alignlog.hip), with the host log twin (p7x_logdp.cpp) for the traces the device flags
+ * and under "host_align".  Such traces carry P7X_TRACE_LOGSPACE, their posteriors are the float64 ones rounded to float,
+ * and no sequence raises P7X_ERANGE.  Every other sequence takes the scaled path unchanged.  The test seam
+ * "align_logspace" = 1 sends every non-empty sequence through the log-space path, whatever the flag. */
+enum { P7X_ALIGN_LOGSPACE = 1 };
+int     p7x_tracealign_compute_opts(const p7x_oprofile *om, int device, const uint8_t *dsq, const int64_t *offsets,
+                                    const int32_t *lengths, size_t n, int host_threads, int flags, p7x_traces **out);
 /* Trace accessors (Traces.__getitem__, Trace.M / L / posterior_probabilities, plan7.pyx:9280-9540): N steps in forward
  * order (P7_TRACE st / k / i / pp), sc2 = Forward score and optimal-accuracy score (nats), the device's status word (0
  * for host-twin traces), origin bits.  copy: st[N] k[N] i[N] pp[N], any of them NULL. */
@@ -515,6 +525,8 @@ int64_t p7x_traces_nflagged(const p7x_traces *tr);           /* device traces th
 /* out4: traces kept from the device, device traces the host twin repeated, device rounds, the largest device workspace
  * (bytes) a round laid out -- at most the budget ("align_workspace_gb") */
 int     p7x_traces_stats(const p7x_traces *tr, int64_t out4[4]);
+/* out2: sequences the log-space path aligned, and of those the device traces its host twin repeated */
+int     p7x_traces_logspace_stats(const p7x_traces *tr, int64_t out2[2]);
 int     p7x_traces_get(const p7x_traces *tr, int64_t idx, int32_t *N, int32_t *M, int32_t *L, float *sc2, int32_t *status, uint8_t *origin);
 int     p7x_traces_copy(const p7x_traces *tr, int64_t idx, int8_t *st, int32_t *k, int32_t *i, float *pp);
 void    p7x_traces_destroy(p7x_traces *tr);
@@ -522,7 +534,7 @@ void    p7x_traces_destroy(p7x_traces *tr);
 /* The multiple alignment of traces (TraceAligner.align_traces, plan7.pyx:9832-9925, upstream p7_tracealign_Seqs):
  * traces concatenated (toff[n + 1]), origin[n] as above (P7X_TRACE_HAS_PP: the row gets a PP line; with om != NULL a
  * PP_cons column within the guard of a digit boundary is averaged again over host-twin posteriors of its P7X_TRACE_DEVICE
- * rows), sequences as for p7x_tracealign_compute, cs = the model's CS line [M+2] or NULL (-> SS_cons).  Rows in text
+ * rows, the log twin's for rows with P7X_TRACE_LOGSPACE), sequences as for p7x_tracealign_compute, cs = the model's CS line [M+2] or NULL (-> SS_cons).  Rows in text
  * form; P7X_MSA_DIGITIZE is the caller's (easel.DigitalMSA). */
 enum { P7X_MSA_TRIM = 1, P7X_MSA_ALL_CONSENSUS_COLS = 2, P7X_MSA_DIGITIZE = 4 };     /* p7_TRIM, p7_ALL_CONSENSUS_COLS, p7_DIGITIZE */
 typedef struct p7x_msa p7x_msa;

@@ -18,7 +18,7 @@ CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libp7x.so"
 
 SOURCES = ["p7x_profile.cpp", "p7x_device.hip", "p7x_devmem.hip", "p7x_devimage.hip", "p7x_msv.hip", "p7x_vitfwd.hip", "p7x_vitpk.hip", "p7x_fwdpk.hip", "p7x_envelope.hip", "p7x_ensemble.hip", "p7x_ssvlong.hip", "p7x_longtarget.hip",
-           "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp", "p7x_builder.cpp", "p7x_calibrate.hip"]
+           "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_logdp.cpp", "p7x_alignlog.hip", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp", "p7x_builder.cpp", "p7x_calibrate.hip"]
 
 
 def _hipcc() -> str:
@@ -266,6 +266,8 @@ _SIGNATURES = {
     "p7x_fasta_parse": (C.c_int, [_VP, C.c_size_t, _VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                   _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_size_t)]),
     "p7x_tracealign_compute": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_size_t, C.c_int, C.POINTER(_VP)]),
+    "p7x_tracealign_compute_opts": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "p7x_traces_logspace_stats": (C.c_int, [_VP, _VP]),
     "p7x_traces_count": (C.c_int64, [_VP]),
     "p7x_traces_nflagged": (C.c_int64, [_VP]),
     "p7x_traces_stats": (C.c_int, [_VP, _VP]),

@@ -142,6 +142,11 @@ std::unique_ptr<EnvelopeScorer> make_device_envelope_scorer(DeviceCtx *ctx, cons
 // hmmalign (p7x_align.hip): requests are whole sequences (i = 1, j = L); the results carry float posteriors and no null2
 std::unique_ptr<EnvelopeScorer> make_device_align_scorer(DeviceCtx *ctx, const p7x_seqdb *db, float oa_guard);
 size_t align_budget_bytes();           // HBM budget of its workspace (24 GiB or half the free memory; option "align_workspace_gb")
+// hmmalign's float64 log-space kernel (p7x_alignlog.hip): sequences <which> (caller indices, longest first) of <db>;
+// out[t] / status[t] (0: the trace is in; bit 6: a close call, the host log twin repeats it; bit 2: failure) for each
+struct AlignTrace;
+int device_align_logspace(const p7x_oprofile *om, DeviceCtx *ctx, const p7x_seqdb *db, const std::vector<int> &which,
+                          std::vector<AlignTrace> &out, std::vector<int32_t> &status, int64_t *nrounds, int64_t *work_bytes);
 std::unique_ptr<EnsembleRunner> make_device_ensemble_runner(DeviceCtx *ctx, const p7x_seqdb *db, float guard);
 
 } // namespace p7x

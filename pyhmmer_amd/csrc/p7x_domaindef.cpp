@@ -1478,7 +1478,7 @@ float host_filter_null_score(const Profile &p, const uint8_t *dsq1, int L, bool 
 // steps of rescore_isolated_domain() without null2, in upstream's summation order unless <order> says otherwise (0
 // upstream, 1 the device's, -1 the "host_order" seam).  dsq1[1..L]; the trace comes out in forward order.  P7X_ERANGE:
 // p7_Decoding overflowed.
-int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order)
+int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order, bool stop_on_own_scales)
 {
   out = AlignTrace{};
   if (L <= 0) return P7X_OK;                    // an empty sequence: an empty trace
@@ -1492,11 +1492,27 @@ int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrac
   int st = forward_full(om, dsq1, L, ws.fwd, &out.fwdsc);
   if (st != P7X_OK) return st;
   if ((st = backward_full(om, dsq1, L, ws.fwd, ws.bck, nullptr)) != P7X_OK) return st;
+  if (stop_on_own_scales && ws.bck.own_scales) return P7X_ERANGE;
   if (decoding(om, ws.fwd, ws.bck) == P7X_ERANGE) return P7X_ERANGE;
   optimal_accuracy(om, ws.bck, ws.fwd, &out.oasc);
   if (oa_trace(om, ws.bck, ws.fwd, ws.tr) != P7X_OK) return P7X_EINVAL;
   out.st = ws.tr.st; out.k = ws.tr.k; out.i = ws.tr.i; out.pp = ws.tr.pp;
   return P7X_OK;
+}
+
+// The event that sends a sequence to hmmalign's log-space path, without the alignment: Forward's and Backward's special rows
+// in upstream's order on two rolling DP rows, as the parsers run them, but unihit with the sequence's own length model.
+bool align_leaves_forward_scales(const Profile &p, const uint8_t *dsq1, int L)
+{
+  if (L <= 0) return false;
+  Model om{ &p, p.M, {} };
+  om.prepare(0);
+  om.configure(false, L);
+  thread_local std::vector<float> fx, bx;
+  RowsOf f(fx), b(bx);
+  if (forward_rows_upstream(om, dsq1, L, f.mx, nullptr, striped_scratch()) != P7X_OK) return true;
+  if (backward_rows_upstream(om, dsq1, L, f.mx.x.data(), b.mx, nullptr, striped_scratch()) != P7X_OK) return true;
+  return b.mx.own_scales;
 }
 
 // A device trace (traceback order, EnvelopeResult's packing: state | k << 8) in forward order, as p7_trace_Reverse leaves it

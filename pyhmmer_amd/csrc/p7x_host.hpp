@@ -87,7 +87,13 @@ uint32_t fast_rng_state(uint32_t seed);          // esl_randomness_Init for the 
 int parser_rows_upstream(const Profile &p, const uint8_t *dsq, int L, std::vector<float> &fx, std::vector<float> &bx);
 // hmmalign's host twin (p7x_domaindef.cpp): the trace of one whole sequence, forward order, float posteriors
 struct AlignTrace { std::vector<int8_t> st; std::vector<int> k, i; std::vector<float> pp; float fwdsc = 0.0f, oasc = 0.0f; };
-int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order = 0);
+// stop_on_own_scales: P7X_ERANGE as soon as Backward has left Forward's scale factors (the trigger of the log-space path)
+int align_trace_upstream(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out, int order = 0, bool stop_on_own_scales = false);
+// the trigger alone, from the rows-only engines (no DP matrix): does the sequence's unihit Backward leave Forward's scale
+// factors (or either pass its float32 range)?
+bool align_leaves_forward_scales(const Profile &p, const uint8_t *dsq1, int L);
+// ... and its float64 log-space twin (p7x_logdp.cpp): nothing is scaled, nothing overflows
+int align_trace_logspace(const Profile &p, const uint8_t *dsq1, int L, AlignTrace &out);
 void align_trace_from_device(const uint32_t *ta, const int32_t *ti, const float *tp, int n, AlignTrace &out);
 
 // p7_domaindef_ByPosteriorHeuristics (p7_domaindef.pxd:69-72).  dsq is 1-indexed (dsq[1..L]);

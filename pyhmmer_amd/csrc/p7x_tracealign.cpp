@@ -26,6 +26,8 @@ struct p7x_traces {
   int64_t nflagged = 0;                // device traces the host twin repeated
   int64_t nrounds = 0;                 // device rounds (launches of the alignment kernel)
   int64_t work_bytes = 0;              // the largest device workspace a round laid out
+  int64_t nlogspace = 0;               // sequences aligned by the float64 log-space path (P7X_ALIGN_LOGSPACE)
+  int64_t nlogspace_flagged = 0;       // ... of those, device traces the host log twin repeated
 };
 
 struct p7x_msa {
@@ -50,9 +52,12 @@ bool pp_near_boundary(double mean, int M)
   return std::fabs(v - std::nearbyint(v)) < (double) align_pp_guard(M) * 10.0;
 }
 
-// the host twin for a set of sequences, in parallel; the error of the lowest sequence index wins (that index in *bad)
+// the host twin for a set of sequences, in parallel; the error of the lowest sequence index wins (that index in *bad).
+// twin: the scaled float32 engines in upstream's order, the same giving up (P7X_ERANGE) as soon as Backward leaves Forward's
+// scale factors, or the float64 log-space twin.  each: the sequences' own statuses, in <which>'s order.
+enum class Twin { Scaled, ScaledOrLeave, Log };
 int host_traces(const Profile &p, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, const std::vector<int> &which,
-                std::vector<AlignTrace> &out, int64_t *bad, int threads = 0)
+                std::vector<AlignTrace> &out, int64_t *bad, int threads = 0, Twin twin = Twin::Scaled, std::vector<int> *each = nullptr)
 {
   std::vector<int> st(which.size(), P7X_OK);
   const int nthreads = std::max(1, std::min<int>(threads > 0 ? threads : tophits_usable_cpus(), (int) which.size()));
@@ -60,13 +65,15 @@ int host_traces(const Profile &p, const uint8_t *dsq, const int64_t *offsets, co
     const int t = which[(size_t) w];
     std::vector<uint8_t> seq((size_t) lengths[t] + 2, 255);           // 1-based, sentinel-framed
     std::memcpy(seq.data() + 1, dsq + offsets[t], (size_t) lengths[t]);
-    st[(size_t) w] = align_trace_upstream(p, seq.data(), lengths[t], out[(size_t) t]);
+    st[(size_t) w] = twin == Twin::Log ? align_trace_logspace(p, seq.data(), lengths[t], out[(size_t) t])
+                                       : align_trace_upstream(p, seq.data(), lengths[t], out[(size_t) t], 0, twin == Twin::ScaledOrLeave);
   });
   // the failure reported is that of the lowest input index, whatever order <which> lists the sequences in (the device path
   // lists what it flagged longest first, the test seam in input order: both name the same sequence)
   int first = P7X_OK;
   for (size_t w = 0; w < which.size(); ++w)
     if (st[w] != P7X_OK && (first == P7X_OK || which[w] < *bad)) { *bad = which[w]; first = st[w]; }
+  if (each) *each = std::move(st);
   return first;
 }
 
@@ -166,16 +173,13 @@ struct SeqdbDeleter { void operator()(p7x_seqdb *db) const { p7x_seqdb_destroy(d
 
 // Device path: sequences longest first, in rounds of lengths within a factor of two (the workspace of a wavefront is sized
 // for the longest sequence of its round); the envelope driver runs each round on a leased stream within the HBM budget.
-int device_traces(const p7x_oprofile *om, int device, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, size_t n,
-                  p7x_traces &out, std::vector<int> &redo)
+// logq (the log-space path is on): the sequences whose decoding overflowed (status bit 1) -- the log kernel's, not the
+// scaled twin's.
+int device_traces(const p7x_oprofile *om, DeviceCtx *ctx, const p7x_seqdb *sdb, const int32_t *lengths, size_t n,
+                  p7x_traces &out, std::vector<int> &redo, std::vector<int> *logq)
 {
   const Profile &p = om->p;
-  DeviceCtx *ctx = nullptr;
-  int st = get_ctx(device, &ctx);
-  if (st != P7X_OK) return st;
-  p7x_seqdb *raw = nullptr;
-  if ((st = p7x_seqdb_create(device, p.abc_type, dsq, offsets, lengths, n, &raw)) != P7X_OK) return st;
-  std::unique_ptr<p7x_seqdb, SeqdbDeleter> db(raw);
+  int st = P7X_OK;
   std::vector<int> order;
   for (size_t t = 0; t < n; ++t) if (lengths[t] > 0) order.push_back((int) t);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return lengths[x] > lengths[y]; });
@@ -202,7 +206,7 @@ int device_traces(const p7x_oprofile *om, int device, const uint8_t *dsq, const 
     }
     EnvelopeJob job;
     job.om = om; job.req = &req; job.targets = &targets;
-    auto scorer = make_device_align_scorer(ctx, db.get(), kAlignGuard);     // one lease per round (released when it ends)
+    auto scorer = make_device_align_scorer(ctx, sdb, kAlignGuard);     // one lease per round (released when it ends)
     if ((st = scorer->begin({ job })) != P7X_OK) return st;
     if ((st = scorer->wait(res)) != P7X_OK) return st;
     out.nrounds++;
@@ -211,6 +215,7 @@ int device_traces(const p7x_oprofile *om, int device, const uint8_t *dsq, const 
       const EnvelopeResult &e = res[0][r];
       const int t = targets[r];
       out.status[(size_t) t] = e.status;
+      if (logq && (e.status & 2)) { logq->push_back(t); continue; }
       if (e.status != 0) { redo.push_back(t); continue; }     // a near-tie, a posterior digit in the guard band, a failure
       AlignTrace &a = out.tr[(size_t) t];
       align_trace_from_device(e.ta, e.ti, e.tp, e.ntrace, a);
@@ -229,27 +234,92 @@ extern "C" {
 int p7x_tracealign_compute(const p7x_oprofile *om, int device, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths,
                            size_t n, int host_threads, p7x_traces **out)
 {
+  return p7x_tracealign_compute_opts(om, device, dsq, offsets, lengths, n, host_threads, 0, out);
+}
+
+int p7x_tracealign_compute_opts(const p7x_oprofile *om, int device, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths,
+                                size_t n, int host_threads, int flags, p7x_traces **out)
+{
   if (!om || !out || (n && (!dsq || !offsets || !lengths))) { set_error("p7x_tracealign_compute: bad arguments"); return P7X_EINVAL; }
   *out = nullptr;
   for (size_t t = 0; t < n; ++t) if (lengths[t] < 0) { set_error("p7x_tracealign_compute: negative sequence length"); return P7X_EINVAL; }
   const Profile &p = om->p;
+  const bool everything = debug_opt(OPT_ALIGN_LOGSPACE) > 0;               // test seam: every non-empty sequence takes the log-space path
+  const bool logspace = (flags & P7X_ALIGN_LOGSPACE) != 0 || everything;
+  const bool on_host = debug_opt(OPT_HOST_ALIGN) > 0;                      // test seam: every trace from the host twins
   auto tr = std::make_unique<p7x_traces>();
   tr->M = p.M;
   tr->tr.assign(n, AlignTrace{});
   tr->L.assign(lengths, lengths + n);
   tr->status.assign(n, 0);
   tr->origin.assign(n, P7X_TRACE_HAS_PP);
-  std::vector<int> redo;
-  if (debug_opt(OPT_HOST_ALIGN) > 0) {                           // test seam: every trace from the host twin
-    for (size_t t = 0; t < n; ++t) if (lengths[t] > 0) redo.push_back((int) t);
+  // redo: the scaled host twin's; logq: the log kernel's; logredo: the host log twin's
+  std::vector<int> redo, logq, logredo, all;
+  for (size_t t = 0; t < n; ++t) if (lengths[t] > 0) all.push_back((int) t);
+  DeviceCtx *ctx = nullptr;
+  std::unique_ptr<p7x_seqdb, SeqdbDeleter> db;
+  if (on_host) {
+    (everything ? logredo : redo) = all;
   } else {
-    const int st = device_traces(om, device, dsq, offsets, lengths, n, *tr, redo);
+    int st = get_ctx(device, &ctx);
     if (st != P7X_OK) return st;
-    tr->nflagged = (int64_t) redo.size();
+    p7x_seqdb *raw = nullptr;
+    if ((st = p7x_seqdb_create(device, p.abc_type, dsq, offsets, lengths, n, &raw)) != P7X_OK) return st;
+    db.reset(raw);
+    if (everything) logq = all;
+    else {
+      if ((st = device_traces(om, ctx, db.get(), lengths, n, *tr, redo, logspace ? &logq : nullptr)) != P7X_OK) return st;
+      tr->nflagged = (int64_t) redo.size();
+      if (logspace) {
+        // The other trigger: Backward on its own scale factors.  The scaled kernel aligns such a sequence (and degrades
+        // from about 80 nats per domain) without saying so, so the traces it kept are checked on the host, rows only.
+        // Few need it: Backward's B cell of row i is at most Forward's total / (ploop^i pmove) <= total x 5 (L + 2), so
+        // xB > 1e16 takes a Forward score above ln 1e16 - ln(5 (L + 2)); half a nat of margin for float32.
+        std::vector<int> cand;
+        for (int t : all)
+          if (tr->status[(size_t) t] == 0 && tr->tr[(size_t) t].fwdsc >= 36.84f - std::log(5.0f * ((float) lengths[t] + 2.0f)) - 0.5f) cand.push_back(t);
+        std::vector<char> own(cand.size(), 0);
+        const int nthreads = std::max(1, std::min<int>(host_threads > 0 ? host_threads : tophits_usable_cpus(), (int) cand.size()));
+        host_parallel_for((int) cand.size(), nthreads, [&](int w) {
+          const int t = cand[(size_t) w];
+          std::vector<uint8_t> seq((size_t) lengths[t] + 2, 255);
+          std::memcpy(seq.data() + 1, dsq + offsets[t], (size_t) lengths[t]);
+          own[(size_t) w] = align_leaves_forward_scales(p, seq.data(), lengths[t]) ? 1 : 0;
+        });
+        for (size_t w = 0; w < cand.size(); ++w)
+          if (own[w]) { const int t = cand[w]; tr->tr[(size_t) t] = AlignTrace{}; tr->origin[(size_t) t] = P7X_TRACE_HAS_PP; logq.push_back(t); }
+      }
+    }
   }
   int64_t bad = -1;
-  const int st = host_traces(p, dsq, offsets, lengths, redo, tr->tr, &bad, host_threads);
-  if (st != P7X_OK) return report_host_error(st, bad, lengths[bad]);
+  if (!logspace) {
+    const int st = host_traces(p, dsq, offsets, lengths, redo, tr->tr, &bad, host_threads);
+    if (st != P7X_OK) return report_host_error(st, bad, lengths[bad]);
+  } else if (!redo.empty()) {
+    // what the scaled twin cannot finish -- Backward on its own scale factors, a range error -- is the log twin's
+    std::vector<int> each;
+    (void) host_traces(p, dsq, offsets, lengths, redo, tr->tr, &bad, host_threads, Twin::ScaledOrLeave, &each);
+    for (size_t w = 0; w < redo.size(); ++w) {
+      if (each[w] == P7X_ERANGE) logredo.push_back(redo[w]);
+      else if (each[w] != P7X_OK) return report_host_error(each[w], redo[w], lengths[redo[w]]);
+    }
+  }
+  if (!logq.empty()) {
+    std::stable_sort(logq.begin(), logq.end(), [&](int x, int y) { return lengths[x] > lengths[y]; });
+    const int st = device_align_logspace(om, ctx, db.get(), logq, tr->tr, tr->status, &tr->nrounds, &tr->work_bytes);
+    if (st != P7X_OK) return st;
+    for (int t : logq) {
+      if (tr->status[(size_t) t] != 0) { logredo.push_back(t); tr->nlogspace_flagged++; }     // a close call on the trace (or a failure: the twin names it)
+      else tr->origin[(size_t) t] = P7X_TRACE_HAS_PP | P7X_TRACE_DEVICE | P7X_TRACE_LOGSPACE;
+    }
+    tr->nlogspace += (int64_t) logq.size() - tr->nlogspace_flagged;
+  }
+  if (!logredo.empty()) {
+    const int st = host_traces(p, dsq, offsets, lengths, logredo, tr->tr, &bad, host_threads, Twin::Log);
+    if (st != P7X_OK) return report_host_error(st, bad, lengths[bad]);
+    for (int t : logredo) tr->origin[(size_t) t] = P7X_TRACE_HAS_PP | P7X_TRACE_LOGSPACE;
+    tr->nlogspace += (int64_t) logredo.size();
+  }
   *out = tr.release();
   return P7X_OK;
 }
@@ -263,6 +333,13 @@ int p7x_traces_stats(const p7x_traces *tr, int64_t out4[4])
   int64_t ndev = 0;
   for (uint8_t o : tr->origin) ndev += (o & P7X_TRACE_DEVICE) ? 1 : 0;
   out4[0] = ndev; out4[1] = tr->nflagged; out4[2] = tr->nrounds; out4[3] = tr->work_bytes;
+  return P7X_OK;
+}
+
+int p7x_traces_logspace_stats(const p7x_traces *tr, int64_t out2[2])
+{
+  if (!tr || !out2) { set_error("p7x_traces_logspace_stats: bad arguments"); return P7X_EINVAL; }
+  out2[0] = tr->nlogspace; out2[1] = tr->nlogspace_flagged;
   return P7X_OK;
 }
 
@@ -418,7 +495,11 @@ int p7x_msa_from_traces(int32_t M, size_t n, const int8_t *st, const int32_t *tk
         }
         std::vector<AlignTrace> host(n);
         int64_t bad = -1;
-        const int hst = host_traces(om->p, dsq, offsets, lengths, which, host, &bad);
+        // rows of the log-space path are averaged again from the log twin, the others from the scaled one
+        std::vector<int> scaled, logrows;
+        for (int idx : which) ((origin[idx] & P7X_TRACE_LOGSPACE) ? logrows : scaled).push_back(idx);
+        int hst = host_traces(om->p, dsq, offsets, lengths, scaled, host, &bad);
+        if (hst == P7X_OK) hst = host_traces(om->p, dsq, offsets, lengths, logrows, host, &bad, 0, Twin::Log);
         if (hst != P7X_OK) return report_host_error(hst, bad, lengths[bad]);
         for (int idx : which) {
           const AlignTrace &h = host[(size_t) idx];

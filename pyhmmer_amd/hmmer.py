@@ -1084,19 +1084,20 @@ def nhmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = 
 
 
 def hmmalign(hmm, sequences, *, cpus: int = 0, digitize: bool = False, trim: bool = False, all_consensus_cols: bool = True,
-             device: int = 0):
+             device: int = 0, logspace: bool = False):
     """Align sequences to a model and return the MSA (reference ``hmmer/_hmmalign.py``; upstream ``hmmalign``).
 
     The traces of all sequences are computed in one call on the device (``p7x_align.hip``), which aligns many
     sequences side by side; ``cpus`` is the number of worker threads of the host twin for the sequences the device
     flags (0: the library's default).  Returns a `~pyhmmer_amd.easel.TextMSA`, or a `~pyhmmer_amd.easel.DigitalMSA`
-    with ``digitize``.
+    with ``digitize``.  ``logspace`` (an extension): sequences with two strong domains of the family, on which the
+    default raises `OverflowError`, are aligned by the float64 log-space path (`~pyhmmer_amd.plan7.TraceAligner`).
     """
     from .plan7 import TraceAligner
     if cpus < 0:
         raise ValueError(f"invalid number of CPUs: {cpus!r}")
     if not isinstance(sequences, DigitalSequenceBlock):
         sequences = DigitalSequenceBlock(hmm.alphabet, sequences)
-    aligner = TraceAligner(device=device, cpus=cpus)
+    aligner = TraceAligner(device=device, cpus=cpus, logspace=logspace)
     traces = aligner.compute_traces(hmm, sequences)
     return aligner.align_traces(hmm, sequences, traces, digitize=digitize, trim=trim, all_consensus_cols=all_consensus_cols)

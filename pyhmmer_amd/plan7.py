@@ -2679,7 +2679,8 @@ def _cat_traces(traces) -> _TraceArrays:
     a.k = cat([t.k for t in traces], np.int32)
     a.i = cat([t.i for t in traces], np.int32)
     a.pp = cat([t._pp if t._pp is not None else np.zeros(len(t.st), np.float32) for t in traces], np.float32)
-    a.origin = np.array([(1 if t._pp is not None else 0) | (2 if t._device else 0) for t in traces], dtype=np.uint8)
+    a.origin = np.array([(1 if t._pp is not None else 0) | (2 if t._device else 0) | (4 if t._logspace else 0) for t in traces],
+                        dtype=np.uint8)
     return a
 
 
@@ -2713,7 +2714,7 @@ class Trace:
     nodes ``k`` and residue positions ``i`` in forward order, and -- for traces computed by `TraceAligner` -- the
     posterior probability of every step (0 where nothing is emitted)."""
 
-    __slots__ = ("st", "k", "i", "_pp", "_M", "_L", "_device")
+    __slots__ = ("st", "k", "i", "_pp", "_M", "_L", "_device", "_logspace")
 
     def __init__(self, posteriors: bool = False):
         self.st = np.zeros(0, dtype=np.int8)
@@ -2722,6 +2723,7 @@ class Trace:
         self._pp = np.zeros(0, dtype=np.float32) if posteriors else None
         self._M = self._L = 0
         self._device = False
+        self._logspace = False    # computed by the float64 log-space path (TraceAligner(logspace=True))
 
     @classmethod
     def from_sequence(cls, sequence) -> "Trace":
@@ -2821,6 +2823,10 @@ class Traces(list):
     nflagged: int = 0
     rounds: int = 0
     workspace_bytes: int = 0
+    # TraceAligner(logspace=True): sequences the float64 log-space path aligned, and of those the device traces its host
+    # twin repeated
+    nlogspace: int = 0
+    nlogspace_flagged: int = 0
 
     def __init__(self, iterable: Iterable = ()):
         super().__init__(iterable)
@@ -2842,17 +2848,26 @@ class Traces(list):
 class TraceAligner:
     """Aligns sequences to a model (reference ``plan7.pyx:9745-9925``; upstream ``p7_tracealign_computeTraces`` and
     ``p7_tracealign_Seqs``).  The traces are computed on the device (``p7x_align.hip``); without a device the call raises
-    `~pyhmmer_amd.errors.DeviceUnavailable` (the test seam ``host_align`` selects the host twin)."""
+    `~pyhmmer_amd.errors.DeviceUnavailable` (the test seam ``host_align`` selects the host twin).
 
-    def __init__(self, device: int = 0, cpus: int = 0):
+    ``logspace`` (an extension): a sequence that carries two strong domains of the family -- its Backward pass leaves
+    Forward's scale factors, or its posterior decoding overflows, where the default raises `OverflowError` -- is
+    aligned by a float64 log-space path instead (``p7x_alignlog.hip``; upstream falls back to its generic DP there).
+    Every other sequence is aligned as without it."""
+
+    def __init__(self, device: int = 0, cpus: int = 0, logspace: bool = False):
         self.device = device
         self.cpus = cpus          # workers of the host twin (the sequences it repeats); 0: the library's default
+        self.logspace = bool(logspace)
 
     def __repr__(self) -> str:
-        return f"{type(self).__name__}()"
+        return f"{type(self).__name__}(logspace=True)" if self.logspace else f"{type(self).__name__}()"
 
     def __reduce__(self):
-        return type(self), (self.device, self.cpus)
+        return type(self), (self.device, self.cpus, self.logspace)
+
+    def copy(self) -> "TraceAligner":
+        return type(self)(self.device, self.cpus, self.logspace)
 
     @staticmethod
     def _check(hmm: HMM, sequences: DigitalSequenceBlock) -> None:
@@ -2869,8 +2884,8 @@ class TraceAligner:
         pk = sequences.packed()
         lib = _lib.lib()
         h = C.c_void_p()
-        st = lib.p7x_tracealign_compute(om._handle, self.device, pk.dsq.ctypes.data, pk.offsets.ctypes.data,
-                                        pk.lengths.ctypes.data, pk.n, int(self.cpus), C.byref(h))
+        st = lib.p7x_tracealign_compute_opts(om._handle, self.device, pk.dsq.ctypes.data, pk.offsets.ctypes.data,
+                                             pk.lengths.ctypes.data, pk.n, int(self.cpus), 1 if self.logspace else 0, C.byref(h))
         if st != 0:
             detail = _lib.last_error()
             m = re.search(r"sequence (\d+)", detail)
@@ -2887,11 +2902,13 @@ class TraceAligner:
                 t.st, t.k, t.i = np.empty(n, np.int8), np.empty(n, np.int32), np.empty(n, np.int32)
                 t._pp = np.empty(n, np.float32)
                 lib.p7x_traces_copy(h, idx, t.st.ctypes.data, t.k.ctypes.data, t.i.ctypes.data, t._pp.ctypes.data)
-                t._M, t._L, t._device = M.value, L.value, bool(origin.value & 2)
+                t._M, t._L, t._device, t._logspace = M.value, L.value, bool(origin.value & 2), bool(origin.value & 4)
                 traces.append(t)
             stats = np.zeros(4, dtype=np.int64)
             lib.p7x_traces_stats(h, stats.ctypes.data)
             traces.ndevice, traces.nflagged, traces.rounds, traces.workspace_bytes = (int(x) for x in stats)
+            lib.p7x_traces_logspace_stats(h, stats.ctypes.data)
+            traces.nlogspace, traces.nlogspace_flagged = int(stats[0]), int(stats[1])
         finally:
             lib.p7x_traces_destroy(h)
         return traces
