@@ -99,12 +99,14 @@ class RefResult:
         return btot, etot, mocc
 
 
-def forward_backward(model, seq, multihit, cells=False):
+def forward_backward(model, seq, multihit, cells=False, length=None):
+    """length: the target length the N / J / C length model is formed from, where it is not len(seq) -- a domain envelope is
+    scored over its own residues under the length model of the whole target."""
     m = model
     M = m.M
     seq = np.asarray(seq, dtype=np.int64)
     L = len(seq)
-    loop, move, emove, eloop = length_model(L, multihit)
+    loop, move, emove, eloop = length_model(L if length is None else length, multihit)
     k = slice(1, M + 1)
     km1 = slice(0, M)
     kp1 = slice(2, M + 2)
@@ -194,12 +196,26 @@ def forward_backward(model, seq, multihit, cells=False):
 
 
 # ---- an independent statement of Forward: the sum over every path, enumerated (tiny models and targets only)
-def enumerate_paths(model, seq, multihit):
-    """log of the summed probability of every complete path S N.. B .. E (J .. B .. E)* C.. T that emits exactly <seq>."""
+def enumerate_paths(model, seq, multihit, length=None, emitters=False):
+    """log of the summed probability of every complete path S N.. B .. E (J .. B .. E)* C.. T that emits exactly <seq>.
+    length: as in forward_backward.  emitters: return (that log, usage) instead, usage[i - 1] = {state: probability} of
+    residue i's emitter over the paths, not normalised -- states ("M", k), ("I", k), ("N", 0), ("J", 0), ("C", 0)."""
     m, M, L = model, model.M, len(seq)
-    loop, move, emove, eloop = (float(np.exp(v)) for v in length_model(L, multihit))
+    loop, move, emove, eloop = (float(np.exp(v)) for v in length_model(L if length is None else length, multihit))
     ex = lambda a: float(np.exp(a))
     total = []
+    who = []                                   # the emitter of each residue emitted so far on the path being walked
+    usage = [{} for _ in range(L)]
+
+    def emits(fn):
+        """<fn> visits a state that has just emitted residue i: it is on the path for as long as the visit lasts."""
+        def inner(state, kk, i, p):
+            if p == 0.0:
+                return
+            who.append((state, kk))
+            fn(state, kk, i, p)
+            who.pop()
+        return inner
 
     def em(kk, i):
         return ex(m.e[seq[i], kk])
@@ -210,48 +226,55 @@ def enumerate_paths(model, seq, multihit):
             return
         if state == "N":
             if i < L:
-                visit("N", 0, i + 1, p * loop)
+                emit("N", 0, i + 1, p * loop)
             visit("B", 0, i, p * move)
         elif state == "B":
             if i < L:
                 for k2 in range(1, M + 1):
-                    visit("M", k2, i + 1, p * ex(m.bm[k2]) * em(k2, i))
+                    emit("M", k2, i + 1, p * ex(m.bm[k2]) * em(k2, i))
         elif state == "M":
             visit("E", 0, i, p)
             if i < L:
-                visit("I", kk, i + 1, p * ex(m.mi[kk]))
+                emit("I", kk, i + 1, p * ex(m.mi[kk]))
                 if kk < M:
-                    visit("M", kk + 1, i + 1, p * ex(m.mm[kk + 1]) * em(kk + 1, i))
+                    emit("M", kk + 1, i + 1, p * ex(m.mm[kk + 1]) * em(kk + 1, i))
             if kk < M:
                 visit("D", kk + 1, i, p * ex(m.md[kk]))
         elif state == "I":
             if i < L:
-                visit("I", kk, i + 1, p * ex(m.ii[kk]))
+                emit("I", kk, i + 1, p * ex(m.ii[kk]))
                 if kk < M:
-                    visit("M", kk + 1, i + 1, p * ex(m.im[kk + 1]) * em(kk + 1, i))
+                    emit("M", kk + 1, i + 1, p * ex(m.im[kk + 1]) * em(kk + 1, i))
         elif state == "D":
             visit("E", 0, i, p)
             if kk < M:
                 visit("D", kk + 1, i, p * ex(m.dd[kk]))
                 if i < L:
-                    visit("M", kk + 1, i + 1, p * ex(m.dm[kk + 1]) * em(kk + 1, i))
+                    emit("M", kk + 1, i + 1, p * ex(m.dm[kk + 1]) * em(kk + 1, i))
         elif state == "E":
             visit("C", 0, i, p * emove)
             visit("J", 0, i, p * eloop)
         elif state == "J":
             if i < L:
-                visit("J", 0, i + 1, p * loop)
+                emit("J", 0, i + 1, p * loop)
                 visit("B", 0, i, p * move)
         elif state == "C":
             if i < L:
-                visit("C", 0, i + 1, p * loop)
+                emit("C", 0, i + 1, p * loop)
             else:
                 total.append(p * move)
+                if emitters:
+                    for pos, state in enumerate(who):
+                        usage[pos].setdefault(state, []).append(p * move)
 
+    emit = emits(visit)
     visit("N", 0, 0, 1.0)
     import math
     s = math.fsum(total)
-    return math.log(s) if s > 0 else NEG
+    logsum = math.log(s) if s > 0 else NEG
+    if emitters:
+        return logsum, [{state: math.fsum(ps) for state, ps in u.items()} for u in usage]
+    return logsum
 
 
 # ---- the float32 engines' outputs in the reference's terms
