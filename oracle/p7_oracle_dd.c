@@ -975,10 +975,14 @@ static int dd_lt_adjust(const P7O_PROFILE *p, DDModel *m, const uint8_t *first, 
   const int M = m->M, K = m->K, Kp = m->Kp;
   float bg[P7O_MAXK];
   p7o_lt_envelope_background(p, first, Ld, window_len, degen, bg);
+  const int Q4 = p->Q4;
   for (int k = 1; k <= M; k++) {
     float sc[P7O_MAXKP];
+    const int qq = (k - 1) % Q4, z = (k - 1) / Q4;
     for (int x = 0; x < K; x++) {
-      const float prob = expf(p->msc[(size_t) x * (M + 1) + k]) * p->bgf[x];      /* the core model's match emission */
+      /* p7_oprofile_GetFwdEmissionArray: the match emission back from the Forward odds of the optimized profile (which
+       * come from esl_sse_expf and differ from expf(msc) by an ulp in a few cells of a hundred) */
+      const float prob = p->rfv[((size_t) x * Q4 + qq) * 4 + z] * p->bgf[x];
       sc[x] = logf(prob / bg[x]);
     }
     sc[K] = sc[Kp - 2] = sc[Kp - 1] = -INFINITY;

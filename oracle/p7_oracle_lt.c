@@ -300,7 +300,7 @@ int p7o_lt_envelope_scores(const P7O_PROFILE *p, const uint8_t *env, int n, int6
   for (int k = 1; k <= M; k++) {
     int qq = (k - 1) % Q, z = (k - 1) / Q;
     for (int x = 0; x < K; x++) {
-      float prob = expf(p->msc[(size_t) x * (M + 1) + k]) * p->bgf[x];       /* the core model's match emission */
+      float prob = p->rfv[((size_t) x * Q + qq) * 4 + z] * p->bgf[x];       /* the match emission, p7_oprofile_GetFwdEmissionArray */
       rfv[((size_t) x * Q + qq) * 4 + z] = expf(logf(prob / bg[x]));
     }
   }

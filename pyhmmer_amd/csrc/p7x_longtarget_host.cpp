@@ -229,7 +229,8 @@ struct LtBlock {                 // one block of one strand, as p7_Pipeline_Long
   bool complement;
 };
 
-struct LtCounters { uint64_t n_past_msv = 0, n_past_bias = 0, n_past_vit = 0, n_past_fwd = 0, pos_past_msv = 0, pos_past_bias = 0, pos_past_vit = 0, pos_past_fwd = 0; };
+struct LtCounters { uint64_t n_past_msv = 0, n_past_bias = 0, n_past_vit = 0, n_past_fwd = 0, pos_past_msv = 0, pos_past_bias = 0, pos_past_vit = 0, pos_past_fwd = 0;
+                    int64_t oa_redone = 0, oa_why[8] = {}; };      // device envelopes the near-tie guard sent to the host twin, by kind of choice
 
 // blk.dsq is not used here: <subseq>[1..window_len] are the window's residues; blk.start / blk.complement and
 // window_start (the window's first residue in the block) map coordinates back to the target.  fwd_given: the window's
@@ -403,6 +404,8 @@ static void lt_finish_tophits(const p7x_pipeline_cfg &cfg_in, const Profile &p, 
   th->ctr.nmodels = 1; th->ctr.nnodes = (uint64_t) p.M; th->ctr.nseqs = nseqs; th->ctr.nres = nres;
   th->ctr.n_past_msv = ctr.n_past_msv; th->ctr.n_past_bias = ctr.n_past_bias; th->ctr.n_past_vit = ctr.n_past_vit; th->ctr.n_past_fwd = ctr.n_past_fwd;
   th->ctr.pos_past_msv = ctr.pos_past_msv; th->ctr.pos_past_bias = ctr.pos_past_bias; th->ctr.pos_past_vit = ctr.pos_past_vit; th->ctr.pos_past_fwd = ctr.pos_past_fwd;
+  th->oa_redone = ctr.oa_redone;
+  for (int b = 0; b < 8; ++b) th->oa_why[b] = ctr.oa_why[b];
   th->hits = std::move(hits);
   th->lt_evalue_window = max_length;
   th->lt_unfinished = true;
@@ -727,6 +730,10 @@ int longtarget_run_host(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, con
         todo.swap(next);
       }
       tick("envelopes on the device");
+      for (const EnvState &e : es) if (e.host) {
+        ctr.oa_redone++;
+        for (int b = 0; b < 8; ++b) if (e.res.status & (1 << (8 + b))) ctr.oa_why[b]++;
+      }
       // phase C: the windows' domains in order, then their hits
       std::vector<std::vector<size_t>> of_win(vj.size());
       for (size_t e = 0; e < es.size(); ++e) of_win[es[e].z].push_back(e);

@@ -989,6 +989,8 @@ int p7x_tophits_merge_longtargets(p7x_tophits **parts, size_t nparts, p7x_tophit
     dst->ctr.n_past_vit += src->ctr.n_past_vit; dst->ctr.n_past_fwd += src->ctr.n_past_fwd;
     dst->ctr.pos_past_msv += src->ctr.pos_past_msv; dst->ctr.pos_past_bias += src->ctr.pos_past_bias;
     dst->ctr.pos_past_vit += src->ctr.pos_past_vit; dst->ctr.pos_past_fwd += src->ctr.pos_past_fwd;
+    dst->oa_redone += src->oa_redone;
+    for (int b = 0; b < 8; ++b) dst->oa_why[b] += src->oa_why[b];
     for (int i = 0; i < p7x_tophits::kMs; ++i) dst->ms[i] = std::max(dst->ms[i], src->ms[i]);      // the parts ran side by side
   }
   dst->cfg.lt_part = 0; dst->cfg.lt_nparts = 1;

@@ -99,9 +99,9 @@ class RefResult:
         return btot, etot, mocc
 
 
-def forward_backward(model, seq, multihit, cells=False, length=None):
+def forward_backward(model, seq, multihit, cells=False, length=None, backward=True):
     """length: the target length the N / J / C length model is formed from, where it is not len(seq) -- a domain envelope is
-    scored over its own residues under the length model of the whole target."""
+    scored over its own residues under the length model of the whole target.  backward=False: Forward only (fwd and fx)."""
     m = model
     M = m.M
     seq = np.asarray(seq, dtype=np.int64)
@@ -144,6 +144,9 @@ def forward_backward(model, seq, multihit, cells=False, length=None):
             r.fM[i], r.fI[i] = Mc, Ic
         Mp, Ip, Dp = Mc, Ic, Dc
     r.fwd = float(fx[L, C] + move)
+    if not backward:
+        r.fx = fx
+        return r
 
     # ---- Backward
     def close_row(xE, a_m, a_d):
