@@ -157,7 +157,7 @@ struct MsvWaveArgs {
 };
 int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st);
 
-// ---- packed Viterbi filter (p7x_vitpk.hip): T lanes per target, 2P nodes per lane, for M <= 640
+// ---- packed Viterbi filter (p7x_vitpk.hip): T lanes per target, 2P nodes per lane, for M <= 2048
 struct VitPkArgs {
   const void *trans, *emis;     // vitpk_build_tables()
   const uint8_t *dsq; const int64_t *slot_off; const int32_t *slot_len;

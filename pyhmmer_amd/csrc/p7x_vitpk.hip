@@ -1,15 +1,17 @@
-// p7x_vitpk.hip -- Viterbi filter, packed: T lanes per target (T = 8 or 16), 64/T targets per wavefront.
+// p7x_vitpk.hip -- Viterbi filter, packed: T lanes per target (T = 8, 16, 32 or 64), 64/T targets per wavefront.
 //
 // The wave-per-target kernel in p7x_vitfwd.hip spends most of a row on work that does not shrink with the model:
 // wave-wide reductions, the scalar special-state chain, and 16-bit values in 32-bit lanes.  For the common
-// Pfam-sized models (M <= 640) this kernel shares those costs between several targets:
+// Pfam-sized models (M <= 640) this kernel shares those costs between several targets (T = 8, 16); the models of 641 to
+// 2,048 nodes get the same packed rows with two targets (T = 32) or one (T = 64) per wavefront:
 //   * the nodes are striped over the 2T half-lanes of a group (Farrar): register q of lane s holds node q+1+s*P in
 //     its low half and node q+1+(s+T)*P in its high half, so the k-1 neighbour of a register is the register
 //     before it and only register 0 takes values from another lane (v_pk_add_i16 clamp / v_pk_max_i16 reproduce
 //     _mm_adds_epi16 / _mm_max_epi16 of impl_sse/vitfilter.c exactly);
 //   * transitions (8 x int16 per node: BM MM IM DM MD MI II DD) and emissions come from LDS as ds_read_b128,
 //     the DP rows (M, I, D) stay in 3P registers, two sets of them (a row reads one and writes the other);
-//   * xE / Dmax are 3- or 4-step DPP butterflies inside the group, the special states are per-lane integers that
+//   * xE / Dmax are 3- or 4-step DPP butterflies inside the group (T = 32, 64: one or two half exchanges between the
+//     16-lane rows on top, v_permlane16_swap / v_permlane32_swap), the special states are per-lane integers that
 //     are uniform within a group; targets that have ended are masked, the row loop runs to the longest target of
 //     the wavefront;
 //   * lazy F follows upstream: D gets only M->D unless Dmax + ddbound > xB for that target; then the D->D closure
@@ -48,6 +50,8 @@ constexpr uint32_t kNeg2 = 0x80008000u;      // (-32768, -32768)
 //           survivors: 3.43 ms against 3.61.  Keeping every chunk twice (slots 0-7 and 8-15, the groups whose second
 //           bit is set reading the second copy) removes the conflicts altogether and was slower, 4.07 ms: 40 KB of
 //           emissions to stage per workgroup, and the kernel is bound by its packed arithmetic (80 % VALU), not by LDS.
+//   T = 32, 64: a chunk is two or four whole bank rows and every service group lies inside one target's group: 16 lanes,
+//           16 different slots of one residue row, as for T = 16.
 constexpr int vitpk_rowq(int T, int P)
 {
   const int n = ((P + 3) / 4) * T;
@@ -63,7 +67,15 @@ __device__ __forceinline__ int group_max(uint32_t v)
   v = pk_max(v, P7X_DPP_U(v, 0xB1));      // quad_perm [1,0,3,2]
   v = pk_max(v, P7X_DPP_U(v, 0x4E));      // quad_perm [2,3,0,1]
   v = pk_max(v, P7X_DPP_U(v, 0x141));     // row_half_mirror: 8 lanes
-  if constexpr (T == 16) v = pk_max(v, P7X_DPP_U(v, 0x140));   // row_mirror: 16 lanes
+  if constexpr (T >= 16) v = pk_max(v, P7X_DPP_U(v, 0x140));   // row_mirror: 16 lanes
+  if constexpr (T >= 32) {      // both operands are v: every lane gets its own value and that of its partner row, in either order
+    const auto x = __builtin_amdgcn_permlane16_swap(v, v, false, false);       // rows 0 <-> 1, 2 <-> 3: 32 lanes
+    v = pk_max(x[0], x[1]);
+  }
+  if constexpr (T == 64) {
+    const auto x = __builtin_amdgcn_permlane32_swap(v, v, false, false);       // lanes 0-31 <-> 32-63
+    v = pk_max(x[0], x[1]);
+  }
   return max(lo_of(v), hi_of(v));
 }
 
@@ -73,11 +85,22 @@ struct RowState { int xN, xB, xJ, xC; bool overflow; };
 
 // Value of the previous stripe for every stripe of a register: lane z-1's register for lanes z >= 1; the first lane of a
 // group takes (-32768, lo half of the group's last lane): stripe 0 has no predecessor, stripe T follows stripe T-1.
+// T = 32, 64: the last lane of a group is in another DPP row than the first.  T = 64: the rotation of the wavefront brings
+// it along.  T = 32 (<hi>: the lane belongs to the second group): two lane reads, both outside the select -- a lane read
+// in one arm of a conditional becomes a branch in the row.
 template <int T>
-__device__ __forceinline__ uint32_t stripe_shift(uint32_t r, bool first)
+__device__ __forceinline__ uint32_t stripe_shift(uint32_t r, bool first, bool hi)
 {
+  if constexpr (T == 64) {
+    const uint32_t w = P7X_DPP_U(r, 0x13C);                           // wave_ror:1: lane 0 <- lane 63
+    return first ? ((w << 16) | 0x8000u) : w;
+  }
   const uint32_t prev = P7X_DPP_U(r, 0x138);                          // wave_shr:1
-  const uint32_t last = P7X_DPP_U(r, T == 8 ? 0x141 : 0x140);         // row_half_mirror / row_mirror: lane 0 <- lane T-1
+  uint32_t last;
+  if constexpr (T == 32) {
+    const uint32_t l31 = (uint32_t) __builtin_amdgcn_readlane((int) r, 31), l63 = (uint32_t) __builtin_amdgcn_readlane((int) r, 63);
+    last = hi ? l63 : l31;
+  } else last = P7X_DPP_U(r, T == 8 ? 0x141 : 0x140);                 // row_half_mirror / row_mirror: lane 0 <- lane T-1
   return first ? ((last << 16) | 0x8000u) : prev;
 }
 
@@ -85,14 +108,14 @@ __device__ __forceinline__ uint32_t stripe_shift(uint32_t r, bool first)
 // Register q of a lane holds the nodes q + 1 + s*P of its two stripes s = lane (low half) and lane + T (high half),
 // so the k-1 neighbour of a register is the register before it and only register 0 needs values from another lane.
 template <int T, int P>
-__device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, const uint4 *trbl, const uint4 *er, bool first,
+__device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, const uint4 *trbl, const uint4 *er, bool first, bool hi,
                                         bool active, int xwm, const uint32_t (&mi)[P], const uint32_t (&ii)[P],
                                         const uint32_t (&di)[P], uint32_t (&mo_)[P], uint32_t (&io_)[P], uint32_t (&do_)[P],
                                         const uint32_t (&tdd)[P], RowState &rs)
 {
   constexpr int PS = (P + 3) & ~3;
   const uint32_t xBv = splat16(rs.xB);
-  uint32_t mp = stripe_shift<T>(mi[P - 1], first), ip = stripe_shift<T>(ii[P - 1], first), dp = stripe_shift<T>(di[P - 1], first);
+  uint32_t mp = stripe_shift<T>(mi[P - 1], first, hi), ip = stripe_shift<T>(ii[P - 1], first, hi), dp = stripe_shift<T>(di[P - 1], first, hi);
   uint32_t xEv = kNeg2, dmaxv = kNeg2, dcv = kNeg2;
 #pragma unroll
   for (int j4 = 0; j4 < PS; j4 += 4) {
@@ -119,7 +142,7 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
     // keep the LDS loads of later registers behind this point: hoisting all 2P transition loads costs 8 VGPRs each
     asm volatile("" ::: "memory");
   }
-  do_[0] = stripe_shift<T>(dcv, first);                          // the first node of a stripe follows the last of the one before
+  do_[0] = stripe_shift<T>(dcv, first, hi);                      // the first node of a stripe follows the last of the one before
   const int xE = group_max<T>(xEv);
   const int Dmax = group_max<T>(dmaxv);
   if (active) {
@@ -143,7 +166,7 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
     do {
 #pragma unroll
       for (int q = 1; q < P; ++q) do_[q] = pk_max(do_[q], pk_adds(do_[q - 1], tdd[q - 1]));
-      uint32_t c = stripe_shift<T>(pk_adds(do_[P - 1], tdd[P - 1]), first);
+      uint32_t c = stripe_shift<T>(pk_adds(do_[P - 1], tdd[P - 1]), first, hi);
       if (!trig) c = kNeg2;
       const uint32_t d0 = pk_max(do_[0], c);
       const bool changed = d0 != do_[0];
@@ -153,14 +176,28 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
   }
 }
 
+// Wavefronts per workgroup.  The tables of a model beyond 640 nodes take 57 to 152 KiB of LDS, so a compute unit holds one
+// or two workgroups whatever their size: with four wavefronts each that is one wavefront per SIMD for P >= 17 (T = 32) and
+// for every T = 64, and the row's LDS reads and dependent packed operations have nothing to overlap with.  The wide
+// instantiations therefore share one copy of the tables between as many wavefronts as their registers allow on a SIMD:
+// four (up to 128 VGPRs: P <= 12; T = 32 gets them as two workgroups of eight), three (up to 170: P = 13 ... 16) or two
+// (T = 32, P >= 17: <32, 17> spills three registers under the limit of 170).
+constexpr int vitpk_waves(int T, int P)
+{
+  if (T == 64) return P <= 12 ? 16 : 12;
+  if (T == 32) return (P >= 13 && P <= 16) ? 12 : 8;
+  return 4;
+}
+
 template <int T, int P>
-__global__ void __launch_bounds__(256) vitpk_kernel(const ArgRef ref)
+__global__ void __launch_bounds__(64 * vitpk_waves(T, P)) vitpk_kernel(const ArgRef ref)
 {
   constexpr int G = 64 / T;                // targets per wavefront
+  constexpr int NW = vitpk_waves(T, P), NT = 64 * NW;
   const VitPkArgs a = load_args<VitPkArgs>(ref);
   const int nlist = a.nlist_ptr ? *a.nlist_ptr : a.nlist;
   const int nskip = a.nskip_ptr ? *a.nskip_ptr : 0;         // the longest targets (a prefix of the list) go elsewhere
-  if (nskip + (int) (blockIdx.x * 4 * G) >= nlist) return;  // no target for this block: skip the table load
+  if (nskip + (int) (blockIdx.x * NW * G) >= nlist) return;  // no target for this block: skip the table load
   constexpr int PS = (P + 3) & ~3;         // table stride per lane, in pairs
   constexpr int ROWQ = vitpk_rowq(T, P);   // uint4 per emission row (see vitpk_rowq)
   // LDS layouts are lane-minor, so that the 16-byte reads of the T lanes of a group (and of the groups of a
@@ -173,16 +210,16 @@ __global__ void __launch_bounds__(256) vitpk_kernel(const ArgRef ref)
   uint4 *em = trb + P * T;
   {
     const uint4 *gt = reinterpret_cast<const uint4 *>(a.trans);
-    for (int i = threadIdx.x; i < 2 * P * T; i += 256) tra[i] = gt[i];
+    for (int i = threadIdx.x; i < 2 * P * T; i += NT) tra[i] = gt[i];
     const uint4 *ge = reinterpret_cast<const uint4 *>(a.emis);
-    for (int i = threadIdx.x; i < a.nrows * ROWQ; i += 256) em[i] = ge[i];
+    for (int i = threadIdx.x; i < a.nrows * ROWQ; i += NT) em[i] = ge[i];
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const int s = lane % T, g = lane / T;
-  const bool first = (s == 0);
-  const int wave0 = rfl((int) (blockIdx.x * 4 + (threadIdx.x >> 6)));
-  const int nwaves = (int) gridDim.x * 4;
+  const bool first = (s == 0), hi = (g != 0);
+  const int wave0 = rfl((int) (blockIdx.x * NW + (threadIdx.x >> 6)));
+  const int nwaves = (int) gridDim.x * NW;
   const uint4 *tral = tra + s, *trbl = trb + s, *eml = em + s;
   uint32_t tdd[P];                 // D->D transitions of this lane's nodes: row-invariant, kept in registers for the closure
 #pragma unroll
@@ -222,11 +259,11 @@ __global__ void __launch_bounds__(256) vitpk_kernel(const ArgRef ref)
       };
       int r = 0;
       for (; r + 1 < nrow; r += 2) {
-        vit_row<T, P>(a, tral, trbl, eml + residue(r) * ROWQ, first, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, tdd, rs);
-        vit_row<T, P>(a, tral, trbl, eml + residue(r + 1) * ROWQ, first, i0 + r + 1 < L, xwm, mB, iB, dB, mA, iA, dA, tdd, rs);
+        vit_row<T, P>(a, tral, trbl, eml + residue(r) * ROWQ, first, hi, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, tdd, rs);
+        vit_row<T, P>(a, tral, trbl, eml + residue(r + 1) * ROWQ, first, hi, i0 + r + 1 < L, xwm, mB, iB, dB, mA, iA, dA, tdd, rs);
       }
       if (r < nrow) {     // odd row count (only the last block of a group): one more row, then back into set A
-        vit_row<T, P>(a, tral, trbl, eml + residue(r) * ROWQ, first, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, tdd, rs);
+        vit_row<T, P>(a, tral, trbl, eml + residue(r) * ROWQ, first, hi, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, tdd, rs);
 #pragma unroll
         for (int j = 0; j < P; ++j) { mA[j] = mB[j]; iA[j] = iB[j]; dA[j] = dB[j]; }
       }
@@ -243,6 +280,11 @@ bool vitpk_pick(int M, int *T, int *P)
   static const int p16[] = { 11, 12, 13, 14, 15, 16, 17, 18, 19, 20 };
   for (int p : p8) if (M <= 8 * 2 * p) { *T = 8; *P = p; return true; }
   for (int p : p16) if (M <= 16 * 2 * p) { *T = 16; *P = p; return true; }
+  if (debug_opt(OPT_VIT_WIDE) == 0) return false;       // A/B and test seam: models beyond 640 nodes stay with vit_kernel
+  static const int p32[] = { 11, 12, 13, 14, 15, 16, 17, 18, 19, 20 };
+  static const int p64[] = { 11, 12, 13, 14, 15, 16 };
+  for (int p : p32) if (M <= 32 * 2 * p) { *T = 32; *P = p; return true; }
+  for (int p : p64) if (M <= 64 * 2 * p) { *T = 64; *P = p; return true; }
   return false;
 }
 
@@ -276,6 +318,7 @@ static int launch_pk(const ArgRun<VitPkArgs> &a, int num_cu, hipStream_t st)
 {
   const size_t lds = ((size_t) 2 * P * T + (size_t) a.at(0).nrows * vitpk_rowq(T, P)) * 16;
   auto kern = vitpk_kernel<T, P>;
+  constexpr int NW = vitpk_waves(T, P), NT = 64 * NW;
   static std::map<int, int> per_cu_by_device;       // the LDS opt-in is a per-device attribute of the kernel: looked up once per device
   static std::mutex mu;
   int per_cu = 0;
@@ -285,15 +328,15 @@ static int launch_pk(const ArgRun<VitPkArgs> &a, int num_cu, hipStream_t st)
     int &cached = per_cu_by_device[dev];
     if (cached == 0) {
       if (lds > 64 * 1024) P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kern, 256, lds));
+      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kern, NT, lds));
       if (cached < 1) cached = 1;
     }
     per_cu = cached;
   }
   long want = 0;
-  for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nlist + 4 * (64 / T) - 1) / (4 * (64 / T)));   // nlist bounds the list
+  for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nlist + NW * (64 / T) - 1) / (NW * (64 / T)));   // nlist bounds the list
   if (want <= 0) return P7X_OK;
-  hipLaunchKernelGGL(kern, dim3(lane_grid(want, (long) num_cu * per_cu, a.n), (unsigned) a.n), dim3(256), lds, st, a.ref());
+  hipLaunchKernelGGL(kern, dim3(lane_grid(want, (long) num_cu * per_cu, a.n), (unsigned) a.n), dim3(NT), lds, st, a.ref());
   P7X_HIP(hipGetLastError());
   return P7X_OK;
 }
@@ -306,6 +349,9 @@ int vitpk_launch(int T, int P, const ArgRun<VitPkArgs> &a, int num_cu, hipStream
   P7X_PK(8, 17) P7X_PK(8, 18) P7X_PK(8, 19) P7X_PK(8, 20)
   P7X_PK(16, 11) P7X_PK(16, 12) P7X_PK(16, 13) P7X_PK(16, 14) P7X_PK(16, 15) P7X_PK(16, 16) P7X_PK(16, 17) P7X_PK(16, 18)
   P7X_PK(16, 19) P7X_PK(16, 20)
+  P7X_PK(32, 11) P7X_PK(32, 12) P7X_PK(32, 13) P7X_PK(32, 14) P7X_PK(32, 15) P7X_PK(32, 16) P7X_PK(32, 17) P7X_PK(32, 18)
+  P7X_PK(32, 19) P7X_PK(32, 20)
+  P7X_PK(64, 11) P7X_PK(64, 12) P7X_PK(64, 13) P7X_PK(64, 14) P7X_PK(64, 15) P7X_PK(64, 16)
 #undef P7X_PK
   set_error("no packed Viterbi kernel for this model length");
   return P7X_EINVAL;
