@@ -640,6 +640,52 @@ double p7x_oprofile_match_relent(const p7x_oprofile *om);
  * bits).  M <= p7x_max_model_length.  P7X_ENODEVICE without a device; P7X_EINVAL for a profile without p7x_oprofile_match_relent. */
 int p7x_calibrate_batch(p7x_oprofile *const *oms, size_t nq, int device, uint32_t seed, float *out_evparam, int32_t *out_scores);
 
+/* ------------------------------------------------------------------ sampling: easel.Randomness, p7x_emit.cpp, p7x_emit.hip
+ * Easel's generators as easel.Randomness holds them (easel.pyx:7006-7161): state[P7X_RNG_STATE_WORDS] = mt[624], mti, x of
+ * ESL_RANDOMNESS.  seed: esl_randomness_Init for one generator (the caller replaces a seed of 0); draw: n calls of
+ * esl_random, deviates x / 2^32 in [0, 1).  The unit the calibration stream draws from (p7x_rng.hpp). */
+#define P7X_RNG_STATE_WORDS 626
+int p7x_rng_seed(int generator, uint32_t seed, uint32_t *state);
+int p7x_rng_draw(int generator, uint32_t *state, size_t n, double *out);
+
+/* The cumulative tables (double) every emitter draws from, built once per core model: P7X_EINVAL for a model that
+ * cannot be sampled (an insert state that is entered and never left; no residue ever emitted).  info: the expected
+ * number of residues of one pass through the core model, and the slot capacity the block emitter starts with (twice
+ * that, a multiple of four; debug option "emit_cap" overrides it). */
+typedef struct p7x_emit_model p7x_emit_model;
+int  p7x_emit_model_create(const p7x_hmm_view *hmm, p7x_emit_model **out);
+void p7x_emit_model_destroy(p7x_emit_model *em);
+int  p7x_emit_model_info(const p7x_emit_model *em, double *expected_length, int32_t *cap);
+/* HMM.emit_sequence / emit_alignment (plan7.pyx:3141-3340; upstream p7_CoreEmit): one path through the core model from
+ * node 0 on the generator in <state>, which advances; a path that emits nothing is drawn again.  dsq / st / node[cap]
+ * (st, node may be NULL): residues, and the state (p7T_M 1, p7T_I 3) and node that emitted each.  *len residues were
+ * emitted; when *len > cap the caller restores the state it had and calls again with room for them.
+ * Profile.emit_sequence (plan7.pyx:8109-8194; upstream p7_ProfileEmit): a path through the local multihit profile
+ * with length model L; counts[2] (may be NULL): residues emitted by core states, passes through the core.
+ * What is claimed is the distribution, not upstream's draw-for-draw stream.  P7X_ERANGE: beyond 100,000 residues. */
+int p7x_emit_core(const p7x_emit_model *em, int generator, uint32_t *state, uint8_t *dsq, int8_t *st, int32_t *node, size_t cap, int64_t *len);
+int p7x_emit_profile(const p7x_emit_model *em, int32_t L, const float *bg_f, int generator, uint32_t *state, uint8_t *dsq, size_t cap,
+                     int64_t *len, int32_t *counts);
+/* HMM.emit_block (an extension): n core-model sequences emitted on the device, one lane per sequence, every (sequence,
+ * attempt, step) with its own Philox-4x32-10 block keyed by <seed> -- sequence i does not depend on n, the grid or the
+ * device.  The block is packed as p7x_seqdb_create takes it (255 x1..xL 255 ...).  p7x_emit_block_host is the host twin:
+ * same tables, same generator, same loop, the same bytes; debug option "host_emit" = 1 makes p7x_emit_block call it.
+ * P7X_ENODEVICE without a device, P7X_EINVAL for n < 0 or a model beyond p7x_max_model_length, P7X_EMEM when the slots of
+ * n sequences do not fit the device's free memory, P7X_ERANGE for a sequence beyond 100,000 residues.
+ * info: 0 n, 1 residues, 2 slot capacity of the first pass, 3 sequences drawn again into an exact slot, 4 emitted on the
+ * device, 5 has traces, 6 microseconds of the emit kernel's launches (device events). copy: dsq[residues + n + 1], offsets / lengths / attempts[n] (the attempt whose path was kept),
+ * with traces st / node[residues + n + 1] laid out as dsq. */
+typedef struct p7x_emitted p7x_emitted;
+int     p7x_emit_block(const p7x_emit_model *em, int device, int64_t n, uint64_t seed, int want_traces, p7x_emitted **out);
+int     p7x_emit_block_host(const p7x_emit_model *em, int64_t n, uint64_t seed, int want_traces, int threads, p7x_emitted **out);
+int64_t p7x_emitted_info(const p7x_emitted *b, int which);
+int     p7x_emitted_copy(const p7x_emitted *b, uint8_t *dsq, int64_t *offsets, int32_t *lengths, int32_t *attempts, int8_t *st, int32_t *node);
+void    p7x_emitted_destroy(p7x_emitted *b);
+/* test seams: one Philox-4x32-10 block (key[2], counter[4] -> out[4]); the device bytes the first pass of n sequences
+ * takes, P7X_EMEM when they exceed <budget> (negative: no budget) */
+int p7x_debug_philox(const uint32_t *key2, const uint32_t *ctr4, uint32_t *out4);
+int p7x_debug_emit_bytes(int64_t n, int64_t cap, int traces, int64_t budget, int64_t *bytes);
+
 const char *p7x_last_error(void);
 
 #ifdef __cplusplus

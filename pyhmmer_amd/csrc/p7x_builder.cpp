@@ -10,6 +10,7 @@
 // The scores come from elsewhere: the device (p7x_calibrate.hip) or, in the CPU tests, the oracle.
 #include "p7x_host.hpp"
 #include "p7x_choice.hpp"
+#include "p7x_rng.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -90,47 +91,6 @@ double match_relent_sum(const float *mat, const float *bg_f, int M, int K)
   }
   return tot;
 }
-
-// ---------------------------------------------------------------- Easel's generators
-// The default one (esl_randomness_Create): MT19937 seeded by mt[z] = 69069 mt[z-1]; the fast one
-// (esl_randomness_CreateFast): the LCG the pipeline already draws with (fast_rng_state, lcg_next).  A deviate is x / 2^32 either way.
-struct EaselRng {
-  int kind = P7X_RNG_FAST;
-  uint32_t mt[624]; int mti = 0;
-  uint32_t x = 0;
-  void fill()
-  {
-    static const uint32_t mag01[2] = { 0x0u, 0x9908b0dfu };
-    uint32_t y; int z;
-    for (z = 0; z < 227; ++z) { y = (mt[z] & 0x80000000u) | (mt[z + 1] & 0x7fffffffu); mt[z] = mt[z + 397] ^ (y >> 1) ^ mag01[y & 1u]; }
-    for (; z < 623; ++z)      { y = (mt[z] & 0x80000000u) | (mt[z + 1] & 0x7fffffffu); mt[z] = mt[z - 227] ^ (y >> 1) ^ mag01[y & 1u]; }
-    y = (mt[623] & 0x80000000u) | (mt[0] & 0x7fffffffu);
-    mt[623] = mt[396] ^ (y >> 1) ^ mag01[y & 1u];
-    mti = 0;
-  }
-  void init(int kind_, uint32_t seed)
-  {
-    kind = kind_;
-    if (kind == P7X_RNG_MERSENNE) {
-      mt[0] = seed;
-      for (int z = 1; z < 624; ++z) mt[z] = 69069u * mt[z - 1];
-      fill();
-    } else {
-      x = fast_rng_state(seed);               // the pipeline's generator: p7x_domaindef.cpp
-    }
-  }
-  double next()
-  {
-    if (kind != P7X_RNG_MERSENNE) { x = lcg_next(x); return (double) x / 4294967296.0; }
-    if (mti >= 624) fill();
-    uint32_t y = mt[mti++];
-    y ^= (y >> 11);
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= (y >> 18);
-    return (double) y / 4294967296.0;
-  }
-};
 
 // esl_rnd_FChoose: the first residue whose cumulative probability exceeds the deviate -- the sums in double over the
 // Kahan-summed norm, the last residue of positive probability when rounding leaves every ratio below it (the same
@@ -267,6 +227,27 @@ int p7x_calibration_stream(int32_t abc_type, const float *bg_f, uint32_t seed, i
   r.init(generator, seed);
   for (int stage = 0; stage < 3; ++stage)
     for (int i = 0; i < kCalN; ++i) { draw_sample(r, bg_f, K, kCalL[stage], out); out += kCalL[stage]; }
+  return P7X_OK;
+}
+
+int p7x_rng_seed(int generator, uint32_t seed, uint32_t *state)
+{
+  if (!state) { set_error("p7x_rng_seed: bad arguments"); return P7X_EINVAL; }
+  if (generator != P7X_RNG_MERSENNE && generator != P7X_RNG_FAST) { set_error("unknown generator"); return P7X_EINVAL; }
+  EaselRng r;
+  r.init(generator, seed);
+  r.save(state);
+  return P7X_OK;
+}
+
+int p7x_rng_draw(int generator, uint32_t *state, size_t n, double *out)
+{
+  if (!state || (n && !out)) { set_error("p7x_rng_draw: bad arguments"); return P7X_EINVAL; }
+  if (generator != P7X_RNG_MERSENNE && generator != P7X_RNG_FAST) { set_error("unknown generator"); return P7X_EINVAL; }
+  EaselRng r;
+  r.load(generator, state);
+  for (size_t i = 0; i < n; ++i) out[i] = r.next();
+  r.save(state);
   return P7X_OK;
 }
 

@@ -4,8 +4,9 @@
 
 Reference: ``src/pyhmmer/easel.pyx`` -- ``Alphabet`` (:183-528), ``TextSequence``
 (:7483), ``DigitalSequence`` (:7741), ``DigitalSequenceBlock`` (:8629-8665),
-``SequenceFile`` (read / read_block).  Everything else in ``pyhmmer.easel``
-(MSA, SSI, matrices, genetic codes, ...) is out of scope.
+``SequenceFile`` (read / read_block), ``MSA`` / ``TextMSA`` / ``DigitalMSA`` as far as hmmalign needs them, and
+``Randomness`` (:7006-7161), the generator the emitters of ``plan7`` draw from.  Everything else in ``pyhmmer.easel``
+(SSI, matrices, genetic codes, ...) is out of scope.
 
 The one deliberate difference from the reference: a ``DigitalSequenceBlock`` here can
 be *packed* once (``block.packed()``) into the flat ``dsq_concat + offsets + lengths``
@@ -21,7 +22,7 @@ import numpy as np
 
 __all__ = [
     "Alphabet", "Sequence", "TextSequence", "DigitalSequence",
-    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA",
+    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "Randomness",
 ]
 
 _AMINO = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -755,3 +756,98 @@ class DigitalMSA(MSA):
     def textize(self) -> TextMSA:
         return TextMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
                                   self.pp_consensus, self.reference, self.secondary_structure)
+
+
+class Randomness:
+    """A random number generator (reference ``easel.pyx:7006-7161``, ``ESL_RANDOMNESS``): Easel's Mersenne Twister
+    (MT19937 seeded by ``mt[z] = 69069 mt[z-1]``) or, with ``fast=True``, its linear congruential generator
+    ``x <- 69069 x + 1`` -- the two generators the calibration stream and the domain-definition ensembles already draw
+    from (``p7x_rng.hpp``), so the streams of deviates are Easel's.  A seed of ``0`` or `None` takes an arbitrary seed
+    (from the operating system, where Easel mixes the clock and the process id).
+
+    ``normalvariate`` has the distribution of ``esl_rnd_Gaussian`` but not its stream: it is the polar Box-Muller method on
+    ``random()``, not the RANLIB routine Easel restates.  As in the reference ``seed`` is a method; the seed in use is
+    ``getstate()[1]`` and shows in the ``repr``."""
+
+    _WORDS = 626                  # P7X_RNG_STATE_WORDS: mt[624], mti, x
+
+    def __init__(self, seed=None, fast: bool = False):
+        self._fast = bool(fast)
+        self._state = np.zeros(self._WORDS, dtype=np.uint32)
+        self._seed = 0
+        self.seed(seed)
+
+    def seed(self, n=None) -> None:
+        """Reinitialize the generator with the given seed (``esl_randomness_Init``)."""
+        import ctypes as C
+        from . import _lib
+        n = 0 if n is None else int(n)
+        if not 0 <= n < 1 << 32:
+            raise OverflowError("seed does not fit 32 bits")
+        while n == 0:
+            n = int.from_bytes(os.urandom(4), "little")
+        self._seed = n
+        if _lib.lib().p7x_rng_seed(1 if self._fast else 0, n, self._state.ctypes.data) != 0:
+            raise ValueError(_lib.last_error())
+
+    @property
+    def fast(self) -> bool:
+        """`True` when the linear congruential generator is in use."""
+        return self._fast
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}({self._seed!r}, fast={self._fast!r})"
+
+    def getstate(self) -> tuple:
+        if self._fast:
+            return (True, self._seed, int(self._state[625]))
+        return (False, self._seed, int(self._state[624]), [int(x) for x in self._state[:624]])
+
+    def setstate(self, state: tuple) -> None:
+        self._seed = int(state[1])
+        self._fast = bool(state[0])
+        if self._fast:
+            self._state[625] = int(state[2])
+        else:
+            self._state[624] = int(state[2])
+            self._state[:624] = np.asarray(state[3], dtype=np.uint32)
+
+    def __getstate__(self):
+        return self.getstate()
+
+    def __setstate__(self, state):
+        if not hasattr(self, "_state"):
+            self._state = np.zeros(self._WORDS, dtype=np.uint32)
+        self.setstate(state)
+
+    def __reduce__(self):
+        state = self.getstate()
+        return Randomness, (state[1], state[0]), state
+
+    def copy(self) -> "Randomness":
+        new = Randomness.__new__(Randomness)
+        new._fast, new._seed, new._state = self._fast, self._seed, self._state.copy()
+        return new
+
+    def __copy__(self) -> "Randomness":
+        return self.copy()
+
+    def _draw(self, n: int) -> np.ndarray:
+        from . import _lib
+        out = np.empty(n, dtype=np.float64)
+        if _lib.lib().p7x_rng_draw(1 if self._fast else 0, self._state.ctypes.data, n, out.ctypes.data) != 0:
+            raise ValueError(_lib.last_error())
+        return out
+
+    def random(self) -> float:
+        """A uniform deviate on [0, 1) (``esl_random``)."""
+        return float(self._draw(1)[0])
+
+    def normalvariate(self, mu: float, sigma: float) -> float:
+        """A Gaussian deviate of mean ``mu`` and standard deviation ``sigma``."""
+        import math
+        while True:
+            u, v = 2.0 * self._draw(2) - 1.0
+            s = u * u + v * v
+            if 0.0 < s < 1.0:
+                return float(mu + sigma * u * math.sqrt(-2.0 * math.log(s) / s))

@@ -21,7 +21,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from .easel import (Alphabet, DigitalSequence, DigitalSequenceBlock, SequenceFile, eslAMINO, eslDNA,
+from .easel import (Alphabet, DigitalSequence, DigitalSequenceBlock, Randomness, SequenceFile, eslAMINO, eslDNA,
                     eslRNA)
 from .errors import (AlphabetMismatch, AllocationError, InvalidParameter, MissingCutoffs,
                      UnexpectedError, status_to_exception)
@@ -557,6 +557,127 @@ class HMM:
         v.consensus = ann(self.consensus)
         v.rf, v.mm, v.cs = ann(self.reference), ann(self.model_mask), ann(self.consensus_structure)
         return v, (t, mat, ins, compo)
+
+    # ---- sampling (reference plan7.pyx:2247-2334, 3141-3340; upstream p7_hmm_Sample, p7_CoreEmit).  The distribution, the
+    # generators and the signatures are the reference's; its draw-for-draw stream is not claimed.
+    @classmethod
+    def sample(cls, alphabet: Alphabet, M: int, randomness=None) -> "HMM":
+        """``p7_hmm_Sample``: a random valid model of ``M`` nodes -- every emission and transition row a draw from the uniform
+        Dirichlet (normalised ``-log(u)`` deviates), node ``M`` with no way into a delete state.  Named ``sampled-hmm``; as
+        upstream it sets no ``max_length`` (a long-target search computes one from the core model)."""
+        if M < 1:
+            raise ValueError("HMM has M < 1")
+        rng = randomness if isinstance(randomness, Randomness) else Randomness(randomness)
+        K = alphabet.K
+        hmm = cls(alphabet, M, "sampled-hmm")
+
+        def dirichlet(n):
+            u = rng._draw(n)
+            while not (u > 0.0).all():                      # log(0): draw the row again
+                u = rng._draw(n)
+            x = -np.log(u)
+            return (x / x.sum()).astype(np.float32)
+        t = hmm.transition_probabilities
+        for k in range(M + 1):
+            if k > 0:
+                hmm.match_emissions[k] = dirichlet(K)
+            hmm.insert_emissions[k] = dirichlet(K)
+            t[k, 0:3] = dirichlet(3)
+            t[k, 3:5] = dirichlet(2)
+            if k > 0:
+                t[k, 5:7] = dirichlet(2)
+        hmm.match_emissions[0, 0] = 1.0                     # the conventions of nodes 0 and M (p7_hmm.c)
+        t[0, 5], t[0, 6] = 1.0, 0.0
+        t[M, 2] = 0.0
+        t[M, 0:3] /= t[M, 0:3].sum()
+        t[M, 5], t[M, 6] = 1.0, 0.0
+        hmm.nseq, hmm.nseq_effective = 0, 0.0
+        hmm.set_composition()
+        hmm.set_consensus()
+        return hmm
+
+    def _emit_model(self) -> "_EmitModel":
+        """The cumulative tables the emitters draw from, built from the model as it is now: O(M K) work and one native
+        allocation on every call.  They are not kept on the HMM, whose arrays can change underneath them."""
+        return _EmitModel(self)
+
+    def _emit_core(self, em: "_EmitModel", rng: "Randomness", traces: bool = False):
+        """One ``p7_CoreEmit`` draw: (residues, states, nodes); states and nodes are None without ``traces``."""
+        cap = max(64, 2 * em.cap)
+        while True:
+            saved = rng._state.copy()
+            dsq = np.empty(cap, dtype=np.uint8)
+            st = np.empty(cap, dtype=np.int8) if traces else None
+            node = np.empty(cap, dtype=np.int32) if traces else None
+            n = C.c_int64()
+            rc = _lib.lib().p7x_emit_core(em.handle, 1 if rng.fast else 0, rng._state.ctypes.data, dsq.ctypes.data,
+                                          None if st is None else st.ctypes.data, None if node is None else node.ctypes.data, cap,
+                                          C.byref(n))
+            if rc != 0:
+                raise status_to_exception(rc, "p7x_emit_core", _lib.last_error())
+            if n.value <= cap:
+                return dsq[:n.value].copy(), (None if st is None else st[:n.value].copy()), (None if node is None else node[:n.value].copy())
+            rng._state[:] = saved                           # the same path again, with room for it
+            cap = int(n.value)
+
+    def emit_sequence(self, randomness=None) -> DigitalSequence:
+        """Emit a sequence from the core model (``p7_CoreEmit``): a path from node 0 by the model's transition rows, a residue
+        from the match or insert row of every M or I state entered; a path that emits nothing is drawn again.  As in the
+        reference only the ``sequence`` field is set, and a seed (or `None`) makes a ``Randomness(seed, fast=True)``.
+
+        Every call builds the model's cumulative tables anew (O(M K); the HMM is mutable, so they are not cached): a loop
+        of single draws pays that each time.  `emit_alignment` and `emit_block` build them once for all their sequences."""
+        rng = randomness if isinstance(randomness, Randomness) else Randomness(randomness, fast=True)
+        dsq, _, _ = self._emit_core(self._emit_model(), rng)
+        return DigitalSequence(self.alphabet, sequence=dsq)
+
+    def _emit_traces(self, N: int, rng: "Randomness"):
+        """N core paths as (sequences named ``<name>-sample<i>`` from 1, their `Trace` objects: B, the core states, E)."""
+        em = self._emit_model()
+        seqs, traces = [], Traces()
+        for i in range(N):
+            dsq, st, node = self._emit_core(em, rng, traces=True)
+            seqs.append(DigitalSequence(self.alphabet, name=f"{self.name}-sample{i + 1}", sequence=dsq))
+            traces.append(_core_trace(st, node, self.M))
+        return DigitalSequenceBlock(self.alphabet, seqs), traces
+
+    def emit_alignment(self, N: int, randomness=None):
+        """Emit ``N`` sequences from the core model and align them by their own paths (``p7_CoreEmit`` kept as traces, then
+        ``p7_tracealign_Seqs`` with all consensus columns): a `DigitalMSA` of ``N`` rows named ``<name>-sample<i>``, i from 1."""
+        from .easel import DigitalMSA
+        N = int(N)
+        if N < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        rng = randomness if isinstance(randomness, Randomness) else Randomness(randomness, fast=True)
+        if N == 0:
+            return DigitalMSA(self.alphabet)
+        seqs, traces = self._emit_traces(N, rng)
+        return TraceAligner().align_traces(self, seqs, traces, digitize=True, all_consensus_cols=True)
+
+    def emit_block(self, N: int, *, seed: int = 42, device: int = 0, traces: bool = False) -> "SequenceDatabase":
+        """Emit ``N`` sequences from the core model on the device (an extension; ``p7x_emit.hip``): one lane per sequence, every
+        (sequence, attempt, step) on its own Philox-4x32-10 block keyed by ``seed``, so sequence ``i`` is the same whatever
+        ``N``, and the same as the host twin's (test seam ``host_emit``).  The result is a `SequenceDatabase` of sequences named
+        ``<name>-sample<i>``, i from 0, whose ``block`` is a `DigitalSequenceBlock` for `hmmsearch` / `hmmalign`; it also
+        carries ``lengths``, ``offsets``, ``attempts`` (the attempt whose path was kept: earlier ones emitted nothing), ``cap``
+        and ``redrawn`` (sequences that outgrew the first pass's slot and were drawn again, identically, into an exact one),
+        and with ``traces=True`` ``states`` and ``nodes``: the state (1 match, 3 insert) and node that emitted each residue,
+        laid out as the packed residues (``offsets[i] .. offsets[i] + lengths[i]``).  The tables are built once per call."""
+        N = int(N)
+        if N < 0:
+            raise ValueError("the number of sequences to emit is negative")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise OverflowError("seed does not fit 64 bits")
+        em = self._emit_model()
+        h = C.c_void_p()
+        rc = _lib.lib().p7x_emit_block(em.handle, int(device), N, seed, 1 if traces else 0, C.byref(h))
+        if rc != 0:
+            raise status_to_exception(rc, "p7x_emit_block", _lib.last_error())
+        try:
+            return _EmittedDatabase(self, h, device)
+        finally:
+            _lib.lib().p7x_emitted_destroy(h)
 
 
 class HMMFile:
@@ -1270,6 +1391,45 @@ class Profile:
         if self._hmm is None:
             raise ValueError("profile is not configured")
         return OptimizedProfile(self._hmm, self._bg, self.L)
+
+    def _emit(self, hmm: HMM, background: Optional[Background], rng: "Randomness"):
+        """One ``p7_ProfileEmit`` draw: (residues, residues emitted by core states, passes through the core)."""
+        if hmm.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, hmm.alphabet)
+        bg = Background(self.alphabet) if background is None else background
+        if bg.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, bg.alphabet)
+        if self._hmm is None:
+            raise ValueError("profile is not configured")
+        if hmm.M != self.M:
+            raise ValueError(f"the HMM has {hmm.M} nodes, the profile {self.M}")
+        em = hmm._emit_model()
+        bgf = np.ascontiguousarray(bg.residue_frequencies, dtype=np.float32)
+        cap = max(256, 2 * em.cap + 2 * int(self.L))
+        counts = np.zeros(2, dtype=np.int32)
+        while True:
+            saved = rng._state.copy()
+            dsq = np.empty(cap, dtype=np.uint8)
+            n = C.c_int64()
+            rc = _lib.lib().p7x_emit_profile(em.handle, int(self.L), bgf.ctypes.data, 1 if rng.fast else 0, rng._state.ctypes.data,
+                                             dsq.ctypes.data, cap, C.byref(n), counts.ctypes.data)
+            if rc != 0:
+                raise status_to_exception(rc, "p7x_emit_profile", _lib.last_error())
+            if n.value <= cap:
+                return dsq[:n.value].copy(), int(counts[0]), int(counts[1])
+            rng._state[:] = saved
+            cap = int(n.value)
+
+    def emit_sequence(self, hmm: HMM, background: Optional[Background] = None, randomness=None) -> DigitalSequence:
+        """Emit a sequence from the implicit search profile (reference ``plan7.pyx:8109-8194``, ``p7_ProfileEmit``): N, C and
+        J emit background residues on their loops (length model ``L``), every pass through the core is a local fragment of
+        the model ``hmm`` (entry by the profile's B->Mk distribution, an exit drawn evenly from the nodes after it), and E
+        returns through J with probability one half.  ``AlphabetMismatch`` when ``hmm`` is of another alphabet; only the
+        ``sequence`` field is set; a seed (or `None`) makes a ``Randomness(seed, fast=True)``.  As `HMM.emit_sequence`, every
+        call builds the cumulative tables of ``hmm`` anew (O(M K))."""
+        rng = randomness if isinstance(randomness, Randomness) else Randomness(randomness, fast=True)
+        dsq, _, _ = self._emit(hmm, background, rng)
+        return DigitalSequence(self.alphabet, sequence=dsq)
 
 
 # --------------------------------------------------------------------------- results
@@ -2658,6 +2818,115 @@ class SequenceDatabase:
         if bias:
             out["filtersc"] = bs
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------- sampling
+class _EmitModel:
+    """The cumulative tables of a core model (``p7x_emit_model``): every emitter draws from them."""
+
+    def __init__(self, hmm: HMM):
+        view, keep = hmm._view()
+        self.handle = C.c_void_p()
+        rc = _lib.lib().p7x_emit_model_create(C.byref(view), C.byref(self.handle))
+        del keep
+        if rc != 0:
+            raise status_to_exception(rc, "p7x_emit_model_create", _lib.last_error())
+        elen, cap = C.c_double(), C.c_int32()
+        _lib.lib().p7x_emit_model_info(self.handle, C.byref(elen), C.byref(cap))
+        self.expected_length, self.cap = elen.value, cap.value
+
+    def __del__(self):
+        if getattr(self, "handle", None):
+            try:
+                _lib.lib().p7x_emit_model_destroy(self.handle)
+            except Exception:                       # noqa: BLE001 - interpreter shutdown
+                pass
+            self.handle = None
+
+
+class _EmittedDatabase(SequenceDatabase):
+    """What `HMM.emit_block` returns: the packed block (``block``: a `DigitalSequenceBlock` whose sequence objects are made
+    on demand) and what the emitter knows about every sequence.
+
+    A `SequenceDatabase` is resident on its device from its constructor on.  This one puts the constructor off until
+    something asks for what it sets (``_handle``, the name tables, anything it sets in future): a block that is only read,
+    or handed on as ``block``, is not uploaded, and the host twin's block exists where there is no device.  The
+    constructor that then runs is `SequenceDatabase.__init__` itself, on this object."""
+
+    def __init__(self, hmm: HMM, handle, device: int):
+        from .easel import PackedBlock, _LazyDigitalSequenceBlock
+        self._resident = False                      # None while SequenceDatabase.__init__ runs, True after it
+        lib = _lib.lib()
+        n, nres = int(lib.p7x_emitted_info(handle, 0)), int(lib.p7x_emitted_info(handle, 1))
+        self.cap, self.redrawn = int(lib.p7x_emitted_info(handle, 2)), int(lib.p7x_emitted_info(handle, 3))
+        self.on_device = bool(lib.p7x_emitted_info(handle, 4))
+        self.kernel_us = int(lib.p7x_emitted_info(handle, 6))
+        traces = bool(lib.p7x_emitted_info(handle, 5))
+        dsq = np.empty(nres + n + 1, dtype=np.uint8)
+        self.offsets, self.lengths = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
+        self.attempts = np.empty(n, dtype=np.int32)
+        self.states = np.empty(nres + n + 1, dtype=np.int8) if traces else None
+        self.nodes = np.empty(nres + n + 1, dtype=np.int32) if traces else None
+        rc = lib.p7x_emitted_copy(handle, dsq.ctypes.data, self.offsets.ctypes.data, self.lengths.ctypes.data, self.attempts.ctypes.data,
+                                  None if self.states is None else self.states.ctypes.data,
+                                  None if self.nodes is None else self.nodes.ctypes.data)
+        if rc != 0:
+            raise status_to_exception(rc, "p7x_emitted_copy", _lib.last_error())
+        # names <name>-sample<i> and one shared empty description, as the native FASTA parser's string table
+        names = [f"{hmm.name}-sample{i}".encode() for i in range(n)]
+        name_off = np.zeros(n, dtype=np.int64)
+        if n:
+            name_off[1:] = np.cumsum([len(b) + 1 for b in names[:-1]])
+        strtab = np.frombuffer(b"".join(b + b"\0" for b in names) + b"\0", dtype=np.uint8)
+        desc_off = np.full(n, strtab.shape[0] - 1, dtype=np.int64)
+        self.block = _LazyDigitalSequenceBlock(hmm.alphabet, PackedBlock.from_arrays(dsq, self.offsets, self.lengths), strtab,
+                                               name_off, desc_off)
+        self.device, self.alphabet = device, hmm.alphabet
+
+    def __getattr__(self, name):
+        # reached only for an attribute this object does not have yet: one that residency gives it
+        state = self.__dict__
+        if name.startswith("__") or state.get("_resident") is not False:
+            raise AttributeError(name)
+        state["_resident"] = None
+        before = set(state)
+        try:
+            SequenceDatabase.__init__(self, self.block, self.device)
+        except BaseException:
+            for half_made in set(state) - before:   # no device, no memory: the next use tries again from the start
+                del state[half_made]
+            state["_resident"] = False
+            raise
+        state["_resident"] = True
+        return getattr(self, name)
+
+    def __del__(self):
+        if self.__dict__.get("_resident"):
+            SequenceDatabase.__del__(self)
+
+    def __getitem__(self, index):
+        return self.block[index]
+
+
+def _core_trace(st: np.ndarray, node: np.ndarray, M: int) -> "Trace":
+    """The `Trace` of a core path from the states that emitted: B, the path with its delete states put back (a node the
+    path passed without emitting was deleted), E."""
+    ts, tk, ti = [_T_B], [0], [0]
+    k = 0
+    for r in range(len(st)):
+        s, kk = int(st[r]), int(node[r])
+        if s == _T_M:
+            for d in range(k + 1, kk):
+                ts.append(_T_D); tk.append(d); ti.append(0)
+        ts.append(s); tk.append(kk); ti.append(r + 1)
+        k = kk
+    for d in range(k + 1, M + 1):
+        ts.append(_T_D); tk.append(d); ti.append(0)
+    ts.append(_T_E); tk.append(0); ti.append(0)
+    t = Trace()
+    t.st, t.k, t.i = np.array(ts, dtype=np.int8), np.array(tk, dtype=np.int32), np.array(ti, dtype=np.int32)
+    t._M, t._L = M, len(st)
+    return t
 
 
 # ---------------------------------------------------------------------------------------------------------- hmmalign
