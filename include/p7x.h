@@ -686,6 +686,39 @@ void    p7x_emitted_destroy(p7x_emitted *b);
 int p7x_debug_philox(const uint32_t *key2, const uint32_t *ctr4, uint32_t *out4);
 int p7x_debug_emit_bytes(int64_t n, int64_t cap, int traces, int64_t budget, int64_t *bytes);
 
+/* ------------------------------------------------------------------ Builder.build_msa: p7x_msabuild.cpp, p7x_msabuild.hip
+ * A protein alignment as a query (hmmbuild).  ax[N * L]: the digital codes of the rows, one after the other (gap 20).
+ * p7x_msa_checksum: Jenkins' one-at-a-time hash over them, the CKSUM of the model.
+ * p7x_msa_counts: fragments (rows spanning less than fragthresh of the columns: the cells outside the span are missing
+ * data), relative weights (weighting 1: position-based over the columns with a residue share of at least symfrac, or the
+ * columns of rf_mask[L] when it is given; 0: none), consensus columns (weighted residue share of at least symfrac, or
+ * rf_mask), and the weighted counts of the rows as paths through them.  The passes over the alignment run on <device>;
+ * debug option "host_build" = 1 runs their host twin, which gives the same bits: every sum over the rows is a sum of
+ * integers (weights in fixed point, unit 2^-40).  "build_rows" = n: rows per block of the kernels.
+ * P7X_ERANGE: N > 2^20, L > 65,535, more consensus columns than p7x_max_model_length(); P7X_EINVAL: an empty alignment,
+ * no consensus column, an alphabet other than amino; P7X_ENODEVICE without a device (and without the seam).
+ * info: 0 N, 1 L, 2 M, 3 weighting columns, 4 counted on the device, 5 fragments, 6-9 nanoseconds of the four passes
+ * (column counts, weights, weighted counts, transitions; device events, wall clock for the twin), 10 of the upload.
+ * get: 0 uint32[L][32] rows holding each code per column, 1 uint64[N] weights, 2 uint64[L][32] weighted counts per column,
+ * 3 int32[M] column of every node (from 0), 4 uint64[M+1][32] weighted counts of every code at every node, 5 uint64[M+1][8]
+ * transition counts (MM MI MD IM II DM DD; node 0 is B): the I->I count, which can pass 2^64, is slot 4 (units 2^-40) plus
+ * slot 7 (units 2^-20); 6 / 7 the counts as doubles ([M+1][20], degenerate residues
+ * spread; [M+1][7]), 8 uint8[L] weighting columns, 9 uint8[N] fragments.
+ * p7x_msa_parameterize: priors (0: the amino Dirichlets, 1: Laplace), the effective sequence number (eff_mode 0: N, 1:
+ * entropy weighting to max(ere, (esigma + log2(M (M + 1) / 2)) / M) bits per node, ere <= 0: 0.59; 2: eff_value) and the
+ * probabilities of the model: t[(M+1)*7], mat / ins[(M+1)*20], caller-allocated; the insert rows are the mean of hmmbuild's
+ * insert prior, whatever bg_f holds.  t64 / mat64 (may be NULL): the same probabilities before they are
+ * rounded to float.  Host code. */
+typedef struct p7x_msacounts p7x_msacounts;
+uint32_t p7x_msa_checksum(const uint8_t *ax, size_t n);
+int      p7x_msa_counts(int32_t abc_type, const uint8_t *ax, int64_t N, int32_t L, const uint8_t *rf_mask, int weighting, double symfrac,
+                        double fragthresh, int device, p7x_msacounts **out);
+int64_t  p7x_msacounts_info(const p7x_msacounts *c, int which);
+int      p7x_msacounts_get(const p7x_msacounts *c, int which, void *out, size_t cap_bytes);
+void     p7x_msacounts_destroy(p7x_msacounts *c);
+int      p7x_msa_parameterize(const p7x_msacounts *c, const float *bg_f, int prior, int eff_mode, double eff_value, double ere, double esigma,
+                              float *t, float *mat, float *ins, double *neff, double *t64, double *mat64);
+
 const char *p7x_last_error(void);
 
 #ifdef __cplusplus

@@ -22,7 +22,7 @@ import numpy as np
 
 __all__ = [
     "Alphabet", "Sequence", "TextSequence", "DigitalSequence",
-    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "Randomness",
+    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness",
 ]
 
 _AMINO = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -756,6 +756,148 @@ class DigitalMSA(MSA):
     def textize(self) -> TextMSA:
         return TextMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
                                   self.pp_consensus, self.reference, self.secondary_structure)
+
+    def _codes(self) -> np.ndarray:
+        """The alignment as an ``(N, L)`` matrix of digital codes (every gap character is the alphabet's gap code):
+        what ``Builder.build_msa`` counts over."""
+        n, alen = len(self._rows), len(self)
+        out = self.alphabet._lut[np.frombuffer("".join(self._rows).encode("ascii"), dtype=np.uint8)].reshape(n, alen)
+        if (out == 255).any():
+            i, c = np.argwhere(out == 255)[0]
+            raise ValueError(f"Invalid symbol {self._rows[i][c]!r} for alphabet {self.alphabet!r}")
+        return out
+
+
+class MSAFile:
+    """Alignment reader with the reference's ``MSAFile`` surface (``read``, iteration, context manager).  Interleaved or
+    single-block Stockholm only: ``#=GF ID / AC / DE``, ``#=GS <name> AC / DE``, ``#=GC RF / SS_cons / PP_cons``,
+    ``#=GR <name> PP``, any number of alignments per file, each closed by ``//``.  Other annotation is skipped."""
+
+    def __init__(self, file, format: str = "stockholm", *, digital: bool = False, alphabet: Optional[Alphabet] = None):
+        if format not in ("stockholm", "pfam"):
+            raise ValueError(f"unsupported MSA format: {format!r} (only 'stockholm')")
+        if isinstance(file, (str, bytes, os.PathLike)):
+            self._fh = open(file, "r")
+            self._own = True
+            self.name = os.fspath(file)
+        else:
+            self._fh = file
+            self._own = False
+            self.name = getattr(file, "name", None)
+        self.format = "stockholm"
+        self.digital = digital
+        self.alphabet = alphabet
+        if digital and alphabet is None:
+            self.alphabet = self.guess_alphabet()
+            if self.alphabet is None:
+                raise ValueError("Could not determine alphabet of file")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self) -> None:
+        if self._own:
+            self._fh.close()
+
+    def guess_alphabet(self) -> Optional[Alphabet]:
+        """Amino unless at least nine residues in ten of the first alignment are nucleotides (RNA when it holds a U)."""
+        pos = self._fh.tell()
+        msa = self._read_text()
+        self._fh.seek(pos)
+        if msa is None:
+            return None
+        text = "".join(msa._rows).upper()
+        res = [c for c in text if c.isalpha()]
+        if not res:
+            return None
+        if sum(c in "ACGTUN" for c in res) >= 0.9 * len(res):
+            return Alphabet.rna() if "U" in res else Alphabet.dna()
+        return Alphabet.amino()
+
+    def _line(self) -> str:
+        line = self._fh.readline()
+        return line.decode() if isinstance(line, bytes) else line
+
+    def _read_text(self) -> Optional["TextMSA"]:
+        line = self._line()
+        while line and not line.strip():
+            line = self._line()
+        if not line:
+            return None
+        if not line.startswith("# STOCKHOLM 1."):
+            raise ValueError(f"not a Stockholm file: expected '# STOCKHOLM 1.0', found {line.rstrip()!r}")
+        gf, gc = {}, {}
+        names: List[str] = []
+        rows, pp, accs, descs = {}, {}, {}, {}
+        closed = False
+        for line in iter(self._line, ""):
+            line = line.rstrip("\r\n")
+            if line.startswith("//"):
+                closed = True
+                break
+            if not line.strip():
+                continue
+            if line.startswith("#=GF"):
+                f = line.split(None, 2)
+                if len(f) == 3 and f[1] in ("ID", "AC", "DE"):
+                    gf[f[1]] = (gf[f[1]] + " " if f[1] in gf else "") + f[2].strip()
+            elif line.startswith("#=GS"):
+                f = line.split(None, 3)
+                if len(f) == 4 and f[2] in ("AC", "DE"):
+                    (accs if f[2] == "AC" else descs)[f[1]] = f[3].strip()
+            elif line.startswith("#=GC"):
+                f = line.split()
+                if len(f) == 3:
+                    gc[f[1]] = gc.get(f[1], "") + f[2]
+            elif line.startswith("#=GR"):
+                f = line.split()
+                if len(f) == 4 and f[2] == "PP":
+                    pp[f[1]] = pp.get(f[1], "") + f[3]
+            elif line.startswith("#"):
+                continue
+            else:
+                f = line.split()
+                if len(f) != 2:
+                    raise ValueError(f"malformed Stockholm line: {line!r}")
+                if f[0] not in rows:
+                    names.append(f[0])
+                    rows[f[0]] = ""
+                rows[f[0]] += f[1]
+        if not closed:
+            raise ValueError("Stockholm alignment is not closed by '//'")
+        alen = len(rows[names[0]]) if names else 0
+        for what, d in (("sequence", rows), ("#=GR PP", pp), ("#=GC", gc)):
+            for key, text in d.items():
+                if len(text) != alen:
+                    raise ValueError(f"{what} line {key!r} has {len(text)} columns, the alignment {alen}")
+        msa = TextMSA._from_rows(names, [rows[n] for n in names], [descs.get(n, "") for n in names],
+                                 [accs.get(n, "") for n in names], [pp[n] for n in names] if len(pp) == len(names) and names else None,
+                                 gc.get("PP_cons"), gc.get("RF"), gc.get("SS_cons"))
+        msa.name, msa.accession, msa.description = gf.get("ID"), gf.get("AC"), gf.get("DE")
+        return msa
+
+    def read(self):
+        """The next alignment of the file (``TextMSA``, or ``DigitalMSA`` in digital mode); ``None`` at the end."""
+        msa = self._read_text()
+        if msa is None or not self.digital:
+            return msa
+        out = msa.digitize(self.alphabet)
+        out.name, out.accession, out.description = msa.name, msa.accession, msa.description
+        out._codes()                        # an illegal character is reported where the file is read
+        return out
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        msa = self.read()
+        if msa is None:
+            raise StopIteration
+        return msa
 
 
 class Randomness:

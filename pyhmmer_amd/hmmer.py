@@ -310,7 +310,7 @@ def phmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = 
     every model against the device's 600 resident random sequences, one set of launches for the batch -- and handed as
     optimized profiles to the machinery ``hmmsearch`` runs its HMM queries through (batched cascades, overlapped host
     stages).  ``callback`` receives ``(query sequence, total)``; every other keyword goes to ``Pipeline``.  MSA queries
-    (``Builder.build_msa``) are not offered."""
+    are not taken here: build their models with ``Builder.build_msa`` / ``build_msa_block`` and search with ``hmmsearch``."""
     import itertools
     if isinstance(queries, DigitalSequence):
         queries = (queries,)

@@ -12,6 +12,7 @@ import math
 import os
 import re
 import sys
+import time
 import weakref
 from typing import Iterable, Iterator, List, Optional, Sequence, Union
 
@@ -21,7 +22,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from .easel import (Alphabet, DigitalSequence, DigitalSequenceBlock, Randomness, SequenceFile, eslAMINO, eslDNA,
+from .easel import (Alphabet, DigitalMSA, DigitalSequence, DigitalSequenceBlock, Randomness, SequenceFile, eslAMINO, eslDNA,
                     eslRNA)
 from .errors import (AlphabetMismatch, AllocationError, InvalidParameter, MissingCutoffs,
                      UnexpectedError, status_to_exception)
@@ -2198,18 +2199,44 @@ def _calibrate(oms: Sequence["OptimizedProfile"], device: int = 0, seed: int = 4
 
 
 class Builder:
-    """The HMM builder for single-sequence queries (reference ``plan7.pyx:604-1150``; upstream ``p7_builder.c``): ``build`` turns
-    a protein sequence into the model ``phmmer`` searches with -- one node per residue, match emissions from the score
-    matrix, gap-open / gap-extend transitions -- and calibrates it on the device.  Amino alphabet and BLOSUM62 only (the DNA
-    score system belongs to nhmmer's sequence queries); ``build_msa`` and the architecture, weighting and prior options of
-    the reference are not offered."""
+    """The HMM builder (reference ``plan7.pyx:604-1150``; upstream ``p7_builder.c``).  ``build`` turns a protein sequence
+    into the model ``phmmer`` searches with -- one node per residue, match emissions from the score matrix, gap-open /
+    gap-extend transitions; ``build_msa`` turns a protein alignment into the model ``hmmbuild`` makes of it -- relative
+    weights, consensus columns, weighted counts (on the device), Dirichlet priors, entropy weighting.  Both calibrate the
+    model on the device.  Amino alphabet and BLOSUM62 only (the DNA score system and priors belong to nhmmer's queries).
+    Of the reference's options for alignments: ``architecture`` "fast" / "hand", ``weighting`` "pb" / "none",
+    ``effective_number`` "entropy" / "none" / a number, ``prior_scheme`` "alphabet" / "laplace"."""
 
-    def __init__(self, alphabet: Alphabet, *, popen: float = 0.02, pextend: float = 0.4, score_matrix: str = "BLOSUM62",
-                 seed: int = 42):
+    _ARCHITECTURES = ("fast", "hand")
+    _WEIGHTINGS = ("pb", "none")
+    _EFFECTIVE = ("entropy", "none")
+    _PRIORS = ("alphabet", "laplace")
+
+    def __init__(self, alphabet: Alphabet, *, architecture: str = "fast", weighting: str = "pb", effective_number="entropy",
+                 prior_scheme: Optional[str] = "alphabet", symfrac: float = 0.5, fragthresh: float = 0.5, ere: Optional[float] = None,
+                 esigma: float = 45.0, popen: float = 0.02, pextend: float = 0.4, score_matrix: str = "BLOSUM62", seed: int = 42):
         if not alphabet.is_amino():
             raise InvalidParameter("alphabet", alphabet, hint="amino alphabet: there is no DNA score system")
         self.alphabet = alphabet
         self.popen, self.pextend, self.score_matrix, self.seed = popen, pextend, score_matrix, seed
+        if architecture not in self._ARCHITECTURES:
+            raise InvalidParameter("architecture", architecture, choices=list(self._ARCHITECTURES))
+        if weighting not in self._WEIGHTINGS:
+            raise InvalidParameter("weighting", weighting, choices=list(self._WEIGHTINGS))
+        if isinstance(effective_number, str):
+            if effective_number not in self._EFFECTIVE:
+                raise InvalidParameter("effective_number", effective_number, choices=list(self._EFFECTIVE), hint="or a positive number")
+        elif isinstance(effective_number, bool) or not isinstance(effective_number, (int, float)) or not effective_number > 0:
+            raise InvalidParameter("effective_number", effective_number, choices=list(self._EFFECTIVE), hint="or a positive number")
+        if prior_scheme not in self._PRIORS:
+            raise InvalidParameter("prior_scheme", prior_scheme, choices=list(self._PRIORS))
+        for name, v in (("symfrac", symfrac), ("fragthresh", fragthresh)):
+            if not (0.0 <= v <= 1.0):
+                raise InvalidParameter(name, v, hint="real number between 0 and 1")
+        if ere is not None and not ere > 0:
+            raise InvalidParameter("ere", ere, hint="positive real number")
+        self.architecture, self.weighting, self.effective_number, self.prior_scheme = architecture, weighting, effective_number, prior_scheme
+        self.symfrac, self.fragthresh, self.ere, self.esigma = float(symfrac), float(fragthresh), ere, float(esigma)
 
     popen = property(lambda self: self._popen)
     pextend = property(lambda self: self._pextend)
@@ -2241,7 +2268,9 @@ class Builder:
         self._seed = int(seed)
 
     def copy(self) -> "Builder":
-        return Builder(self.alphabet, popen=self.popen, pextend=self.pextend, score_matrix=self.score_matrix, seed=self.seed)
+        return Builder(self.alphabet, architecture=self.architecture, weighting=self.weighting, effective_number=self.effective_number,
+                       prior_scheme=self.prior_scheme, symfrac=self.symfrac, fragthresh=self.fragthresh, ere=self.ere, esigma=self.esigma,
+                       popen=self.popen, pextend=self.pextend, score_matrix=self.score_matrix, seed=self.seed)
 
     def __copy__(self) -> "Builder":
         return self.copy()
@@ -2290,6 +2319,129 @@ class Builder:
         profile = Profile(hmm.M, self.alphabet)
         profile.configure(hmm, background, Pipeline.L_HINT)
         return hmm, profile, om
+
+    # ---- alignments as queries (hmmbuild; reference plan7.pyx:1018-1150, upstream p7_Builder)
+    def _msa_counts(self, msa: DigitalMSA, device: int = 0) -> "_MSACounts":
+        """Fragments, relative weights, consensus columns and weighted counts of an alignment (``p7x_msa_counts``): on the
+        device, or from the host twin under the seam ``host_build``."""
+        if not isinstance(msa, DigitalMSA):
+            raise TypeError(f"Expected DigitalMSA, found {type(msa).__name__}")
+        if msa.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, msa.alphabet)
+        if not msa.name:
+            raise ValueError("Could not build HMM: the alignment has no name")
+        ax = np.ascontiguousarray(msa._codes())
+        n, alen = ax.shape
+        if n < 1 or alen < 1:
+            raise ValueError("Could not build HMM: the alignment is empty")
+        rf = None
+        if self.architecture == "hand":
+            if msa.reference is None:
+                raise ValueError("Could not build HMM: the hand architecture needs a reference annotation (#=GC RF)")
+            rf = np.array([c not in "-._~" for c in msa.reference], dtype=np.uint8)
+        handle = C.c_void_p()
+        st = _lib.lib().p7x_msa_counts(self.alphabet.type_code, ax.ctypes.data, n, alen, None if rf is None else rf.ctypes.data,
+                                       int(self.weighting == "pb"), self.symfrac, self.fragthresh, int(device), C.byref(handle))
+        if st == 11:
+            raise ValueError(f"Could not build HMM: {_lib.last_error()}")
+        if st != 0:
+            raise status_to_exception(st, "p7x_msa_counts", _lib.last_error())
+        return _MSACounts(handle, ax)
+
+    def _msa_parameters(self, counts: "_MSACounts", background: Background, hmm: HMM):
+        """Priors, effective sequence number and probabilities (``p7x_msa_parameterize``) into the arrays of ``hmm``; returns
+        the effective sequence number and the transition and match probabilities as the library holds them before it rounds
+        them to float32 (float64 ``(M+1, 7)``, ``(M+1, K)``)."""
+        M, K = counts.M, self.alphabet.K
+        bgf = np.ascontiguousarray(background.residue_frequencies, dtype=np.float32)
+        eff = self.effective_number
+        mode, value = (1, 0.0) if eff == "entropy" else (0, 0.0) if eff == "none" else (2, float(eff))
+        neff = C.c_double()
+        t64, mat64 = np.zeros((M + 1, 7)), np.zeros((M + 1, K))
+        st = _lib.lib().p7x_msa_parameterize(counts._handle, bgf.ctypes.data, self._PRIORS.index(self.prior_scheme), mode, value,
+                                             0.0 if self.ere is None else float(self.ere), self.esigma,
+                                             hmm.transition_probabilities.ctypes.data, hmm.match_emissions.ctypes.data,
+                                             hmm.insert_emissions.ctypes.data, C.byref(neff), t64.ctypes.data, mat64.ctypes.data)
+        if st != 0:
+            raise status_to_exception(st, "p7x_msa_parameterize", _lib.last_error())
+        return float(neff.value), t64, mat64
+
+    def _model_msa(self, msa: DigitalMSA, background: Background, device: int = 0) -> HMM:
+        """The uncalibrated model of ``msa`` (upstream ``p7_Builder`` up to the calibration)."""
+        if background.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, background.alphabet)
+        counts = self._msa_counts(msa, device)
+        hmm = HMM(self.alphabet, counts.M, msa.name)
+        neff = self._msa_parameters(counts, background, hmm)[0]
+        hmm.accession = msa.accession or None
+        hmm.description = msa.description or None
+        hmm.nseq, hmm.nseq_effective = counts.N, float(np.float32(neff))      # upstream holds a float
+        hmm.checksum = int(_lib.lib().p7x_msa_checksum(counts._ax.ctypes.data, counts._ax.size))
+        hmm.map = np.concatenate([[0], counts.map + 1]).astype(np.int64)
+        if self.architecture == "hand":
+            hmm.reference = "".join(msa.reference[c] for c in counts.map)
+        hmm.set_composition()
+        hmm.set_consensus()
+        hmm.command_line = " ".join(sys.argv)
+        hmm.creation_time = time.ctime()
+        return hmm
+
+    def build_msa(self, msa: DigitalMSA, background: Background, device: int = 0):
+        """``(HMM, Profile, OptimizedProfile)`` of a query alignment, calibrated (reference ``plan7.pyx:1018-1150``)."""
+        return self.build_msa_block([msa], background, device=device)[0]
+
+    def build_msa_block(self, msas, background: Background, device: int = 0):
+        """The models of several alignments (an extension): each as ``build_msa`` makes it, all calibrated in one batch on
+        the device."""
+        hmms = [self._model_msa(msa, background, device) for msa in msas]
+        oms = [OptimizedProfile(hmm, background, Pipeline.L_HINT) for hmm in hmms]
+        if oms:
+            _calibrate(oms, device=device, seed=self._calibration_seed())
+        out = []
+        for hmm, om in zip(hmms, oms):
+            profile = Profile(hmm.M, self.alphabet)
+            profile.configure(hmm, background, Pipeline.L_HINT)
+            out.append((hmm, profile, om))
+        return out
+
+
+class _MSACounts:
+    """What ``p7x_msa_counts`` leaves of one alignment: sizes, and the arrays of ``p7x_msacounts_get`` by name."""
+
+    _ARRAYS = {"column_counts": (0, np.uint32, "L32"), "weights": (1, np.uint64, "N"), "weighted_counts": (2, np.uint64, "L32"),
+               "map": (3, np.int32, "M"), "node_counts": (4, np.uint64, "M32"), "transition_counts": (5, np.uint64, "M8"),
+               "emissions": (6, np.float64, "M20"), "transitions": (7, np.float64, "M7"), "weight_columns": (8, np.uint8, "L"),
+               "fragments": (9, np.uint8, "N")}
+
+    def __init__(self, handle, ax: np.ndarray):
+        self._handle, self._ax = handle, ax
+        info = lambda i: int(_lib.lib().p7x_msacounts_info(handle, i))
+        self.N, self.L, self.M, self.weight_column_count, self.on_device, self.fragment_count = (info(i) for i in range(6))
+        self.kernel_ns = tuple(info(i) for i in range(6, 10))
+        self.upload_ns = info(10)
+        self.map = self._get("map")
+
+    def __del__(self):
+        try:
+            if self._handle:
+                _lib.lib().p7x_msacounts_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    def _get(self, name: str) -> np.ndarray:
+        which, dtype, shape = self._ARRAYS[name]
+        shape = {"L32": (self.L, 32), "N": (self.N,), "M": (self.M,), "M32": (self.M + 1, 32), "M7": (self.M + 1, 7), "M8": (self.M + 1, 8),
+                 "M20": (self.M + 1, 20), "L": (self.L,)}[shape]
+        out = np.zeros(shape, dtype=dtype)
+        if _lib.lib().p7x_msacounts_get(self._handle, which, out.ctypes.data, out.nbytes) != 0:
+            raise ValueError(_lib.last_error())
+        return out
+
+    def __getattr__(self, name: str):
+        if name in _MSACounts._ARRAYS:
+            return self._get(name)
+        raise AttributeError(name)
 
 
 # --------------------------------------------------------------------------- Pipeline
