@@ -719,6 +719,32 @@ void     p7x_msacounts_destroy(p7x_msacounts *c);
 int      p7x_msa_parameterize(const p7x_msacounts *c, const float *bg_f, int prior, int eff_mode, double eff_value, double ere, double esigma,
                               float *t, float *mat, float *ins, double *neff, double *t64, double *mat64);
 
+/* ------------------------------------------------------------------ pairwise identity: p7x_msapair.cpp, p7x_msapair.hip
+ * The all-pairs fractional identity of the rows of an alignment of any alphabet (ax[N * L] digital codes, as above), and the
+ * two things built on it.  len_i: canonical residues of row i; idents_ij: columns where both rows hold the same canonical
+ * residue; pid_ij = idents_ij / min(len_i, len_j), 0 when that is 0; two rows are linked when pid_ij >= (double)(float) maxid.
+ * The counting runs on <device>; debug option "host_pairid" = 1 runs the host twin, which gives the same bytes: everything is
+ * an integer, "linked" included (idents >= need[min len], a table built on the host).  "pairid_tile" = n (1..64): rows per
+ * tile side of the kernel, and candidate blocks / bands of two tiles.  P7X_ENODEVICE without a device (and without the seam);
+ * P7X_ERANGE beyond the limits; P7X_EINVAL for an empty alignment or a code outside the alphabet.
+ * p7x_msa_pair_idents: idents[N][N] and len[N] (may be NULL); N <= 4,096.
+ * p7x_msa_idfilter: the greedy identity filter.  Rows are visited in order[N] (a permutation); a row is kept unless it is
+ *   linked to a row kept before it.  keep[N]: 1 for the rows kept.  N <= 2^20, L <= 65,535.
+ * p7x_msa_linkage: single-linkage clusters of "linked".  cluster[N]: the smallest row index of every row's cluster;
+ *   *nclusters (may be NULL).  N <= 2^18: N^2 / 16 bytes of link bits come back from the device (4 GiB at the limit).
+ * stats[4] (may be NULL): pairs compared, nanoseconds of the kernels (device events; wall clock for the twin), nanoseconds
+ *   of the upload, 1 when counted on the device.
+ * p7x_debug_msa_pair_links (test seam): rows_a[na] against rows_b[nb] (row indices): bits[na][(nb + 63) / 64], bit j & 63 of
+ *   word j / 64 set when rows_a[i] and rows_b[j] are linked, and any[na], 1 when the row is linked to any of rows_b; either
+ *   may be NULL. */
+int p7x_msa_pair_idents(int32_t abc_type, const uint8_t *ax, int64_t N, int32_t L, int device, uint32_t *idents, uint32_t *len);
+int p7x_msa_idfilter(int32_t abc_type, const uint8_t *ax, int64_t N, int32_t L, const int64_t *order, double maxid, int device,
+                     uint8_t *keep, int64_t *stats);
+int p7x_msa_linkage(int32_t abc_type, const uint8_t *ax, int64_t N, int32_t L, double maxid, int device, int32_t *cluster,
+                    int64_t *nclusters, int64_t *stats);
+int p7x_debug_msa_pair_links(int32_t abc_type, const uint8_t *ax, int64_t N, int32_t L, double maxid, int device, const int32_t *rows_a,
+                             int64_t na, const int32_t *rows_b, int64_t nb, uint64_t *bits, uint8_t *any);
+
 const char *p7x_last_error(void);
 
 #ifdef __cplusplus

@@ -31,6 +31,7 @@ _RNA = "ACGU-RYMKSWHBVDN*~"
 
 eslRNA, eslDNA, eslAMINO = 1, 2, 3   # libeasel/alphabet.pxd type codes
 DSQ_SENTINEL = 255                   # libeasel/__init__.pxd:21 (eslDSQ_SENTINEL)
+_MSA_WEIGHT_PREFERENCES = ("conscover", "origorder", "random")      # easel.pyx:175-179
 
 
 class Alphabet:
@@ -646,6 +647,7 @@ class MSA:
         self.pp_consensus: Optional[str] = None
         self.reference: Optional[str] = None
         self.secondary_structure: Optional[str] = None
+        self._weights: Optional[np.ndarray] = None      # None: the default weights (Easel's eslMSA_HASWGTS unset)
         for seq in sequences or ():
             self._add(seq)
 
@@ -694,6 +696,90 @@ class MSA:
     def alignment(self) -> tuple:
         return tuple(self._rows)
 
+    # ---- sequence weights, fragments, subsets (reference easel.pyx:5135-5196, 5274, 5324)
+    @property
+    def sequence_weights(self) -> np.ndarray:
+        """The weights of the rows (float64, one per row; a numpy array where the reference returns a ``VectorD``): ones
+        by default.  Set them through the property, which checks that there is one per row and that they sum to the
+        number of rows within 1e-3; ``del msa.sequence_weights`` goes back to the default."""
+        if self._weights is None:
+            return np.ones(len(self._rows), dtype=np.float64)
+        return self._weights
+
+    @sequence_weights.setter
+    def sequence_weights(self, weights) -> None:
+        if weights is None:
+            raise TypeError("weights must not be None")
+        w = np.array(weights, dtype=np.float64)
+        n = len(self._rows)
+        if w.ndim != 1 or w.shape[0] != n:
+            raise ValueError(f"dimension mismatch: expected {n}, found {w.shape[0] if w.ndim == 1 else w.shape}")
+        s = float(w.sum())
+        if not abs(s - n) <= 0.001:
+            raise ValueError(f"weights must sum to {n}, got {s} instead")
+        self._weights = w
+
+    @sequence_weights.deleter
+    def sequence_weights(self) -> None:
+        self._weights = None
+
+    def _residue_mask(self) -> np.ndarray:
+        """``(N, L)`` bool: the cells that hold a residue.  In a text alignment every alphanumeric character is one."""
+        n, alen = len(self._rows), len(self)
+        raw = np.frombuffer("".join(self._rows).encode("ascii"), dtype=np.uint8).reshape(n, alen)
+        return ((raw >= 48) & (raw <= 57)) | ((raw >= 65) & (raw <= 90)) | ((raw >= 97) & (raw <= 122))
+
+    def _spans(self):
+        """Per row: whether it has a residue, the columns of its first and last one."""
+        res = self._residue_mask()
+        alen = res.shape[1]
+        has = res.any(axis=1) if alen else np.zeros(res.shape[0], dtype=bool)
+        first = res.argmax(axis=1) if alen else np.zeros(res.shape[0], dtype=np.int64)
+        last = alen - 1 - res[:, ::-1].argmax(axis=1) if alen else np.zeros(res.shape[0], dtype=np.int64)
+        return res, has, first, last
+
+    def mark_fragments(self, threshold: float) -> np.ndarray:
+        """Which rows are fragments (a bool array where the reference returns a ``Bitfield``): those whose span, first to
+        last residue, is less than ``threshold`` (taken as a C ``float``, as in the reference) of the columns.  A row
+        without residues is not one (the rule of ``Builder.build_msa``).  Host code."""
+        from .errors import InvalidParameter
+        if not 0.0 <= threshold <= 1.0:
+            raise InvalidParameter("threshold", threshold, hint="real number between 0 and 1")
+        n, alen = len(self._rows), len(self)
+        if n == 0 or alen == 0:
+            return np.zeros(n, dtype=bool)
+        _, has, first, last = self._spans()
+        return has & ((last - first + 1).astype(np.float64) / float(alen) < float(np.float32(threshold)))
+
+    def select(self, sequences=None, columns=None) -> "MSA":
+        """A copy holding a subset of the rows and / or columns, by index, in the alignment's own order (the indices make
+        a mask, as in the reference); per-row and per-column annotation follows.  `IndexError` for an index out of bounds."""
+        import operator
+
+        def mask(indices, n):
+            m = np.zeros(n, dtype=bool)
+            for i in indices:
+                i = operator.index(i)
+                if not 0 <= i < n:
+                    raise IndexError(i)
+                m[i] = True
+            return np.flatnonzero(m)
+
+        n, alen = len(self._rows), len(self)
+        rows = np.arange(n) if sequences is None else mask(sequences, n)
+        cols = None if columns is None else mask(columns, alen)
+        cut = (lambda s: s) if cols is None else (
+            lambda s: None if s is None else np.frombuffer(s.encode("ascii"), dtype=np.uint8)[cols].tobytes().decode("ascii"))
+        pp = self.posterior_probabilities
+        out = type(self)._from_rows([self._names[i] for i in rows], [cut(self._rows[i]) for i in rows],
+                                    [self._descs[i] for i in rows], [self._accs[i] for i in rows],
+                                    None if pp is None else [cut(pp[i]) for i in rows], cut(self.pp_consensus), cut(self.reference),
+                                    cut(self.secondary_structure), alphabet=getattr(self, "alphabet", None))
+        out.name, out.description, out.accession = self.name, self.description, self.accession
+        if self._weights is not None:
+            out._weights = self._weights[rows].copy()
+        return out
+
     def write(self, fh, format: str = "stockholm") -> None:
         """Write the alignment to a file object (binary or text) in Stockholm format, as Easel's writer prints it."""
         if format != "stockholm":
@@ -733,8 +819,10 @@ class TextMSA(MSA):
                 for nm, r, d, a in zip(self._names, self._rows, self._descs, self._accs)]
 
     def digitize(self, alphabet: Alphabet) -> "DigitalMSA":
-        return DigitalMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
-                                     self.pp_consensus, self.reference, self.secondary_structure, alphabet=alphabet)
+        out = DigitalMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
+                                    self.pp_consensus, self.reference, self.secondary_structure, alphabet=alphabet)
+        out._weights = None if self._weights is None else self._weights.copy()
+        return out
 
 
 class DigitalMSA(MSA):
@@ -754,8 +842,162 @@ class DigitalMSA(MSA):
                 for nm, r, d, a in zip(self._names, self._rows, self._descs, self._accs)]
 
     def textize(self) -> TextMSA:
-        return TextMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
-                                  self.pp_consensus, self.reference, self.secondary_structure)
+        out = TextMSA._from_rows(self._names, self._rows, self._descs, self._accs, self.posterior_probabilities,
+                                 self.pp_consensus, self.reference, self.secondary_structure)
+        out._weights = None if self._weights is None else self._weights.copy()
+        return out
+
+    def _residue_mask(self) -> np.ndarray:
+        """Residues are the canonical and the degenerate codes; the gap, ``*`` and ``~`` are none."""
+        ax, K, Kp = self._codes(), self.alphabet.K, self.alphabet.Kp
+        return (ax < K) | ((ax > K) & (ax <= Kp - 3))
+
+    # ---- preparing an alignment: identity filter and relative weights (reference easel.pyx:6247-6477; DESIGN.md 3.16)
+    @staticmethod
+    def _check_weight_arguments(fragment_threshold, consensus_fraction, sample_threshold, sample_count, max_fragments, preference):
+        from .errors import InvalidParameter
+        if fragment_threshold < 0 or fragment_threshold > 1:
+            raise InvalidParameter("fragment_threshold", fragment_threshold, hint="real number between 0 and 1")
+        if consensus_fraction < 0 or consensus_fraction > 1:
+            raise InvalidParameter("consensus_fraction", consensus_fraction, hint="real number between 0 and 1")
+        if sample_threshold < 0:
+            raise InvalidParameter("sample_threshold", sample_threshold, hint="positive integer")
+        if sample_count < 0:
+            raise InvalidParameter("sample_count", sample_count, hint="positive integer")
+        if max_fragments < 0:
+            raise InvalidParameter("max_fragments", max_fragments, hint="positive integer")
+        if preference not in _MSA_WEIGHT_PREFERENCES:
+            raise InvalidParameter("preference", preference, choices=list(_MSA_WEIGHT_PREFERENCES))
+
+    def _rf_mask(self, ignore_rf: bool) -> Optional[np.ndarray]:
+        if self.reference is None or ignore_rf:
+            return None
+        return np.array([c not in "-._~" for c in self.reference], dtype=np.uint8)
+
+    def _conscover_order(self, fragment_threshold: float, consensus_fraction: float, ignore_rf: bool) -> np.ndarray:
+        """The rows by decreasing number of consensus columns inside their span; ties keep the alignment's order.
+        Consensus columns: the ``#=GC RF`` columns, or residues / (residues + gaps) >= ``consensus_fraction`` over all
+        the rows, a fragment's cells outside its span counting as missing.  O(N L) host code."""
+        res, has, first, last = self._spans()
+        n, alen = res.shape
+        cons = self._rf_mask(ignore_rf)
+        if cons is None:
+            gap = self._codes() == self.alphabet.K
+            frag = has & ((last - first + 1).astype(np.float64) / float(alen) < fragment_threshold)
+            if frag.any():
+                cols = np.arange(alen)
+                gap &= ~(frag[:, None] & ((cols[None, :] < first[:, None]) | (cols[None, :] > last[:, None])))
+            r, g = res.sum(axis=0, dtype=np.int64), gap.sum(axis=0, dtype=np.int64)
+            cons = (r + g > 0) & (r.astype(np.float64) >= consensus_fraction * (r + g).astype(np.float64))
+        cum = np.concatenate([[0], np.cumsum(cons != 0, dtype=np.int64)])
+        cover = np.where(has, cum[last + 1] - cum[first], 0)
+        return np.argsort(-cover, kind="stable").astype(np.int64)
+
+    def _filter_order(self, preference: str, fragment_threshold: float = 0.5, consensus_fraction: float = 0.5,
+                      ignore_rf: bool = False, seed: Optional[int] = 42) -> np.ndarray:
+        """The order in which ``identity_filter`` visits the rows (int64 row indices)."""
+        n = len(self._rows)
+        if preference == "conscover":
+            return self._conscover_order(float(np.float32(fragment_threshold)), float(np.float32(consensus_fraction)), bool(ignore_rf))
+        order = np.arange(n, dtype=np.int64)
+        if preference == "random":
+            u = Randomness((int(seed) & 0xFFFFFFFF) if seed else None)._draw(max(n - 1, 1))
+            for k, i in enumerate(range(n - 1, 0, -1)):            # Fisher-Yates, from the top
+                j = int(u[k] * (i + 1))
+                order[i], order[j] = order[j], order[i]
+        return order
+
+    def identity_filter(self, max_identity: float = 0.8, fragment_threshold: float = 0.5, consensus_fraction: float = 0.5,
+                        ignore_rf: bool = False, sample: bool = True, sample_threshold: int = 50000, sample_count: int = 10000,
+                        max_fragments: int = 5000, seed: Optional[int] = 42, preference: str = "conscover",
+                        device: int = 0) -> "DigitalMSA":
+        """Remove rows by fractional identity (``esl-weight -f``; reference ``easel.pyx:6369-6477``): the rows are visited
+        in the order of ``preference`` and a row is kept unless its pairwise identity -- identical canonical residues over
+        the shorter of the two rows -- to a row already kept is at least ``max_identity`` (taken as a C ``float``, as
+        in the reference).  The result holds the rows kept, in the alignment's own order.
+
+        ``preference``: ``"conscover"`` (rows whose span covers more consensus columns first), ``"origorder"``, or
+        ``"random"`` (a shuffle drawn from ``Randomness(seed)``; 0 or `None`: an arbitrary seed).  The consensus is always
+        taken from all the rows: ``sample``, ``sample_threshold``, ``sample_count`` and ``max_fragments`` are checked as
+        the reference checks them and otherwise unused.  The pairwise identities are counted on ``device``; there is no
+        CPU path (`DeviceUnavailable` without a device)."""
+        from . import _lib
+        from .errors import status_to_exception
+        self._check_weight_arguments(fragment_threshold, consensus_fraction, sample_threshold, sample_count, max_fragments, preference)
+        n, alen = len(self._rows), len(self)
+        if n == 0 or alen == 0:
+            return self.select()
+        order = self._filter_order(preference, fragment_threshold, consensus_fraction, ignore_rf, seed)
+        ax = np.ascontiguousarray(self._codes())
+        keep = np.zeros(n, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.int64)
+        st = _lib.lib().p7x_msa_idfilter(self.alphabet.type_code, ax.ctypes.data, n, alen, order.ctypes.data, float(max_identity),
+                                         int(device), keep.ctypes.data, stats.ctypes.data)
+        if st != 0:
+            raise status_to_exception(st, "p7x_msa_idfilter", _lib.last_error())
+        out = self.select(sequences=np.flatnonzero(keep))
+        out._pair_stats = stats
+        return out
+
+    def compute_weights(self, method: str = "pb", max_identity: float = 0.62, fragment_threshold: float = 0.5,
+                        consensus_fraction: float = 0.5, ignore_rf: bool = False, sample: bool = True, sample_threshold: int = 50000,
+                        sample_count: int = 10000, max_fragments: int = 5000, seed: Optional[int] = 42,
+                        preference: str = "conscover", device: int = 0) -> np.ndarray:
+        """Relative weights of the rows (``esl-weight``; reference ``easel.pyx:6247-6367``), stored in
+        ``sequence_weights`` and returned (a numpy array where the reference returns a ``VectorD``).
+
+        ``"blosum"``: single-linkage clusters of the rows at ``max_identity`` (pairwise identity as in
+        ``identity_filter``), 1 / (size of the row's cluster), scaled to sum to the number of rows; any alphabet; the
+        identities are counted on ``device``.  ``"pb"``: Henikoff position-based weights over the consensus columns, by
+        the unit behind ``Builder.build_msa`` (``fragment_threshold``, ``consensus_fraction`` and the ``#=GC RF`` line
+        mapped onto it; weights in fixed point, unit 2^-40): amino alignments only.  ``"gsc"`` is not built.  The four
+        sampling arguments and ``preference`` are checked and otherwise unused."""
+        import ctypes as C
+        from . import _lib
+        from .errors import InvalidParameter, status_to_exception
+        method = method.lower()
+        if method == "gsc":
+            raise NotImplementedError("Gerstein/Sonnhammer/Chothia weights are not built (DESIGN.md 3.16)")
+        if method not in ("pb", "blosum"):
+            raise InvalidParameter("method", method, choices=["pb", "gsc", "blosum"])
+        n, alen = len(self._rows), len(self)
+        if method == "blosum":
+            if n == 0 or alen == 0:
+                w = np.ones(n, dtype=np.float64)
+            else:
+                ax = np.ascontiguousarray(self._codes())
+                cluster = np.zeros(n, dtype=np.int32)
+                ncl, stats = C.c_int64(), np.zeros(4, dtype=np.int64)
+                st = _lib.lib().p7x_msa_linkage(self.alphabet.type_code, ax.ctypes.data, n, alen, float(max_identity), int(device),
+                                                cluster.ctypes.data, C.byref(ncl), stats.ctypes.data)
+                if st != 0:
+                    raise status_to_exception(st, "p7x_msa_linkage", _lib.last_error())
+                w = 1.0 / np.bincount(cluster, minlength=n)[cluster].astype(np.float64)
+                w *= n / w.sum()
+                self._pair_stats, self._clusters = stats, cluster
+        else:
+            self._check_weight_arguments(fragment_threshold, consensus_fraction, sample_threshold, sample_count, max_fragments, preference)
+            if not self.alphabet.is_amino():
+                raise NotImplementedError("position-based weights are built for amino alignments only (the unit behind Builder.build_msa)")
+            if n == 0 or alen == 0:
+                raise ValueError("the alignment is empty")
+            ax = np.ascontiguousarray(self._codes())
+            rf = self._rf_mask(bool(ignore_rf))
+            handle = C.c_void_p()
+            lib = _lib.lib()
+            st = lib.p7x_msa_counts(self.alphabet.type_code, ax.ctypes.data, n, alen, None if rf is None else rf.ctypes.data, 1,
+                                    float(np.float32(consensus_fraction)), float(np.float32(fragment_threshold)), int(device), C.byref(handle))
+            if st != 0:
+                raise status_to_exception(st, "p7x_msa_counts", _lib.last_error())
+            try:
+                wq = np.zeros(n, dtype=np.uint64)
+                if lib.p7x_msacounts_get(handle, 1, wq.ctypes.data, wq.nbytes) != 0:
+                    raise ValueError(_lib.last_error())
+            finally:
+                lib.p7x_msacounts_destroy(handle)
+            w = np.ldexp(wq.astype(np.float64), -40)
+        self._weights = w
+        return w
 
     def _codes(self) -> np.ndarray:
         """The alignment as an ``(N, L)`` matrix of digital codes (every gap character is the alphabet's gap code):
@@ -770,7 +1012,7 @@ class DigitalMSA(MSA):
 
 class MSAFile:
     """Alignment reader with the reference's ``MSAFile`` surface (``read``, iteration, context manager).  Interleaved or
-    single-block Stockholm only: ``#=GF ID / AC / DE``, ``#=GS <name> AC / DE``, ``#=GC RF / SS_cons / PP_cons``,
+    single-block Stockholm only: ``#=GF ID / AC / DE``, ``#=GS <name> AC / DE / WT``, ``#=GC RF / SS_cons / PP_cons``,
     ``#=GR <name> PP``, any number of alignments per file, each closed by ``//``.  Other annotation is skipped."""
 
     def __init__(self, file, format: str = "stockholm", *, digital: bool = False, alphabet: Optional[Alphabet] = None):
@@ -832,7 +1074,7 @@ class MSAFile:
             raise ValueError(f"not a Stockholm file: expected '# STOCKHOLM 1.0', found {line.rstrip()!r}")
         gf, gc = {}, {}
         names: List[str] = []
-        rows, pp, accs, descs = {}, {}, {}, {}
+        rows, pp, accs, descs, wts = {}, {}, {}, {}, {}
         closed = False
         for line in iter(self._line, ""):
             line = line.rstrip("\r\n")
@@ -849,6 +1091,8 @@ class MSAFile:
                 f = line.split(None, 3)
                 if len(f) == 4 and f[2] in ("AC", "DE"):
                     (accs if f[2] == "AC" else descs)[f[1]] = f[3].strip()
+                elif len(f) == 4 and f[2] == "WT":
+                    wts[f[1]] = float(f[3])
             elif line.startswith("#=GC"):
                 f = line.split()
                 if len(f) == 3:
@@ -878,6 +1122,8 @@ class MSAFile:
                                  [accs.get(n, "") for n in names], [pp[n] for n in names] if len(pp) == len(names) and names else None,
                                  gc.get("PP_cons"), gc.get("RF"), gc.get("SS_cons"))
         msa.name, msa.accession, msa.description = gf.get("ID"), gf.get("AC"), gf.get("DE")
+        if names and all(n in wts for n in names):      # the file's weights as they stand, as Easel takes them
+            msa._weights = np.array([wts[n] for n in names], dtype=np.float64)
         return msa
 
     def read(self):
