@@ -326,6 +326,10 @@ int  p7x_debug_order_spread(const p7x_oprofile *om, const uint8_t *dsq1, int32_t
  * whose rows the region-scan guard scans again): the special-state rows of dsq1[1..L], multihit with the length model of L,
  * fx / bx = (L+1) x [E,N,J,B,C,SCALE] floats each. */
 int  p7x_debug_parser_rows(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, float *fx, float *bx);
+/* Test seam of the bias filter's host twin (bias_filter_score: what the F3 guard and the long-target windows score with, the
+ * same float32 operations as bias_kernel): p7_bg_FilterScore of dsq1[1..L] in nats.  L = 0: the null1 score of an empty
+ * target, no residue read. */
+int  p7x_debug_bias_filter_host(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, float *sc);
 /* Test seam of the long-target SSV scan's tables (host code, no device): the registers per lane R the kernel takes for this
  * model, the most a cell can lose in one row with a canonical residue (byte units), and the table it stages in LDS --
  * [parity][x < 4][q][lane][c] packed pairs (lo, hi) of bias - rb[x][k], register j = 4q + c of the lane holding nodes

@@ -239,6 +239,7 @@ _SIGNATURES = {
     "p7x_debug_choice": (C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
     "p7x_debug_order_spread": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int, _VP]),
     "p7x_debug_parser_rows": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP]),
+    "p7x_debug_bias_filter_host": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_float)]),
     "p7x_debug_ssv_tables": (C.c_int64, [_VP, C.c_int, _VP, _VP, _VP, C.c_size_t]),
     "p7x_debug_ssv_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int]),
     "p7x_debug_ssv_part_tables": (C.c_int64, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t]),

@@ -1440,6 +1440,7 @@ int host_forward_parser_exact(const Profile &p, const uint8_t *dsq1, int L, floa
 // p7_bg_FilterScore: Forward score of the two-state composition HMM (esl_hmm_Forward), float arithmetic as upstream
 float bias_filter_score(const Profile &p, const uint8_t *dsq, int64_t L)
 {
+  if (L < 1) return null1_score((int) L);         // no residue 1 to start from: dsq[1] is the sentinel (bias_kernel does the same)
   const Alphabet &abc = Alphabet::get(p.abc_type);
   float eo[MAXKP][2];
   for (int x = 0; x < p.Kp; ++x) { eo[x][0] = 1.0f; eo[x][1] = 1.0f; }
@@ -1681,6 +1682,17 @@ extern "C" int p7x_debug_parser_rows(const p7x_oprofile *om, const uint8_t *dsq1
   if (st != P7X_OK) return st;
   std::memcpy(fx, f.data(), f.size() * sizeof(float));
   std::memcpy(bx, b.data(), b.size() * sizeof(float));
+  return P7X_OK;
+}
+
+// Test seam of the bias filter's host twin (tests/test_host_bias_reference.py holds it to the float64 reference)
+extern "C" int p7x_debug_bias_filter_host(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, float *sc)
+{
+  using namespace p7x;
+  if (!om || !dsq1 || L < 0 || !sc) { set_error("p7x_debug_bias_filter_host: bad arguments"); return P7X_EINVAL; }
+  for (int32_t i = 1; i <= L; ++i)
+    if (dsq1[i] >= om->p.Kp) { set_error("p7x_debug_bias_filter_host: residue code out of range"); return P7X_EINVAL; }
+  *sc = bias_filter_score(om->p, dsq1, L);
   return P7X_OK;
 }
 

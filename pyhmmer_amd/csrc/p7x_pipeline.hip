@@ -167,7 +167,7 @@ __global__ void bias_kernel(const ArgRef ref)
     const float usc = b.usc[s];
     double P;
     bool pass = true;
-    if (p.do_bias) {
+    if (p.do_bias && L >= 1) {                 // an empty target has no residue 1: the byte at sq[0] is a sentinel, not a row of s_eo
       const uint8_t *sq = dsq + a.slot_off[s];
       const float p1 = (float) L / (float) (L + 1);
       const float L1 = (float) ((double) (float) p.M / 8.0);
