@@ -12,6 +12,7 @@
 // Integer results are those of vit_kernel / msv_wave_kernel bit for bit (same operations in the same order); the Forward
 // score is fwd_kernel's (same summation order).
 #include "p7x_wave.hpp"
+#include "p7x_launch.hpp"
 #include "p7x_host.hpp"
 #include <algorithm>
 #include <cmath>
@@ -282,15 +283,12 @@ __global__ void __launch_bounds__(kWsBlock) cal_fwd_kernel(const ArgRef ref, con
 }
 
 // ---------------------------------------------------------------------------- host side
-static size_t cal_lds_msv(int C, int K) { return C > 32 ? (size_t) 256 : (size_t) 64 * C * K * 2; }
-static size_t cal_lds_vit(int C, int K) { return C > 128 ? (size_t) 256 : (size_t) 64 * C * (16 + (C <= 32 ? K * 2 : 0)); }
-static size_t cal_lds_fwd(int C, int K) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? K * 4 : 0)); }
-
+// (dynamic LDS: the layouts of p7x_kernels.hpp, with the K rows of the canonical residues that the kernels stage)
 template <typename Kern>
 static int cal_launch(Kern kernel, size_t lds, const ArgRef &ref, int nmodels, const uint8_t *d_stream, hipStream_t st)
 {
-  if (lds > 64 * 1024)
-    P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  const int gst = kernel_grant_lds(kernel, lds);
+  if (gst != P7X_OK) return gst;
   hipLaunchKernelGGL(kernel, dim3(kCalN / (kWsBlock / 64), (unsigned) nmodels), dim3(kWsBlock), lds, st, ref, d_stream);
   P7X_HIP(hipGetLastError());
   return P7X_OK;
@@ -359,9 +357,9 @@ static int cal_run(CalSet &set, int n, const uint8_t *d_stream)
     const int K = ha[lo].K, nm = hi - lo;
     const int st = node_tier_dispatch(ha[lo].C, "model too long for the calibration kernels", [&](auto tier) {
       constexpr int CC = decltype(tier)::value;
-      int s1 = cal_launch(cal_msv_kernel<CC>, cal_lds_msv(CC, K), ref, nm, d_stream, set.stream);
-      if (s1 == P7X_OK) s1 = cal_launch(cal_vit_kernel<CC>, cal_lds_vit(CC, K), ref, nm, d_stream, set.stream);
-      if (s1 == P7X_OK) s1 = cal_launch(cal_fwd_kernel<CC>, cal_lds_fwd(CC, K), ref, nm, d_stream, set.stream);
+      int s1 = cal_launch(cal_msv_kernel<CC>, msv_wave_lds_bytes(CC, K), ref, nm, d_stream, set.stream);
+      if (s1 == P7X_OK) s1 = cal_launch(cal_vit_kernel<CC>, vit_lds_bytes(CC, K), ref, nm, d_stream, set.stream);
+      if (s1 == P7X_OK) s1 = cal_launch(cal_fwd_kernel<CC>, fwd_lds_bytes(CC, K), ref, nm, d_stream, set.stream);
       return s1;
     });
     if (st != P7X_OK) return st;

@@ -2,8 +2,10 @@
 #include "p7x_device.hpp"
 #include <cstdlib>
 #include "p7x_kernels.hpp"
+#include "p7x_launch.hpp"
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -116,6 +118,52 @@ int get_ctx(int device, DeviceCtx **out)
   }
   *out = ctx.get();
   g_ctx[device] = std::move(ctx);
+  return P7X_OK;
+}
+
+// ---------------------------------------------------------------------------- LDS opt-in and occupancy (p7x_launch.hpp)
+namespace {
+struct KernelState { size_t granted = 0; std::map<std::pair<int, size_t>, int> per_cu; };      // per_cu by (threads, LDS bytes)
+struct LaunchInfo { std::mutex mu; std::map<std::pair<int, const void *>, KernelState> of; };   // by (device, kernel): the opt-in is per device
+LaunchInfo &launch_info() { static LaunchInfo *k = new LaunchInfo(); return *k; }               // never destroyed: launches may outlive exit()
+
+int grant_locked(KernelState &ks, const void *kernel, size_t bytes)
+{
+  if (bytes > 64 * 1024 && bytes > ks.granted) {
+    P7X_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes));
+    ks.granted = bytes;
+  }
+  return P7X_OK;
+}
+} // namespace
+
+int kernel_grant_lds_fn(const void *kernel, size_t lds_bytes)
+{
+  if (lds_bytes <= 64 * 1024) return P7X_OK;
+  int dev = 0; P7X_HIP(hipGetDevice(&dev));
+  LaunchInfo &li = launch_info();
+  std::lock_guard<std::mutex> lk(li.mu);
+  return grant_locked(li.of[{ dev, kernel }], kernel, lds_bytes);
+}
+
+int kernel_blocks_per_cu_fn(const void *kernel, int threads, size_t lds_bytes, int *per_cu, size_t grant_bytes, const char *trace)
+{
+  int dev = 0; P7X_HIP(hipGetDevice(&dev));
+  LaunchInfo &li = launch_info();
+  std::lock_guard<std::mutex> lk(li.mu);
+  KernelState &ks = li.of[{ dev, kernel }];
+  const auto it = ks.per_cu.find({ threads, lds_bytes });
+  if (it != ks.per_cu.end()) { *per_cu = it->second; return P7X_OK; }      // filled after the grant: ks.granted >= lds_bytes
+  const int st = grant_locked(ks, kernel, std::max(lds_bytes, grant_bytes));
+  if (st != P7X_OK) return st;
+  int v = 0;
+  P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, threads, lds_bytes));
+  if (trace && debug_opt(OPT_TRACE_ENVELOPE) > 0) {
+    hipFuncAttributes fa; (void) hipFuncGetAttributes(&fa, kernel);
+    std::fprintf(stderr, "[%s] occupancy %d blocks/CU of %d threads, lds %zu, regs %d, static lds %zu, maxthreads %d\n", trace, v, threads, lds_bytes,
+                 fa.numRegs, fa.sharedSizeBytes, fa.maxThreadsPerBlock);
+  }
+  *per_cu = ks.per_cu[{ threads, lds_bytes }] = std::max(v, 1);
   return P7X_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "p7x_wave.hpp"
+#include "p7x_launch.hpp"
 #include "p7x_envfwd.hpp"
 #include "p7x_choice.hpp"
 #include "p7x_host.hpp"
@@ -566,13 +567,8 @@ static int ens_walk_launch(const EnsArgs &a, hipStream_t st)
 {
   if (a.nregions <= 0) return P7X_OK;
   const size_t lds = (size_t) a.lds_bytes;
-  if (lds > 64 * 1024) {
-    static std::mutex mu; static std::map<int, size_t> granted_by_device;       // a per-device attribute of the kernel
-    int dev = 0; P7X_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    size_t &granted = granted_by_device[dev];
-    if (lds > granted) { P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ens_walk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) (128 * 1024))); granted = 128 * 1024; }
-  }
+  const int gst = kernel_grant_lds(ens_walk_kernel, lds > 64 * 1024 ? std::max<size_t>(lds, 128 * 1024) : lds);      // beyond 64 KiB: 128 KiB in one step
+  if (gst != P7X_OK) return gst;
   hipLaunchKernelGGL(ens_walk_kernel, dim3((unsigned) a.nregions), dim3(64), lds, st, a);
   P7X_HIP(hipGetLastError());
   return P7X_OK;

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "p7x_wave.hpp"
+#include "p7x_launch.hpp"
 #include "p7x_envfwd.hpp"
 #include "p7x_oaguard.hpp"
 
@@ -683,39 +684,15 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
 }
 
 // ---------------------------------------------------------------------------- host side
-// dynamic LDS of a block: the transitions (none above C = 64) and, up to C = 16, the emission rows (never in long-target mode)
-inline size_t env_lds_bytes(int C, int nrows, bool emis = true) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (emis && C <= 16 ? (size_t) nrows * 4 : 0)); }
-
-template <typename K>
-static int env_set_lds(K kernel, size_t lds_bytes)
-{
-  if (lds_bytes > 64 * 1024)
-    P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-  return P7X_OK;
-}
-
+// dynamic LDS of a block: fwd_lds_bytes (p7x_kernels.hpp), the emission rows never in long-target mode
 template <typename K>
 static int env_launch_kernel(K kernel, const ArgRun<EnvArgs> &a, size_t lds_bytes, hipStream_t st)
 {
-  const int s = env_set_lds(kernel, lds_bytes); if (s != P7X_OK) return s;
+  const int s = kernel_grant_lds(kernel, lds_bytes); if (s != P7X_OK) return s;
   int gx = 1;
   for (int i = 0; i < a.n; ++i) gx = std::max(gx, a.at(i).nblocks);
   hipLaunchKernelGGL(kernel, dim3((unsigned) gx, (unsigned) a.n), dim3((unsigned) env_waves(a.at(0).C) * 64), lds_bytes, st, a.ref());
   P7X_HIP(hipGetLastError());
-  return P7X_OK;
-}
-
-template <typename K>
-static int env_occupancy(K kernel, int kEnvBlock, size_t lds_bytes, int *per_cu)
-{
-  const int s = env_set_lds(kernel, lds_bytes); if (s != P7X_OK) return s;
-  P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, kEnvBlock, lds_bytes));
-  if (debug_opt(OPT_TRACE_ENVELOPE) > 0) {
-    hipFuncAttributes fa; (void) hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernel));
-    std::fprintf(stderr, "[env] occupancy %d blocks/CU of %d threads, lds %zu, regs %d, static lds %zu, maxthreads %d\n", *per_cu, kEnvBlock, lds_bytes,
-                 fa.numRegs, fa.sharedSizeBytes, fa.maxThreadsPerBlock);
-  }
-  if (*per_cu < 1) *per_cu = 1;
   return P7X_OK;
 }
 
@@ -735,7 +712,7 @@ template <EnvMode Mode>
 static int env_max_blocks_of(int C, int nrows, int num_cu, int *nblocks)
 {
   int per_cu = 1;
-  const int st = env_dispatch<Mode>(C, true, [&](auto kern) { return env_occupancy(kern, env_waves(C) * 64, env_lds_bytes(C, nrows), &per_cu); });
+  const int st = env_dispatch<Mode>(C, true, [&](auto kern) { return kernel_blocks_per_cu(kern, env_waves(C) * 64, fwd_lds_bytes(C, nrows), &per_cu, 0, "env"); });
   if (st == P7X_OK) *nblocks = num_cu * per_cu;
   return st;
 }
@@ -745,7 +722,7 @@ static int env_launch_of(const ArgRun<EnvArgs> &a, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C;
-  const size_t lds = env_lds_bytes(C, a.at(0).nrows, Mode != EnvMode::LongTarget);
+  const size_t lds = fwd_lds_bytes(C, a.at(0).nrows, Mode != EnvMode::LongTarget);
   return env_dispatch<Mode>(C, a.at(0).oa_guard > 0.0f, [&](auto kern) { return env_launch_kernel(kern, a, lds, st); });
 }
 

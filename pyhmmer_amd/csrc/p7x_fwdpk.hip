@@ -14,8 +14,7 @@
 // and of the D->D chain associate differently, so scores differ from fwd_kernel's in the last bits -- as fwd_kernel's do
 // from upstream's; F3 decisions inside the guard band are re-taken on the host in upstream's order either way.
 #include "p7x_wave.hpp"
-#include <map>
-#include <mutex>
+#include "p7x_launch.hpp"
 
 namespace p7x {
 
@@ -187,16 +186,16 @@ __global__ void __launch_bounds__(256) fwdg_kernel(const ArgRef ref)
 // Which (T, C) serves a model: the wave-per-target kernels' nodes-per-lane classes 1 .. 4 (M <= 256) map onto one grouped
 // instantiation each (and 5, 6 -- M <= 384 -- onto T = 32 with ten and twelve nodes per lane), so the lanes of a kernel class
 // (LaneClass::C) share it.
+// X(vitC, T, C), M <= 64 vitC = T C: the one list that fwdg_pick and fwdg_launch expand
+#define P7X_FWDG_TILES(X) X(1, 16, 4) X(2, 16, 8) X(3, 32, 6) X(4, 32, 8) X(5, 32, 10) X(6, 32, 12)
+
 bool fwdg_pick(int M, int vitC, int *T, int *C)
 {
   (void) M;
   switch (vitC) {
-    case 1: *T = 16; *C = 4; return true;      // M <= 64
-    case 2: *T = 16; *C = 8; return true;      // M <= 128
-    case 3: *T = 32; *C = 6; return true;      // M <= 192
-    case 4: *T = 32; *C = 8; return true;      // M <= 256
-    case 5: *T = 32; *C = 10; return true;     // M <= 320
-    case 6: *T = 32; *C = 12; return true;     // M <= 384
+#define P7X_FG(VC, TT, CC) case VC: *T = TT; *C = CC; return true;
+    P7X_FWDG_TILES(P7X_FG)
+#undef P7X_FG
     default: return false;
   }
 }
@@ -223,20 +222,9 @@ static int launch_fwdg(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   const size_t lds = ((size_t) 2 * T * C * 16) + (size_t) a.at(0).nrows * T * C * 4;
   auto kern = fwdg_kernel<T, C>;
-  static std::map<int, int> per_cu_by_device;
-  static std::mutex mu;
   int per_cu = 0;
-  {
-    int dev = 0; P7X_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    int &cached = per_cu_by_device[dev];
-    if (cached == 0) {
-      if (lds > 64 * 1024) P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kern, 256, lds));
-      if (cached < 1) cached = 1;
-    }
-    per_cu = cached;
-  }
+  const int pst = kernel_blocks_per_cu(kern, 256, lds, &per_cu);
+  if (pst != P7X_OK) return pst;
   constexpr int G = 64 / T;
   long want = 0;      // a group per expected target (the groups fetch their work themselves: fewer blocks only make the chains longer)
   for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nlist + 4 * G - 1) / (4 * G));
@@ -251,12 +239,9 @@ int fwdg_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
   if (a.n <= 0) return P7X_OK;
   const int T = a.at(0).C / 256, C = a.at(0).C % 256;
-  if (T == 16 && C == 4) return launch_fwdg<16, 4>(a, num_cu, st);
-  if (T == 16 && C == 8) return launch_fwdg<16, 8>(a, num_cu, st);
-  if (T == 32 && C == 6) return launch_fwdg<32, 6>(a, num_cu, st);
-  if (T == 32 && C == 8) return launch_fwdg<32, 8>(a, num_cu, st);
-  if (T == 32 && C == 10) return launch_fwdg<32, 10>(a, num_cu, st);
-  if (T == 32 && C == 12) return launch_fwdg<32, 12>(a, num_cu, st);
+#define P7X_FG(VC, TT, CC) if (T == TT && C == CC) return launch_fwdg<TT, CC>(a, num_cu, st);
+  P7X_FWDG_TILES(P7X_FG)
+#undef P7X_FG
   set_error("no grouped Forward kernel for this model length");
   return P7X_EINVAL;
 }

@@ -137,6 +137,14 @@ struct WaveSeqArgs {
   const float *fwd_xmx;     // Backward only: Forward's blocks (for the scale factors)
 };
 int vit_pick_C(int M);
+// Dynamic LDS of the wave-per-target layouts (the search, envelope / alignment and calibration kernels index LDS by them).
+// Viterbi filter: the transitions, 16 bytes per node (M > 8192: read through L2), and the emission rows up to M = 2048
+inline size_t vit_lds_bytes(int C, int nrows) { return C > 128 ? (size_t) 256 : (size_t) 64 * C * (16 + (C <= 32 ? nrows * 2 : 0)); }
+// Parsers and envelopes: the transitions, 32 bytes per node (M > 4096: read through L2), and, where <emis>, the emission rows
+// while they fit beside them (M <= 1024: the instantiations without EG)
+inline size_t fwd_lds_bytes(int C, int nrows, bool emis = true) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (emis && C <= 16 ? (size_t) nrows * 4 : 0)); }
+// MSV, one target per wavefront: the emission rows up to M = 2048
+inline size_t msv_wave_lds_bytes(int C, int nrows) { return C > 32 ? (size_t) 256 : (size_t) 64 * C * nrows * 2; }
 // every record of a run has the same C (and nrows); nlist of the host copies bounds the lists and sizes the grid
 int vit_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st);
 int fwd_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st);

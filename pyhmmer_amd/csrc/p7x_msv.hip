@@ -21,10 +21,9 @@
 //   * residues arrive as coalesced 16-byte loads from 64-sequence interleaved tiles (p7x_seqdb).
 #include <cstdlib>
 #include <iterator>
-#include <map>
-#include <mutex>
 #include "p7x_device.hpp"
 #include "p7x_kernels.hpp"
+#include "p7x_launch.hpp"
 
 namespace p7x {
 
@@ -619,32 +618,11 @@ static int launch_RK(const ArgRun<MsvArgs> &main, const ArgRun<MsvArgs> *amb, in
 {
   constexpr int BLK = msv_block_c(K);
   const size_t lds_bytes = (size_t) msv_parities_c(K) * kTabRows * msv_row_stride_c(R, K) * 4;
-  // occupancy and the LDS opt-in are per kernel instantiation: looked up once
-  struct Info { int per_cu_exact = 0, per_cu_fast = 0, per_cu_half = 0; bool ok = false; };
-  static std::map<int, Info> info_by_device;       // ... and per device (the opt-in is an attribute of the kernel ON a device)
-  static std::mutex mu;
-  Info info;
-  {
-    int dev = 0; P7X_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    Info &slot = info_by_device[dev];
-    if (!slot.ok) {
-      Info &info = slot;
-      if (lds_bytes > 64 * 1024) {
-        P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&msv_kernel<R, K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-        P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&msv_fast_kernel<R, K, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-        P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&msv_fast_kernel<R, K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-      }
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&info.per_cu_exact, msv_kernel<R, K>, BLK, lds_bytes));
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&info.per_cu_fast, msv_fast_kernel<R, K, false>, BLK, lds_bytes));
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&info.per_cu_half, msv_fast_kernel<R, K, true>, BLK, lds_bytes));
-      if (info.per_cu_exact < 1) info.per_cu_exact = 1;
-      if (info.per_cu_fast < 1) info.per_cu_fast = 1;
-      if (info.per_cu_half < 1) info.per_cu_half = 1;
-      info.ok = true;
-    }
-    info = slot;
-  }
+  int per_cu_exact = 0, per_cu_fast = 0, per_cu_half = 0;
+  int pst = kernel_blocks_per_cu(&msv_kernel<R, K>, BLK, lds_bytes, &per_cu_exact);
+  if (pst == P7X_OK) pst = kernel_blocks_per_cu(&msv_fast_kernel<R, K, false>, BLK, lds_bytes, &per_cu_fast);
+  if (pst == P7X_OK) pst = kernel_blocks_per_cu(&msv_fast_kernel<R, K, true>, BLK, lds_bytes, &per_cu_half);
+  if (pst != P7X_OK) return pst;
   if (amb_only) {                        // the fast kernel ran as part of a tier launch: only the lists of ambiguous groups are left
     hipLaunchKernelGGL((msv_kernel<R, K>), dim3(lane_grid(32, 32, amb->n), (unsigned) amb->n), dim3(BLK), lds_bytes, st, amb->ref());
     P7X_HIP(hipGetLastError());
@@ -654,14 +632,14 @@ static int launch_RK(const ArgRun<MsvArgs> &main, const ArgRun<MsvArgs> *amb, in
   long want = 1;
   for (int i = 0; i < main.n; ++i) want = std::max<long>(want, ((long) (main.at(i).ngroups - main.at(i).group_first) * K + wpb - 1) / wpb);
   if (amb == nullptr) {           // exact kernel over every group
-    const unsigned gx = lane_grid_pull(want, (long) num_cu * info.per_cu_exact, main.n, debug_opt(OPT_MSV_LANE_BLOCKS) == 0);
+    const unsigned gx = lane_grid_pull(want, (long) num_cu * per_cu_exact, main.n, debug_opt(OPT_MSV_LANE_BLOCKS) == 0);
     hipLaunchKernelGGL((msv_kernel<R, K>), dim3(gx, (unsigned) main.n), dim3(BLK), lds_bytes, st, main.ref());
     P7X_HIP(hipGetLastError());
     return P7X_OK;
   }
   // fast kernel over every group, then the exact kernel over the (normally empty) lists of ambiguous groups
   const bool half = debug_opt(OPT_MSV_F16) != 0;          // the half-float flavour unless a test asks for the integer one
-  int per_cu2 = half ? info.per_cu_half : info.per_cu_fast;
+  int per_cu2 = half ? per_cu_half : per_cu_fast;
   // A/B switch: cap the resident blocks per CU so that other kernels' wavefronts fit beside the MSV row registers
   const int cap = debug_opt(OPT_MSV_BLOCKS_PER_CU);
   if (cap > 0 && per_cu2 > cap) per_cu2 = cap;
@@ -702,29 +680,11 @@ static int launch_tier(const ArgRun<MsvArgs> &main, int num_cu, hipStream_t st)
     want = std::max<long>(want, ((long) (a.ngroups - a.group_first) * K + wpb - 1) / wpb);
   }
   const size_t lds_bytes = (size_t) msv_table_dwords(Rmax, K) * 4;
-  // occupancy by (device, LDS bytes); the LDS opt-in once per device, for the tier's largest tile
-  static std::map<std::pair<int, size_t>, int> per_cu_of;
-  static std::map<int, bool> opted;
-  static std::mutex mu;
+  // the LDS opt-in in one step, for the tier's largest tile
+  constexpr int Rtop = TIER == 0 ? 92 : (TIER == 1 ? 136 : (TIER >= 4 ? 128 : 224));
   int per_cu = 0;
-  {
-    int dev = 0; P7X_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (!opted[dev]) {
-      constexpr int Rtop = TIER == 0 ? 92 : (TIER == 1 ? 136 : (TIER >= 4 ? 128 : 224));
-      const size_t most = (size_t) msv_table_dwords(Rtop, K) * 4;
-      if (most > 64 * 1024)
-        P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&msv_tier_kernel<TIER>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) most));
-      opted[dev] = true;
-    }
-    auto it = per_cu_of.find({ dev, lds_bytes });
-    if (it == per_cu_of.end()) {
-      int v = 0;
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, msv_tier_kernel<TIER>, BLK, lds_bytes));
-      it = per_cu_of.emplace(std::make_pair(dev, lds_bytes), std::max(v, 1)).first;
-    }
-    per_cu = it->second;
-  }
+  const int pst = kernel_blocks_per_cu(&msv_tier_kernel<TIER>, BLK, lds_bytes, &per_cu, (size_t) msv_table_dwords(Rtop, K) * 4);
+  if (pst != P7X_OK) return pst;
   const unsigned gx = lane_grid_pull(want, (long) num_cu * per_cu, main.n, debug_opt(OPT_MSV_LANE_BLOCKS) == 0);
   hipLaunchKernelGGL((msv_tier_kernel<TIER>), dim3(gx, (unsigned) main.n), dim3(BLK), lds_bytes, st, main.ref());
   P7X_HIP(hipGetLastError());

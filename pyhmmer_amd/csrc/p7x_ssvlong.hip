@@ -22,9 +22,8 @@
 // cell at or above a threshold it has already reached.
 #include <climits>
 #include <cstdlib>
-#include <map>
 #include "p7x_wave.hpp"
-#include <mutex>
+#include "p7x_launch.hpp"
 
 namespace p7x {
 
@@ -339,7 +338,11 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
 }
 
 // ---------------------------------------------------------------------------- host side
-static const int kSsvR[] = { 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 20, 24, 32, 48 };      // packed registers per lane
+// packed registers per lane: the instantiations, for ssvlong_pick_R, ssvlong_plan and the dispatch
+#define P7X_SSV_R(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(14) X(16) X(20) X(24) X(32) X(48)
+#define P7X_SSV_ITEM(RR) RR,
+static const int kSsvR[] = { P7X_SSV_R(P7X_SSV_ITEM) };
+#undef P7X_SSV_ITEM
 
 int ssvlong_pick_R(int M, bool virtual_node)
 {
@@ -434,20 +437,9 @@ static int launch_ssv_quad(const SsvLongArgs &a, int num_cu, hipStream_t st, lon
 {
   const size_t lds = (size_t) 2 * 4 * ((R + 3) / 4) * 64 * 16;
   auto kern = ssvlong_quad_kernel<R, PAIR, H, BIN, BOUT>;
-  static std::map<int, int> per_cu_by_device;       // the LDS opt-in is a per-device attribute of the kernel: looked up once per device
-  static std::mutex mu;
   int per_cu = 0;
-  {
-    int dev = 0; P7X_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    int &cached = per_cu_by_device[dev];
-    if (cached == 0) {
-      if (lds > 64 * 1024) P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kern, 256, lds));
-      if (cached < 1) cached = 1;
-    }
-    per_cu = cached;
-  }
+  const int pst = kernel_blocks_per_cu(kern, 256, lds, &per_cu);
+  if (pst != P7X_OK) return pst;
   if (cap_waves) { *cap_waves = (long long) num_cu * per_cu * 4; return P7X_OK; }
   long long grid = std::min<long long>((a.nchunks + 3) / 4, (long long) num_cu * per_cu);
   if (grid < 1) grid = 1;
@@ -474,8 +466,7 @@ static int ssvlong_quad_dispatch(int R, bool pair, bool half, bool bin, bool bou
 {
 #define P7X_SQ(RR) case RR: return ssvlong_flavour_dispatch<RR>(pair, half, bin, bout, a, num_cu, st, cap_waves);
   switch (R) {
-    P7X_SQ(2) P7X_SQ(3) P7X_SQ(4) P7X_SQ(5) P7X_SQ(6) P7X_SQ(7) P7X_SQ(8) P7X_SQ(9) P7X_SQ(10) P7X_SQ(11) P7X_SQ(12) P7X_SQ(14) P7X_SQ(16)
-    P7X_SQ(20) P7X_SQ(24) P7X_SQ(32) P7X_SQ(48)
+    P7X_SSV_R(P7X_SQ)
     default: set_error(model_too_long("model too long for the long-target SSV kernel")); return P7X_EINVAL;
   }
 #undef P7X_SQ

@@ -13,6 +13,7 @@
 // Integer semantics follow upstream impl_sse/vitfilter.c exactly (signed saturating 16-bit adds via
 // v_add_i16 clamp); float semantics follow impl_sse/fwdback.c up to the association order of sums.
 #include "p7x_wave.hpp"
+#include "p7x_launch.hpp"
 
 namespace p7x {
 
@@ -667,29 +668,6 @@ int vit_pick_C(int M)
   return -1;
 }
 
-// occupancy and the LDS opt-in of one kernel instantiation, looked up once
-struct KernelInfo { std::mutex mu; std::map<std::pair<int, const void *>, int> per_cu; };      // by (device, kernel): the opt-in is per device
-static KernelInfo &kernel_info() { static KernelInfo *k = new KernelInfo(); return *k; }
-template <typename K>
-static int blocks_per_cu(K kernel, size_t lds_bytes, int *out)
-{
-  KernelInfo &ki = kernel_info();
-  std::lock_guard<std::mutex> lk(ki.mu);
-  int dev = 0; P7X_HIP(hipGetDevice(&dev));
-  const void *fn = reinterpret_cast<const void *>(kernel);
-  const std::pair<int, const void *> key(dev, fn);
-  auto it = ki.per_cu.find(key);
-  if (it != ki.per_cu.end()) { *out = it->second; return P7X_OK; }
-  if (lds_bytes > 64 * 1024)
-    P7X_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-  int per_cu = 0;
-  P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWsBlock, lds_bytes));
-  if (per_cu < 1) per_cu = 1;
-  ki.per_cu[key] = per_cu;
-  *out = per_cu;
-  return P7X_OK;
-}
-
 template <typename K>
 static int launch_ws(K kernel, const ArgRun<WaveSeqArgs> &a, size_t lds_bytes, int num_cu, hipStream_t st)
 {
@@ -697,18 +675,12 @@ static int launch_ws(K kernel, const ArgRun<WaveSeqArgs> &a, size_t lds_bytes, i
   for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nlist + 3) / 4);      // nlist bounds the device-side count
   if (want <= 0) return P7X_OK;
   int per_cu = 0;
-  const int pst = blocks_per_cu(kernel, lds_bytes, &per_cu);
+  const int pst = kernel_blocks_per_cu(kernel, kWsBlock, lds_bytes, &per_cu);
   if (pst != P7X_OK) return pst;
   hipLaunchKernelGGL(kernel, dim3(lane_grid(want, (long) num_cu * per_cu, a.n), (unsigned) a.n), dim3(kWsBlock), lds_bytes, st, a.ref());
   P7X_HIP(hipGetLastError());
   return P7X_OK;
 }
-
-// Dynamic LDS of the Viterbi filter: the transitions, 16 bytes per node (M > 8192: read through L2), and the emission rows up to M = 2048
-static size_t vit_lds_bytes(int C, int nrows) { return C > 128 ? (size_t) 256 : (size_t) 64 * C * (16 + (C <= 32 ? nrows * 2 : 0)); }
-// Dynamic LDS of the parsers: the transitions, 32 bytes per node (M > 4096: read through L2), and the emission rows while
-// they fit beside them (M <= 1024: the instantiations without EG)
-static size_t fwd_lds_bytes(int C, int nrows) { return C > 64 ? (size_t) 256 : (size_t) 64 * C * (32 + (C <= 16 ? nrows * 4 : 0)); }
 
 int vit_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 {
@@ -731,7 +703,8 @@ int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st)
     for (int i = 0; i < a.n; ++i) wantpk = std::max<long>(wantpk, ((long) a.at(i).nslots + kPkWaves - 1) / kPkWaves);
     auto gopk = [&](auto kernel) -> int {
       const size_t lds = (size_t) 64 * C * nrows * 2;
-      P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+      const int gst = kernel_grant_lds(kernel, lds);
+      if (gst != P7X_OK) return gst;
       hipLaunchKernelGGL(kernel, dim3(lane_grid(wantpk, (long) num_cu, a.n), (unsigned) a.n), dim3(kPkWaves * 64), lds, st, a.ref());
       P7X_HIP(hipGetLastError());
       return P7X_OK;
@@ -746,9 +719,9 @@ int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st)
     }
   }
   auto go = [&](auto kernel) -> int {
-    const size_t lds = C > 32 ? (size_t) 256 : (size_t) 64 * C * nrows * 2;
+    const size_t lds = msv_wave_lds_bytes(C, nrows);
     int per_cu = 0;
-    const int pst = blocks_per_cu(kernel, lds, &per_cu);
+    const int pst = kernel_blocks_per_cu(kernel, kWsBlock, lds, &per_cu);
     if (pst != P7X_OK) return pst;
     hipLaunchKernelGGL(kernel, dim3(lane_grid(want, (long) num_cu * per_cu, a.n), (unsigned) a.n), dim3(kWsBlock), lds, st, a.ref());
     P7X_HIP(hipGetLastError());

@@ -18,9 +18,8 @@
 //     is evaluated in full: two packed ops per register walk every stripe, the carry into the next stripe is a
 //     stripe shift, passes repeat until nothing improves (two on average).
 // Results are bit-identical to p7x_vitfwd.hip::vit_kernel and to the oracle (tests/test_gpu_filters.py).
-#include <map>
 #include "p7x_wave.hpp"
-#include <mutex>
+#include "p7x_launch.hpp"
 
 namespace p7x {
 
@@ -274,17 +273,20 @@ __global__ void __launch_bounds__(64 * vitpk_waves(T, P)) vitpk_kernel(const Arg
 }
 
 // ---------------------------------------------------------------------------- host side
+// The instantiations, X(T, P), by increasing model length 2 T P: vitpk_pick takes the first that holds the model,
+// vitpk_launch dispatches on the same list.
+#define P7X_VITPK_TILES(X) \
+  X(8, 2) X(8, 4) X(8, 6) X(8, 8) X(8, 10) X(8, 12) X(8, 14) X(8, 15) X(8, 16) X(8, 17) X(8, 18) X(8, 19) X(8, 20) \
+  X(16, 11) X(16, 12) X(16, 13) X(16, 14) X(16, 15) X(16, 16) X(16, 17) X(16, 18) X(16, 19) X(16, 20) \
+  X(32, 11) X(32, 12) X(32, 13) X(32, 14) X(32, 15) X(32, 16) X(32, 17) X(32, 18) X(32, 19) X(32, 20) \
+  X(64, 11) X(64, 12) X(64, 13) X(64, 14) X(64, 15) X(64, 16)
+
 bool vitpk_pick(int M, int *T, int *P)
 {
-  static const int p8[] = { 2, 4, 6, 8, 10, 12, 14, 15, 16, 17, 18, 19, 20 };
-  static const int p16[] = { 11, 12, 13, 14, 15, 16, 17, 18, 19, 20 };
-  for (int p : p8) if (M <= 8 * 2 * p) { *T = 8; *P = p; return true; }
-  for (int p : p16) if (M <= 16 * 2 * p) { *T = 16; *P = p; return true; }
-  if (debug_opt(OPT_VIT_WIDE) == 0) return false;       // A/B and test seam: models beyond 640 nodes stay with vit_kernel
-  static const int p32[] = { 11, 12, 13, 14, 15, 16, 17, 18, 19, 20 };
-  static const int p64[] = { 11, 12, 13, 14, 15, 16 };
-  for (int p : p32) if (M <= 32 * 2 * p) { *T = 32; *P = p; return true; }
-  for (int p : p64) if (M <= 64 * 2 * p) { *T = 64; *P = p; return true; }
+  const bool wide = debug_opt(OPT_VIT_WIDE) != 0;       // 0: A/B and test seam: models beyond 640 nodes stay with vit_kernel
+#define P7X_PK(TT, PP) if (M <= 2 * TT * PP) { if (TT >= 32 && !wide) return false; *T = TT; *P = PP; return true; }
+  P7X_VITPK_TILES(P7X_PK)
+#undef P7X_PK
   return false;
 }
 
@@ -319,20 +321,9 @@ static int launch_pk(const ArgRun<VitPkArgs> &a, int num_cu, hipStream_t st)
   const size_t lds = ((size_t) 2 * P * T + (size_t) a.at(0).nrows * vitpk_rowq(T, P)) * 16;
   auto kern = vitpk_kernel<T, P>;
   constexpr int NW = vitpk_waves(T, P), NT = 64 * NW;
-  static std::map<int, int> per_cu_by_device;       // the LDS opt-in is a per-device attribute of the kernel: looked up once per device
-  static std::mutex mu;
   int per_cu = 0;
-  {
-    int dev = 0; P7X_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    int &cached = per_cu_by_device[dev];
-    if (cached == 0) {
-      if (lds > 64 * 1024) P7X_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      P7X_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kern, NT, lds));
-      if (cached < 1) cached = 1;
-    }
-    per_cu = cached;
-  }
+  const int pst = kernel_blocks_per_cu(kern, NT, lds, &per_cu);
+  if (pst != P7X_OK) return pst;
   long want = 0;
   for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nlist + NW * (64 / T) - 1) / (NW * (64 / T)));   // nlist bounds the list
   if (want <= 0) return P7X_OK;
@@ -345,13 +336,7 @@ int vitpk_launch(int T, int P, const ArgRun<VitPkArgs> &a, int num_cu, hipStream
 {
   if (a.n <= 0) return P7X_OK;
 #define P7X_PK(TT, PP) if (T == TT && P == PP) return launch_pk<TT, PP>(a, num_cu, st);
-  P7X_PK(8, 2) P7X_PK(8, 4) P7X_PK(8, 6) P7X_PK(8, 8) P7X_PK(8, 10) P7X_PK(8, 12) P7X_PK(8, 14) P7X_PK(8, 15) P7X_PK(8, 16)
-  P7X_PK(8, 17) P7X_PK(8, 18) P7X_PK(8, 19) P7X_PK(8, 20)
-  P7X_PK(16, 11) P7X_PK(16, 12) P7X_PK(16, 13) P7X_PK(16, 14) P7X_PK(16, 15) P7X_PK(16, 16) P7X_PK(16, 17) P7X_PK(16, 18)
-  P7X_PK(16, 19) P7X_PK(16, 20)
-  P7X_PK(32, 11) P7X_PK(32, 12) P7X_PK(32, 13) P7X_PK(32, 14) P7X_PK(32, 15) P7X_PK(32, 16) P7X_PK(32, 17) P7X_PK(32, 18)
-  P7X_PK(32, 19) P7X_PK(32, 20)
-  P7X_PK(64, 11) P7X_PK(64, 12) P7X_PK(64, 13) P7X_PK(64, 14) P7X_PK(64, 15) P7X_PK(64, 16)
+  P7X_VITPK_TILES(P7X_PK)
 #undef P7X_PK
   set_error("no packed Viterbi kernel for this model length");
   return P7X_EINVAL;

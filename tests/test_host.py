@@ -790,3 +790,35 @@ def test_optimized_profile_cutoffs_and_evalue_parameters_are_read_only():
     assert om.cutoffs.gathering == hmm.cutoffs.gathering and om.evalue_parameters == hmm.evalue_parameters
     hmm.cutoffs.gathering = (1.0, 2.0)
     assert hmm.cutoffs.gathering == (1.0, 2.0)
+
+
+# vitpk_pick's instantiations as they stood before one list served the pick and the dispatch: register pairs per lane P by
+# lanes per target T; T lanes with P pairs hold 2 T P nodes
+_PK_PAIRS = {8: (2, 4, 6, 8, 10, 12, 14, 15, 16, 17, 18, 19, 20), 16: tuple(range(11, 21)), 32: tuple(range(11, 21)), 64: tuple(range(11, 17))}
+
+
+def _packed_tile(M, wide):
+    for T in (8, 16) + ((32, 64) if wide else ()):
+        for P in _PK_PAIRS[T]:
+            if M <= 2 * T * P:
+                return T, P
+    return None
+
+
+@pytest.mark.parametrize("wide", [1, 0])
+def test_packed_viterbi_tile_of_every_model_length(libp7x, wide):
+    """(T, P) that a profile's device image is laid out for (p7x_devimage.hip asks p7x::vitpk_pick, a host function that the
+    library exports under its C++ name; the image itself is only built on a device), M = 1 .. 2,048 and beyond, with option
+    "vit_wide" on and off."""
+    pick = libp7x["_ZN3p7x10vitpk_pickEiPiS0_"]
+    pick.restype, pick.argtypes = C.c_bool, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    assert _packed_tile(640, 0) == (16, 20) and _packed_tile(641, 0) is None and _packed_tile(641, 1) == (32, 11)
+    assert _packed_tile(2048, 1) == (64, 16) and _packed_tile(2049, 1) is None
+    _lib.set_debug_option("vit_wide", wide)
+    try:
+        for M in range(1, 2100):
+            T, P = C.c_int(0), C.c_int(0)
+            got = (T.value, P.value) if pick(M, C.byref(T), C.byref(P)) else None
+            assert got == _packed_tile(M, wide), (M, wide, got)
+    finally:
+        _lib.set_debug_option("vit_wide", -1)
