@@ -9,9 +9,10 @@
 // samples, and only the emission rows of the canonical residues are staged in LDS (a random sequence holds nothing else).
 // blockIdx.y is the model; the models of a launch share their tier of nodes per lane (P7X_NODE_TIERS).  The three stages
 // are three launches per tier on one stream; the host waits once, for the copy of the raw results, and does the fits.
-// Integer results are those of vit_kernel / msv_wave_kernel bit for bit (same operations in the same order); the Forward
-// score is fwd_kernel's (same summation order).
-#include "p7x_wave.hpp"
+// The rows are the shared ones of p7x_waverows.hpp -- msv_wave_kernel's (one reduction per row), vit_kernel's and
+// fwd_kernel's run the same bodies -- so a kernel here is its staging with K rows, its sample, the constant-length row loop
+// and one store.
+#include "p7x_waverows.hpp"
 #include "p7x_launch.hpp"
 #include "p7x_host.hpp"
 #include <algorithm>
@@ -42,244 +43,90 @@ struct CalArgs {
 __device__ __forceinline__ int cal_sample() { return rfl((int) (blockIdx.x * (kWsBlock / 64) + (threadIdx.x >> 6))); }
 
 // ======================================================================================= MSV
-// Row body: the twin of msv_wave_kernel's kBlk == 1 path (p7x_vitfwd.hip).  A fix there belongs here too;
-// tests/test_gpu_calibrate.py::test_raw_scores_against_the_oracle_and_the_cascade_kernels ties the two bit for bit.
 template <int C>
 __global__ void __launch_bounds__(kWsBlock) cal_msv_kernel(const ArgRef ref, const uint8_t *__restrict__ stream)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int Mpad = 64 * C;
+  constexpr int Mpad = 64 * C, L = kCalLmsv;
   constexpr bool EG = C > 32;         // M > 2048: the table is read where it lies (L2)
   const CalArgs a = load_args<CalArgs>(ref);
-  const short *em = EG ? reinterpret_cast<const short *>(a.msv_emis) : reinterpret_cast<const short *>(smem);
-  if constexpr (!EG) {
-    const uint4 *ge = reinterpret_cast<const uint4 *>(a.msv_emis);
-    uint4 *le = reinterpret_cast<uint4 *>(smem);
-    for (int i = threadIdx.x; i < a.K * Mpad / 8; i += kWsBlock) le[i] = ge[i];
-  }
+  if constexpr (!EG) stage_lds(smem, a.msv_emis, a.K * Mpad / 8);
   __syncthreads();
   const int lane = threadIdx.x & 63;
+  const short *em = EG ? reinterpret_cast<const short *>(a.msv_emis) : reinterpret_cast<const short *>(smem);
   const int s = cal_sample();
-  const uint8_t *sq = stream + (size_t) s * kCalLmsv;
-  constexpr int L = kCalLmsv;
+  const uint8_t *sq = stream + (size_t) s * L;
   int mm[C];
-#pragma unroll unroll_c(C)
-  for (int c = 0; c < C; ++c) mm[c] = 0;
-  int xJ = 0, xEmax = 0;
-  int xB = max(a.base_b - a.tjbm, 0);
+  MsvSpecials m;
+  msv_init(mm, m, a.base_b, a.tjbm);
   for (int i0 = 0; i0 < L; i0 += 64) {
     const int nrow = min(64, L - i0);
     const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
-    for (int r = 0; r < nrow; ++r) {
-      const int x = __builtin_amdgcn_readlane((int) resid, r);
-      const short *er = em + x * Mpad + lane;
-      int mp = dpp_shr1(mm[C - 1], 0);
-      int rowmax = kNegPad;
-#pragma unroll unroll_c(C)
-      for (int c = 0; c < C; ++c) {
-        const int sv = max(mp, xB) + (int) er[c * 64];
-        mp = mm[c];
-        mm[c] = sv;
-        rowmax = max(rowmax, sv);
-      }
-      const int xE = wave_max_i32(rowmax);
-      xEmax = max(xEmax, xE);
-      xJ = max(xJ, xE - a.tec_b);
-      xB = max(max(a.base_b, xJ) - a.tjbm, 0);
-    }
+    for (int r = 0; r < nrow; ++r) msv_step(mm, m, em + __builtin_amdgcn_readlane((int) resid, r) * Mpad + lane, a.base_b, a.tec_b, a.tjbm);
   }
-  if (lane == 0) a.out[s] = (xEmax >= 255 - a.bias_b) ? -1 : xJ;
+  if (lane == 0) a.out[s] = m.score(a.bias_b);
 }
 
 // ======================================================================================= Viterbi filter
-// Row body: the twin of vit_kernel (p7x_vitfwd.hip) without its long-target branch; tied to it bit for bit by the same test.
 template <int C>
 __global__ void __launch_bounds__(kWsBlock) cal_vit_kernel(const ArgRef ref, const uint8_t *__restrict__ stream)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int Mpad = 64 * C;
+  constexpr int Mpad = 64 * C, L = kCalLvit;
   constexpr bool EG = C > 32;         // M > 2048: only the transitions are staged
   constexpr bool TG = C > 128;        // M > 8192: the transitions are read through L2 as well (as vit_kernel)
   static_assert(!TG || EG, "transitions through L2 only where the emissions are");
   const CalArgs a = load_args<CalArgs>(ref);
-  const uint4 *tr = TG ? reinterpret_cast<const uint4 *>(a.vit_trans) : reinterpret_cast<const uint4 *>(smem);      // [Mpad]
-  const short *em = EG ? reinterpret_cast<const short *>(a.vit_emis) : reinterpret_cast<const short *>(smem + (size_t) Mpad * 16);
-  {
-    if constexpr (!TG) {
-      const uint4 *gt = reinterpret_cast<const uint4 *>(a.vit_trans);
-      uint4 *lt = reinterpret_cast<uint4 *>(smem);
-      for (int i = threadIdx.x; i < Mpad; i += kWsBlock) lt[i] = gt[i];
-    }
-    if constexpr (!EG) {
-      const uint4 *ge = reinterpret_cast<const uint4 *>(a.vit_emis);
-      uint4 *le = reinterpret_cast<uint4 *>(smem + (size_t) Mpad * 16);
-      for (int i = threadIdx.x; i < a.K * Mpad / 8; i += kWsBlock) le[i] = ge[i];
-    }
-  }
+  if constexpr (!TG) stage_lds(smem, a.vit_trans, Mpad);
+  if constexpr (!EG) stage_lds(smem + (size_t) Mpad * 16, a.vit_emis, a.K * Mpad / 8);
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const short NEG = (short) -32768;
+  const uint4 *tr = TG ? reinterpret_cast<const uint4 *>(a.vit_trans) : reinterpret_cast<const uint4 *>(smem);      // [Mpad]
+  const short *em = EG ? reinterpret_cast<const short *>(a.vit_emis) : reinterpret_cast<const short *>(smem + (size_t) Mpad * 16);
   const int s = cal_sample();
-  const uint8_t *sq = stream + kCalOffVit + (size_t) s * kCalLvit;
-  constexpr int L = kCalLvit;
-  const int xwm = a.xwm;
-
+  const uint8_t *sq = stream + kCalOffVit + (size_t) s * L;
   short mm[C], im[C], dm[C], tdd[C];
-#pragma unroll unroll_c(C)
-  for (int c = 0; c < C; ++c) { mm[c] = im[c] = dm[c] = NEG; tdd[c] = NEG; }
-  int xN = a.base_w, xB = xN + xwm, xJ = -32768, xC = -32768;
-  bool overflow = false;
-  for (int i0 = 0; i0 < L && !overflow; i0 += 64) {
+  ViterbiSpecials v;
+  vit_init(mm, im, dm, tdd, v, a.base_w, a.xwm);
+  for (int i0 = 0; i0 < L && !v.overflow; i0 += 64) {
     const int nrow = min(64, L - i0);
     const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
-    for (int r = 0; r < nrow && !overflow; ++r) {
-      const int x = __builtin_amdgcn_readlane((int) resid, r);
-      const short *er = em + x * Mpad + lane;
-      const short xBs = (short) xB;
-      short mp = (short) dpp_shr1(mm[C - 1], NEG);
-      short ip = (short) dpp_shr1(im[C - 1], NEG);
-      short dp = (short) dpp_shr1(dm[C - 1], NEG);
-      short rowmax = NEG, dmax = NEG, dcarry = NEG;
-#pragma unroll unroll_c(C)
-      for (int c = 0; c < C; ++c) {
-        const uint4 t = tr[c * 64 + lane];
-        short sv = adds16(xBs, lo16(t.x));
-        sv = max16(sv, adds16(mp, hi16(t.x)));
-        sv = max16(sv, adds16(ip, lo16(t.y)));
-        sv = max16(sv, adds16(dp, hi16(t.y)));
-        sv = adds16(sv, er[c * 64]);
-        rowmax = max16(rowmax, sv);
-        mp = mm[c]; ip = im[c]; dp = dm[c];
-        im[c] = max16(adds16(mp, hi16(t.z)), adds16(ip, lo16(t.w)));
-        mm[c] = sv;
-        dm[c] = dcarry;                       // M(i,k-1) -> D(i,k); node c = 0 is patched below
-        dcarry = adds16(sv, lo16(t.z));
-        dmax = max16(dmax, dcarry);
-        tdd[c] = hi16(t.w);
-      }
-      dm[0] = (short) dpp_shr1(dcarry, NEG);
-
-      const int xE = wave_max_i32((int) rowmax);
-      if (xE >= 32767) overflow = true;
-      xC = max(xC, xE + a.xw_e);
-      xJ = max(xJ, xE + a.xw_e);
-      xB = max(xJ + xwm, xN + xwm);
-
-      const int Dmax = wave_max_i32((int) dmax);
-      if (Dmax + a.ddbound > xB) {            // lazy F, then the chunk carries relaxed to their fixed point
-#pragma unroll unroll_c(C)
-        for (int c = 1; c < C; ++c) dm[c] = max16(dm[c], adds16(dm[c - 1], tdd[c - 1]));
-        for (int pass = 0; pass < 64; ++pass) {
-          const short ddout = adds16(dm[C - 1], tdd[C - 1]);
-          const short cand = (short) dpp_shr1(ddout, NEG);
-          const int improved = wave_max_i32((cand > dm[0]) ? 1 : 0);
-          if (improved == 0) break;
-          dm[0] = max16(dm[0], cand);
-#pragma unroll unroll_c(C)
-          for (int c = 1; c < C; ++c) dm[c] = max16(dm[c], adds16(dm[c - 1], tdd[c - 1]));
-        }
-      }
+    for (int r = 0; r < nrow && !v.overflow; ++r) {
+      const int xE = vit_cells(mm, im, dm, tdd, v, tr, em + __builtin_amdgcn_readlane((int) resid, r) * Mpad + lane, lane);
+      vit_finish(dm, tdd, v, xE, a.xw_e, a.xwm, a.ddbound);
     }
   }
-  if (lane == 0) a.out[kCalN + s] = overflow ? 32767 : xC;
+  if (lane == 0) a.out[kCalN + s] = v.score();
 }
 
 // ======================================================================================= Forward parser
-// Row body: the twin of fwd_kernel (p7x_vitfwd.hip) without the stored rows; the same test requires equal scores, bit for bit.
 template <int C>
 __global__ void __launch_bounds__(kWsBlock) cal_fwd_kernel(const ArgRef ref, const uint8_t *__restrict__ stream)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int Mpad = 64 * C;
+  constexpr int Mpad = 64 * C, L = kCalLfwd;
   constexpr bool EG = C > 16;         // M > 1024: the emission rows are read through L2
   constexpr bool TG = C > 64;         // M > 4096: the transitions too
   const CalArgs a = load_args<CalArgs>(ref);
-  const float4 *tr = TG ? reinterpret_cast<const float4 *>(a.fwd_trans) : reinterpret_cast<const float4 *>(smem);      // [2 Mpad]
+  const TransView<false> tr{ TG ? reinterpret_cast<const float4 *>(a.fwd_trans) : reinterpret_cast<const float4 *>(smem), 0 };      // [2 Mpad]
   const float *em = EG ? reinterpret_cast<const float *>(a.fwd_emis) : reinterpret_cast<const float *>(smem + (size_t) Mpad * 32);
-  {
-    if constexpr (!TG) {
-      const float4 *gt = reinterpret_cast<const float4 *>(a.fwd_trans);
-      float4 *lt = reinterpret_cast<float4 *>(smem);
-      for (int i = threadIdx.x; i < 2 * Mpad; i += kWsBlock) lt[i] = gt[i];
-    }
-    if constexpr (!EG) {
-      const float4 *ge = reinterpret_cast<const float4 *>(a.fwd_emis);
-      float4 *le = reinterpret_cast<float4 *>(smem + (size_t) Mpad * 32);
-      for (int i = threadIdx.x; i < a.K * Mpad / 4; i += kWsBlock) le[i] = ge[i];
-    }
-  }
+  if constexpr (!TG) stage_lds(smem, a.fwd_trans, 2 * Mpad);
+  if constexpr (!EG) stage_lds(smem + (size_t) Mpad * 32, a.fwd_emis, a.K * Mpad / 4);
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const int s = cal_sample();
-  const uint8_t *sq = stream + kCalOffFwd + (size_t) s * kCalLfwd;
-  constexpr int L = kCalLfwd;
+  const uint8_t *sq = stream + kCalOffFwd + (size_t) s * L;
   const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f), ploop = 1.0f - pmove;
-
   float mm[C], im[C], dm[C];
-#pragma unroll unroll_c(C)
-  for (int c = 0; c < C; ++c) mm[c] = im[c] = dm[c] = 0.0f;
-  float ddprod = 1.0f;                // product of this lane's D->D probabilities: the multiplier of an incoming D carry
-#pragma unroll unroll_c(C)
-  for (int c = 0; c < C; ++c) ddprod *= tr[2 * (c * 64 + lane) + 1].w;
-
-  float xN = 1.0f, xB = pmove, xJ = 0.0f, xC = 0.0f, xE = 0.0f, totscale = 0.0f;
+  ForwardRow<C, unroll_c(C), ForwardRefs<C>> f{{mm, im, dm}};
+  f.init(tr, lane, pmove);
   for (int i0 = 0; i0 < L; i0 += 64) {
     const int nrow = min(64, L - i0);
     const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
-    for (int r = 0; r < nrow; ++r) {
-      const int x = __builtin_amdgcn_readlane((int) resid, r);
-      const float *er = em + x * Mpad + lane;
-      float mp = dpp_shr1f(mm[C - 1], 0.0f), ip = dpp_shr1f(im[C - 1], 0.0f), dp = dpp_shr1f(dm[C - 1], 0.0f);
-      float esum = 0.0f, dcarry = 0.0f;
-      float tdd[C], tmd[C];
-#pragma unroll unroll_c(C)
-      for (int c = 0; c < C; ++c) {
-        const F8 t = load_f8(tr, c * 64 + lane);
-        float sv = xB * t.bm;
-        sv = sv + mp * t.mm;
-        sv = sv + ip * t.im;
-        sv = sv + dp * t.dm;
-        sv = sv * er[c * 64];
-        esum = esum + sv;
-        mp = mm[c]; ip = im[c]; dp = dm[c];
-        im[c] = mp * t.mi + ip * t.ii;
-        mm[c] = sv;
-        tdd[c] = t.dd; tmd[c] = t.md;
-      }
-      // D(i,k) = M(i,k-1) tMD(k-1) + D(i,k-1) tDD(k-1): serial inside the lane, affine scan across the lanes
-      float A = 0.0f;
-#pragma unroll unroll_c(C)
-      for (int c = 0; c < C; ++c) { dm[c] = A; A = mm[c] * tmd[c] + A * tdd[c]; }
-      float sa = A, sp = ddprod;
-      affine_scan_up(sa, sp);
-      dcarry = dpp_shr1f(sa, 0.0f);
-      {
-        float w = dcarry;
-#pragma unroll unroll_c(C)
-        for (int c = 0; c < C; ++c) { dm[c] = dm[c] + w; esum = esum + dm[c]; w = w * tdd[c]; }
-      }
-      xE = wave_sum_f32(esum);
-      xN = xN * ploop;
-      xC = (xC * ploop) + (xE * a.xf_e_move);
-      xJ = (xJ * ploop) + (xE * a.xf_e_loop);
-      xB = (xJ * pmove) + (xN * pmove);
-      if (xE > 1.0e4f) {
-        xN = xN / xE; xC = xC / xE; xJ = xJ / xE; xB = xB / xE;
-        const float inv = (float) (1.0 / (double) xE);
-#pragma unroll unroll_c(C)
-        for (int c = 0; c < C; ++c) { mm[c] *= inv; dm[c] *= inv; im[c] *= inv; }
-        totscale = (float) ((double) totscale + log((double) xE));
-        xE = 1.0f;
-      }
-    }
+    for (int r = 0; r < nrow; ++r)
+      f.row(tr, em, Mpad, lane, __builtin_amdgcn_readlane((int) resid, r), pmove, ploop, a.xf_e_move, a.xf_e_loop);
   }
-  if (lane == 0) {
-    float sc;
-    if (xC != xC) sc = __builtin_nanf("");
-    else if (xC == 0.0f || __builtin_isinf(xC)) sc = __builtin_inff();
-    else sc = (float) ((double) totscale + log((double) (xC * pmove)));
-    a.out[2 * kCalN + s] = __builtin_bit_cast(int32_t, sc);
-  }
+  if (lane == 0) a.out[2 * kCalN + s] = __builtin_bit_cast(int32_t, forward_score(f.xC, f.totscale, pmove, L));
 }
 
 // ---------------------------------------------------------------------------- host side

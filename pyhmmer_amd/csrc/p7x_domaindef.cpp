@@ -156,7 +156,7 @@ template <bool FULL> static inline int row_at(int r) { return FULL ? r : (r & 1)
 
 // dsq is 1-indexed over the envelope: residues dsq[1..L].
 // D(i,k) = M(i,k-1) tMD(k-1) + D(i,k-1) tDD(k-1), k = 1..M, given the finished M row; returns xE = sum_k M(i,k) + D(i,k).
-// EnvForward<C>::row (p7x_envelope.hip) operation for operation: every lane runs its own chain from a zero carry, the
+// ForwardRow<C, U>::row (p7x_waverows.hpp) operation for operation: every lane runs its own chain from a zero carry, the
 // lanes' affine maps are composed by the scan, the carry enters a lane's nodes through successive products, and the row
 // sum takes a lane's match cells, then its delete cells, then the reduction tree.
 static float dchain_forward(const Model &om, const float *__restrict mc, float *__restrict dc)

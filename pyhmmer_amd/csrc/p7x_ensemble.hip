@@ -7,7 +7,7 @@
 // (impl_sse/null2.c p7_Null2_ByTrace).  A region is therefore one serial walk of ~200 x (region length + alignment
 // length) dependent choices.  Two kernels:
 //
-//   ens_forward_kernel<C>   one wavefront per region: p7_Forward, multihit, with the row in registers (EnvForward<C>, the
+//   ens_forward_kernel<C>   one wavefront per region: p7_Forward, multihit, with the row in registers (ForwardRow<C, U>, the
 //                           envelope kernel's recurrence: same operations, same order, same bits as the host twin's
 //                           forward_full) -- and, cell by cell while the values are at hand, the INTEGER thresholds of
 //                           every choice a traceback can face there (p7x_choice.hpp): all floating-point work of the
@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include "p7x_wave.hpp"
 #include "p7x_launch.hpp"
-#include "p7x_envfwd.hpp"
+#include "p7x_waverows.hpp"
 #include "p7x_choice.hpp"
 #include "p7x_host.hpp"
 #include <algorithm>
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(64) ens_forward_kernel(const EnsArgs a, const 
   const float pmove = (2.0f + nj) / ((float) reg.L + 2.0f + nj), ploop = 1.0f - pmove;
   const float xf_e_move = 0.5f, xf_e_loop = 0.5f;
 
-  EnvForward<C> f;
+  ForwardRow<C, unroll_env(C)> f;
   f.init(tr, lane, pmove);
   // leaving transitions of the node before this lane's first one (the delete cell's choice looks one node back)
   float p_md0, p_dd0;

@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include "p7x_wave.hpp"
 #include "p7x_launch.hpp"
-#include "p7x_envfwd.hpp"
+#include "p7x_waverows.hpp"
 #include "p7x_oaguard.hpp"
 
 namespace p7x {
@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
     // ------------------------------------------------------------------ 1. Forward (score and scale factors)
     float envsc;
     {
-      EnvForward<C> f;
+      ForwardRow<C, unroll_env(C)> f;
       f.init(tr, lane, pmove);
       if (lane == 0) { fx[0] = 0.0f; fx[1] = 1.0f; fx[2] = 0.0f; fx[3] = f.xB; fx[4] = 0.0f; fx[5] = 1.0f; }
       for (int i0 = 0; i0 < Ld; i0 += 64) {
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
     }
     if constexpr (LT) {            // Forward with the profile's own odds: the envelope's score proper.  (Run row by row next to
                                    // the first recurrence it was slower: 66 against 58 ms for the benchmark's two rounds.)
-      EnvForward<C> g;
+      ForwardRow<C, unroll_env(C)> g;
       g.init(tr, lane, pmove);
       for (int i0 = 0; i0 < Ld; i0 += 64) {
         const int nrow = min(64, Ld - i0);
@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(env_waves(C) * 64, env_waves(C) / 4) env_kerne
 #pragma unroll unroll_env(C)
         for (int c = 0; c < C; ++c) { c2[c] = rbm[c * 64]; d[c] = rbi[c * 64]; }      // every lane loads (its own columns: valid
       };                                                                                 // memory); dead lanes are zeroed at the use
-      EnvForward<C> f;                 // Forward again, row by row, next to the decoding
+      ForwardRow<C, unroll_env(C)> f;                 // Forward again, row by row, next to the decoding
       f.init(tr, lane, pmove);
       auto fetch_x = [&](int r) -> float {       // unconditional: lanes past 16 repeat the pattern, nobody reads them
         const int l = min(lane & 7, 5);

@@ -12,7 +12,11 @@
 //     max-plus, hence bit-identical to the serial evaluation; Forward/Backward use a 6-step affine scan.
 // Integer semantics follow upstream impl_sse/vitfilter.c exactly (signed saturating 16-bit adds via
 // v_add_i16 clamp); float semantics follow impl_sse/fwdback.c up to the association order of sums.
-#include "p7x_wave.hpp"
+// The rows of the Viterbi filter, of MSV and of Forward are those of p7x_waverows.hpp, which the calibration kernels
+// (p7x_calibrate.hip) and, for Forward, the envelope and ensemble kernels run too; what is written here is each kernel's
+// staging, its work items and length model, vit_kernel's long-target branch, msv_wave_kernel's blocks of rows with the
+// begin score held, Forward's stored rows -- and Backward, whose recurrence has no second user.
+#include "p7x_waverows.hpp"
 #include "p7x_launch.hpp"
 
 namespace p7x {
@@ -29,68 +33,28 @@ __global__ void __launch_bounds__(kWsBlock) vit_kernel(const ArgRef ref)
   constexpr bool EG = C > 32;         // long models (M > 2048): the emission table is read where it lies (L2), only the transitions are staged
   constexpr bool TG = C > 128;        // M > 8192: 16 bytes per node no longer fit the LDS, the transitions are read through L2 as well
   static_assert(!TG || EG, "transitions through L2 only where the emissions are");
-  const uint4 *tr = TG ? reinterpret_cast<const uint4 *>(a.trans) : reinterpret_cast<const uint4 *>(smem);      // [Mpad]
-  const short *em = EG ? reinterpret_cast<const short *>(a.emis) : reinterpret_cast<const short *>(smem + (size_t) Mpad * 16);  // [kTabRows][Mpad]
-  {
-    if constexpr (!TG) {
-      const uint4 *gt = reinterpret_cast<const uint4 *>(a.trans);
-      uint4 *lt = reinterpret_cast<uint4 *>(smem);
-      for (int i = threadIdx.x; i < Mpad; i += kWsBlock) lt[i] = gt[i];
-    }
-    if constexpr (!EG) {
-      const uint4 *ge = reinterpret_cast<const uint4 *>(a.emis);
-      uint4 *le = reinterpret_cast<uint4 *>(smem + (size_t) Mpad * 16);
-      for (int i = threadIdx.x; i < a.nrows * Mpad / 8; i += kWsBlock) le[i] = ge[i];
-    }
-  }
+  if constexpr (!TG) stage_lds(smem, a.trans, Mpad);
+  if constexpr (!EG) stage_lds(smem + (size_t) Mpad * 16, a.emis, a.nrows * Mpad / 8);
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const short NEG = (short) -32768;
+  const uint4 *tr = TG ? reinterpret_cast<const uint4 *>(a.trans) : reinterpret_cast<const uint4 *>(smem);      // [Mpad]
+  const short *em = EG ? reinterpret_cast<const short *>(a.emis) : reinterpret_cast<const short *>(smem + (size_t) Mpad * 16);  // [kTabRows][Mpad]
 
   P7X_WAVE_ITEMS(it) {
     const Item item = load_item(a, it);
     const int L = item.L;
     const uint8_t *sq = item.sq;
     const int xwm = rfl((int) a.xwmove_tab[L]);
-
-    short mm[C], im[C], dm[C], tdd[C];
-#pragma unroll unroll_c(C)
-    for (int c = 0; c < C; ++c) { mm[c] = im[c] = dm[c] = NEG; tdd[c] = NEG; }
-    int xN = a.base_w, xB = xN + xwm, xJ = -32768, xC = -32768;
-    bool overflow = false;
     const int lt_thr = a.lt_thresh ? rfl(a.lt_thresh[it]) : INT_MAX;
+    short mm[C], im[C], dm[C], tdd[C];
+    ViterbiSpecials v;
+    vit_init(mm, im, dm, tdd, v, a.base_w, xwm);
 
-    for (int i0 = 0; i0 < L && !overflow; i0 += 64) {
+    for (int i0 = 0; i0 < L && !v.overflow; i0 += 64) {
       const int nrow = min(64, L - i0);
       const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
-      for (int r = 0; r < nrow && !overflow; ++r) {
-        const int x = __builtin_amdgcn_readlane((int) resid, r);
-        const short *er = em + x * Mpad + lane;
-        const short xBs = (short) xB;
-        short mp = (short) dpp_shr1(mm[C - 1], NEG);
-        short ip = (short) dpp_shr1(im[C - 1], NEG);
-        short dp = (short) dpp_shr1(dm[C - 1], NEG);
-        short rowmax = NEG, dmax = NEG, dcarry = NEG;
-#pragma unroll unroll_c(C)
-        for (int c = 0; c < C; ++c) {
-          const uint4 t = tr[c * 64 + lane];
-          short sv = adds16(xBs, lo16(t.x));
-          sv = max16(sv, adds16(mp, hi16(t.x)));
-          sv = max16(sv, adds16(ip, lo16(t.y)));
-          sv = max16(sv, adds16(dp, hi16(t.y)));
-          sv = adds16(sv, er[c * 64]);
-          rowmax = max16(rowmax, sv);
-          mp = mm[c]; ip = im[c]; dp = dm[c];
-          im[c] = max16(adds16(mp, hi16(t.z)), adds16(ip, lo16(t.w)));
-          mm[c] = sv;
-          dm[c] = dcarry;                       // M(i,k-1) -> D(i,k); node c=0 is patched below
-          dcarry = adds16(sv, lo16(t.z));
-          dmax = max16(dmax, dcarry);
-          tdd[c] = hi16(t.w);
-        }
-        dm[0] = (short) dpp_shr1(dcarry, NEG);
-
-        const int xE = wave_max_i32((int) rowmax);
+      for (int r = 0; r < nrow && !v.overflow; ++r) {
+        const int xE = vit_cells(mm, im, dm, tdd, v, tr, em + __builtin_amdgcn_readlane((int) resid, r) * Mpad + lane, lane);
         if (xE >= lt_thr) {
           // long-target scan: every match cell that holds the row maximum seeds a window; the rows start afresh and the
           // special states keep their values (upstream p7_ViterbiFilter_longtarget)
@@ -101,32 +65,14 @@ __global__ void __launch_bounds__(kWsBlock) vit_kernel(const ArgRef ref)
               const int slot = atomicAdd(a.lt_nrec, 1);
               if (slot < a.lt_cap) { a.lt_rec[3 * slot] = it; a.lt_rec[3 * slot + 1] = i0 + r + 1; a.lt_rec[3 * slot + 2] = k; }
             }
-            mm[c] = im[c] = dm[c] = NEG;
           }
+          vit_restart(mm, im, dm);
           continue;
         }
-        if (xE >= 32767) overflow = true;
-        xC = max(xC, xE + a.xw_e);              // xw[C][LOOP] = xw[J][LOOP] = xw[N][LOOP] = 0
-        xJ = max(xJ, xE + a.xw_e);
-        xB = max(xJ + xwm, xN + xwm);
-
-        const int Dmax = wave_max_i32((int) dmax);
-        if (Dmax + a.ddbound > xB) {            // lazy F: only now can a D->D path beat B->M on the next row
-#pragma unroll unroll_c(C)
-          for (int c = 1; c < C; ++c) dm[c] = max16(dm[c], adds16(dm[c - 1], tdd[c - 1]));
-          for (int pass = 0; pass < 64; ++pass) { // a carry can cross at most 63 lane boundaries
-            const short ddout = adds16(dm[C - 1], tdd[C - 1]);
-            const short cand = (short) dpp_shr1(ddout, NEG);
-            const int improved = wave_max_i32((cand > dm[0]) ? 1 : 0);
-            if (improved == 0) break;
-            dm[0] = max16(dm[0], cand);
-#pragma unroll unroll_c(C)
-            for (int c = 1; c < C; ++c) dm[c] = max16(dm[c], adds16(dm[c - 1], tdd[c - 1]));
-          }
-        }
+        vit_finish(dm, tdd, v, xE, a.xw_e, xwm, a.ddbound);
       }
     }
-    if (lane == 0) a.out_xC[it] = overflow ? 32767 : xC;
+    if (lane == 0) a.out_xC[it] = v.score();
   }
 }
 
@@ -148,14 +94,10 @@ __global__ void __launch_bounds__(kWsBlock) msv_wave_kernel(const ArgRef ref)
   const int nlist = a.nslots;
   if ((int) (blockIdx.x * (kWsBlock / 64)) >= nlist) return;
   constexpr bool EG = C > 32;         // long models (M > 2048): the table is read where it lies (L2)
-  const short *em = EG ? reinterpret_cast<const short *>(a.emis) : reinterpret_cast<const short *>(smem);      // [nrows][Mpad] bias - cost, kNegPad outside the model
-  if constexpr (!EG) {
-    const uint4 *ge = reinterpret_cast<const uint4 *>(a.emis);
-    uint4 *le = reinterpret_cast<uint4 *>(smem);
-    for (int i = threadIdx.x; i < a.nrows * Mpad / 8; i += kWsBlock) le[i] = ge[i];
-  }
+  if constexpr (!EG) stage_lds(smem, a.emis, a.nrows * Mpad / 8);
   __syncthreads();
   const int lane = threadIdx.x & 63;
+  const short *em = EG ? reinterpret_cast<const short *>(a.emis) : reinterpret_cast<const short *>(smem);      // [nrows][Mpad] bias - cost, kNegPad outside the model
   P7X_WAVE_ITEMS(it) {
     const int slot = it;
     const int L = rfl(a.slot_len[slot]);
@@ -164,10 +106,8 @@ __global__ void __launch_bounds__(kWsBlock) msv_wave_kernel(const ArgRef ref)
     const uint8_t *sq = a.dsq + (((unsigned long long) hi << 32) | lo);
     const int tjbm = rfl((int) a.tjb_tab[L]) + a.tbm;
     int mm[C];
-#pragma unroll unroll_c(C)
-    for (int c = 0; c < C; ++c) mm[c] = 0;
-    int xJ = 0, xEmax = 0;
-    int xB = max(a.base - tjbm, 0);
+    MsvSpecials m;
+    msv_init(mm, m, a.base, tjbm);
     // The begin score xB moves only when a row's maximum lifts xJ above the base, i.e. on a real hit.  Rows are therefore
     // run in blocks of kBlk with xB held: no wavefront reduction (and nothing else across the lanes but the one-lane
     // shift) sits on the row-to-row chain, and one reduction of the block's maximum tells whether the assumption held.
@@ -177,23 +117,10 @@ __global__ void __launch_bounds__(kWsBlock) msv_wave_kernel(const ArgRef ref)
     for (int i0 = 0; i0 < L; i0 += 64) {
       const int nrow = min(64, L - i0);
       const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
+      auto er = [&](int r) { return em + __builtin_amdgcn_readlane((int) resid, r) * Mpad + lane; };
       for (int r0 = 0; r0 < nrow; r0 += kBlk) {
         if (kBlk == 1) {                               // the recurrence as written, one reduction per row
-          const int x = __builtin_amdgcn_readlane((int) resid, r0);
-          const short *er = em + x * Mpad + lane;
-          int mp = dpp_shr1(mm[C - 1], 0);
-          int rowmax = kNegPad;
-#pragma unroll unroll_c(C)
-          for (int c = 0; c < C; ++c) {
-            const int sv = max(mp, xB) + (int) er[c * 64];
-            mp = mm[c];
-            mm[c] = sv;
-            rowmax = max(rowmax, sv);
-          }
-          const int xE = wave_max_i32(rowmax);
-          xEmax = max(xEmax, xE);
-          xJ = max(xJ, xE - a.tec);
-          xB = max(max(a.base, xJ) - tjbm, 0);
+          msv_step(mm, m, er(r0), a.base, a.tec, tjbm);
           continue;
         }
         const int nb = min(kBlk, nrow - r0);
@@ -201,56 +128,28 @@ __global__ void __launch_bounds__(kWsBlock) msv_wave_kernel(const ArgRef ref)
 #pragma unroll unroll_c(C)
         for (int c = 0; c < C; ++c) saved[c] = mm[c];
         int blkmax = kNegPad;
-        auto row_held = [&](int r) {
-          const int x = __builtin_amdgcn_readlane((int) resid, r);
-          const short *er = em + x * Mpad + lane;
-          int mp = dpp_shr1(mm[C - 1], 0);
-#pragma unroll unroll_c(C)
-          for (int c = 0; c < C; ++c) {
-            const int sv = max(mp, xB) + (int) er[c * 64];
-            mp = mm[c];
-            mm[c] = sv;
-            blkmax = max(blkmax, sv);
-          }
-        };
         if (C <= 4 && nb == kBlk) {                    // short models: the rows unrolled (their LDS reads issue ahead of the chain)
 #pragma unroll
-          for (int rr = 0; rr < kBlk; ++rr) row_held(r0 + rr);
+          for (int rr = 0; rr < kBlk; ++rr) msv_held(mm, m.xB, er(r0 + rr), blkmax);
         } else if (C <= 12) {
 #pragma unroll 4
-          for (int rr = 0; rr < nb; ++rr) row_held(r0 + rr);
+          for (int rr = 0; rr < nb; ++rr) msv_held(mm, m.xB, er(r0 + rr), blkmax);
         } else {
 #pragma unroll 2
-          for (int rr = 0; rr < nb; ++rr) row_held(r0 + rr);
+          for (int rr = 0; rr < nb; ++rr) msv_held(mm, m.xB, er(r0 + rr), blkmax);
         }
         const int xEb = wave_max_i32(blkmax);
-        if (xEb - a.tec <= max(a.base, xJ)) {          // xB was right for every row of the block
-          xEmax = max(xEmax, xEb);
-          xJ = max(xJ, xEb - a.tec);
+        if (xEb - a.tec <= max(a.base, m.xJ)) {        // xB was right for every row of the block
+          m.xEmax = max(m.xEmax, xEb);
+          m.xJ = max(m.xJ, xEb - a.tec);
           continue;
         }
 #pragma unroll unroll_c(C)
         for (int c = 0; c < C; ++c) mm[c] = saved[c];
-        for (int r = r0; r < r0 + nb; ++r) {
-          const int x = __builtin_amdgcn_readlane((int) resid, r);
-          const short *er = em + x * Mpad + lane;
-          int mp = dpp_shr1(mm[C - 1], 0);
-          int rowmax = kNegPad;
-#pragma unroll unroll_c(C)
-          for (int c = 0; c < C; ++c) {
-            const int sv = max(mp, xB) + (int) er[c * 64];
-            mp = mm[c];
-            mm[c] = sv;
-            rowmax = max(rowmax, sv);
-          }
-          const int xE = wave_max_i32(rowmax);
-          xEmax = max(xEmax, xE);
-          xJ = max(xJ, xE - a.tec);
-          xB = max(max(a.base, xJ) - tjbm, 0);
-        }
+        for (int r = r0; r < r0 + nb; ++r) msv_step(mm, m, er(r), a.base, a.tec, tjbm);
       }
     }
-    if (lane == 0 && L > 0) a.out_xJ[slot] = (xEmax >= 255 - a.bias) ? (int16_t) -1 : (int16_t) xJ;
+    if (lane == 0 && L > 0) a.out_xJ[slot] = (int16_t) m.score(a.bias);
   }
 }
 
@@ -372,9 +271,7 @@ __global__ void __launch_bounds__(kPkWaves * 64) msv_wavepk_kernel(const ArgRef 
 }
 
 // ======================================================================================= Forward parser
-// EG: the emission table does not fit in LDS next to the transitions (M > 1024) and is read from global memory
-// (it stays L2-resident: 30 rows x Mpad floats).
-template <int C, bool EG = false>
+template <int C>
 __global__ void __launch_bounds__(kWsBlock) fwd_kernel(const ArgRef ref)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -382,21 +279,13 @@ __global__ void __launch_bounds__(kWsBlock) fwd_kernel(const ArgRef ref)
   const WaveSeqArgs a = load_args<WaveSeqArgs>(ref);
   const int nlist = (a.abort_flag && *a.abort_flag) ? 0 : (a.nlist_ptr ? *a.nlist_ptr : a.nlist);
   if ((int) (blockIdx.x * (kWsBlock / 64)) >= nlist) return;         // no item for this block: skip the table load
+  constexpr bool EG = C > 16;         // M > 1024: the emission table does not fit in LDS next to the transitions and is read
+                                      // from global memory (it stays L2-resident: 30 rows x Mpad floats)
   constexpr bool TG = C > 64;         // M > 4096: the transitions no longer fit the LDS either and are read through L2
-  const float4 *tr = TG ? reinterpret_cast<const float4 *>(a.trans) : reinterpret_cast<const float4 *>(smem);      // [2*Mpad]
+  const TransView<false> tr{ TG ? reinterpret_cast<const float4 *>(a.trans) : reinterpret_cast<const float4 *>(smem), 0 };      // [2*Mpad]
   const float *em = EG ? reinterpret_cast<const float *>(a.emis) : reinterpret_cast<const float *>(smem + (size_t) Mpad * 32);      // [kTabRows][Mpad]
-  {
-    if constexpr (!TG) {
-      const float4 *gt = reinterpret_cast<const float4 *>(a.trans);
-      float4 *lt = reinterpret_cast<float4 *>(smem);
-      for (int i = threadIdx.x; i < 2 * Mpad; i += kWsBlock) lt[i] = gt[i];
-    }
-    if constexpr (!EG) {
-      const float4 *ge = reinterpret_cast<const float4 *>(a.emis);
-      float4 *le = reinterpret_cast<float4 *>(smem + (size_t) Mpad * 32);
-      for (int i = threadIdx.x; i < a.nrows * Mpad / 4; i += kWsBlock) le[i] = ge[i];
-    }
-  }
+  if constexpr (!TG) stage_lds(smem, a.trans, 2 * Mpad);
+  if constexpr (!EG) stage_lds(smem + (size_t) Mpad * 32, a.emis, a.nrows * Mpad / 4);
   __syncthreads();
   const int lane = threadIdx.x & 63;
 
@@ -408,85 +297,27 @@ __global__ void __launch_bounds__(kWsBlock) fwd_kernel(const ArgRef ref)
     const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f), ploop = 1.0f - pmove;
 
     float mm[C], im[C], dm[C];
-#pragma unroll unroll_c(C)
-    for (int c = 0; c < C; ++c) mm[c] = im[c] = dm[c] = 0.0f;
-    // product of this lane's D->D probabilities: the multiplier of an incoming D carry
-    float ddprod = 1.0f;
-#pragma unroll unroll_c(C)
-    for (int c = 0; c < C; ++c) ddprod *= tr[2 * (c * 64 + lane) + 1].w;
-
-    float xN = 1.0f, xB = pmove, xJ = 0.0f, xC = 0.0f, xE = 0.0f, totscale = 0.0f;
-    if (xo && lane == 0) { xo[0] = 0.0f; xo[1] = 1.0f; xo[2] = 0.0f; xo[3] = xB; xo[4] = 0.0f; xo[5] = 1.0f; }
+    ForwardRow<C, unroll_c(C), ForwardRefs<C>> f{{mm, im, dm}};
+    f.init(tr, lane, pmove);
+    if (xo && lane == 0) { xo[0] = 0.0f; xo[1] = 1.0f; xo[2] = 0.0f; xo[3] = f.xB; xo[4] = 0.0f; xo[5] = 1.0f; }
     for (int i0 = 0; i0 < L; i0 += 64) {
-     const int nrow = min(64, L - i0);
-     const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
-     for (int r = 0; r < nrow; ++r) {
-      const int i = i0 + r;
-      const int x = __builtin_amdgcn_readlane((int) resid, r);
-      const float *er = em + x * Mpad + lane;
-      float mp = dpp_shr1f(mm[C - 1], 0.0f), ip = dpp_shr1f(im[C - 1], 0.0f), dp = dpp_shr1f(dm[C - 1], 0.0f);
-      float esum = 0.0f, dcarry = 0.0f;
-      float tdd[C], tmd[C];
-#pragma unroll unroll_c(C)
-      for (int c = 0; c < C; ++c) {
-        const F8 t = load_f8(tr, c * 64 + lane);
-        float sv = xB * t.bm;
-        sv = sv + mp * t.mm;
-        sv = sv + ip * t.im;
-        sv = sv + dp * t.dm;
-        sv = sv * er[c * 64];
-        esum = esum + sv;
-        mp = mm[c]; ip = im[c]; dp = dm[c];
-        im[c] = mp * t.mi + ip * t.ii;
-        mm[c] = sv;
-        tdd[c] = t.dd; tmd[c] = t.md;
+      const int nrow = min(64, L - i0);
+      const uint32_t resid = (lane < nrow) ? sq[i0 + lane] : 0;
+      for (int r = 0; r < nrow; ++r) {
+        f.row(tr, em, Mpad, lane, __builtin_amdgcn_readlane((int) resid, r), pmove, ploop, a.xf_e_move, a.xf_e_loop);
+        if (xo && lane == 0) {
+          float *row = xo + (size_t) (i0 + r + 1) * 6;
+          row[0] = f.xE; row[1] = f.xN; row[2] = f.xJ; row[3] = f.xB; row[4] = f.xC; row[5] = f.scale;
+        }
       }
-      // D(i,k) = M(i,k-1) tMD(k-1) + D(i,k-1) tDD(k-1): serial inside the lane, affine scan across lanes
-      float A = 0.0f;                                   // this lane's outgoing carry for a zero incoming carry
-#pragma unroll unroll_c(C)
-      for (int c = 0; c < C; ++c) { dm[c] = A; A = mm[c] * tmd[c] + A * tdd[c]; }
-      float sa = A, sp = ddprod;                        // inclusive scan of (carry, multiplier)
-      affine_scan_up(sa, sp);
-      dcarry = dpp_shr1f(sa, 0.0f);                     // exclusive: the carry entering this lane
-      {
-        float w = dcarry;
-#pragma unroll unroll_c(C)
-        for (int c = 0; c < C; ++c) { dm[c] = dm[c] + w; esum = esum + dm[c]; w = w * tdd[c]; }
-      }
-      xE = wave_sum_f32(esum);
-      xN = xN * ploop;
-      xC = (xC * ploop) + (xE * a.xf_e_move);
-      xJ = (xJ * ploop) + (xE * a.xf_e_loop);
-      xB = (xJ * pmove) + (xN * pmove);
-      float scale = 1.0f;
-      if (xE > 1.0e4f) {
-        xN = xN / xE; xC = xC / xE; xJ = xJ / xE; xB = xB / xE;
-        const float inv = (float) (1.0 / (double) xE);
-#pragma unroll unroll_c(C)
-        for (int c = 0; c < C; ++c) { mm[c] *= inv; dm[c] *= inv; im[c] *= inv; }
-        scale = xE;
-        totscale = (float) ((double) totscale + log((double) xE));
-        xE = 1.0f;
-      }
-      if (xo && lane == 0) {
-        float *row = xo + (size_t) (i + 1) * 6;
-        row[0] = xE; row[1] = xN; row[2] = xJ; row[3] = xB; row[4] = xC; row[5] = scale;
-      }
-     }
     }
-    if (lane == 0) {
-      float sc;
-      if (xC != xC) sc = __builtin_nanf("");
-      else if ((L > 0 && xC == 0.0f) || __builtin_isinf(xC)) sc = __builtin_inff();
-      else sc = (float) ((double) totscale + log((double) (xC * pmove)));
-      a.out_sc[it] = sc;
-    }
+    if (lane == 0) a.out_sc[it] = forward_score(f.xC, f.totscale, pmove, L);
   }
 }
 
 // ======================================================================================= Backward parser
 // Mirror of the Forward parser, re-using Forward's per-row scale factors (upstream backward_engine).
-template <int C, bool EG = false>
+template <int C>
 __global__ void __launch_bounds__(kWsBlock) bck_kernel(const ArgRef ref)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -494,21 +325,11 @@ __global__ void __launch_bounds__(kWsBlock) bck_kernel(const ArgRef ref)
   const WaveSeqArgs a = load_args<WaveSeqArgs>(ref);
   const int nlist = (a.abort_flag && *a.abort_flag) ? 0 : (a.nlist_ptr ? *a.nlist_ptr : a.nlist);
   if ((int) (blockIdx.x * (kWsBlock / 64)) >= nlist) return;         // no item for this block: skip the table load
-  constexpr bool TG = C > 64;         // M > 4096: the transitions no longer fit the LDS either and are read through L2
+  constexpr bool EG = C > 16, TG = C > 64;      // as fwd_kernel
   const float4 *tr = TG ? reinterpret_cast<const float4 *>(a.trans) : reinterpret_cast<const float4 *>(smem);      // [2*Mpad]
   const float *em = EG ? reinterpret_cast<const float *>(a.emis) : reinterpret_cast<const float *>(smem + (size_t) Mpad * 32);      // [kTabRows][Mpad]
-  {
-    if constexpr (!TG) {
-      const float4 *gt = reinterpret_cast<const float4 *>(a.trans);
-      float4 *lt = reinterpret_cast<float4 *>(smem);
-      for (int i = threadIdx.x; i < 2 * Mpad; i += kWsBlock) lt[i] = gt[i];
-    }
-    if constexpr (!EG) {
-      const float4 *ge = reinterpret_cast<const float4 *>(a.emis);
-      float4 *le = reinterpret_cast<float4 *>(smem + (size_t) Mpad * 32);
-      for (int i = threadIdx.x; i < a.nrows * Mpad / 4; i += kWsBlock) le[i] = ge[i];
-    }
-  }
+  if constexpr (!TG) stage_lds(smem, a.trans, 2 * Mpad);
+  if constexpr (!EG) stage_lds(smem + (size_t) Mpad * 32, a.emis, a.nrows * Mpad / 4);
   __syncthreads();
   const int lane = threadIdx.x & 63;
 
@@ -668,11 +489,15 @@ int vit_pick_C(int M)
   return -1;
 }
 
-template <typename K>
-static int launch_ws(K kernel, const ArgRun<WaveSeqArgs> &a, size_t lds_bytes, int num_cu, hipStream_t st)
+// a launch of kWsBlock threads, one wavefront per item; the record's own count bounds the device-side one
+static int item_bound(const WaveSeqArgs &r) { return r.nlist; }
+static int item_bound(const MsvWaveArgs &r) { return r.nslots; }
+
+template <typename K, typename A>
+static int launch_ws(K kernel, const ArgRun<A> &a, size_t lds_bytes, int num_cu, hipStream_t st)
 {
   long want = 0;
-  for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nlist + 3) / 4);      // nlist bounds the device-side count
+  for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) item_bound(a.at(i)) + 3) / 4);
   if (want <= 0) return P7X_OK;
   int per_cu = 0;
   const int pst = kernel_blocks_per_cu(kernel, kWsBlock, lds_bytes, &per_cu);
@@ -694,13 +519,12 @@ int vit_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
 
 int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st)
 {
-  long want = 0;
-  for (int i = 0; i < a.n; ++i) want = std::max<long>(want, ((long) a.at(i).nslots + 3) / 4);
-  if (want <= 0) return P7X_OK;
+  if (a.n <= 0) return P7X_OK;
   const int C = a.at(0).C, nrows = a.at(0).nrows;
   if (a.at(0).emis_pk && C >= 20) {          // long models: packed pairs, sixteen wavefronts per copy of the table
     long wantpk = 0;
     for (int i = 0; i < a.n; ++i) wantpk = std::max<long>(wantpk, ((long) a.at(i).nslots + kPkWaves - 1) / kPkWaves);
+    if (wantpk <= 0) return P7X_OK;
     auto gopk = [&](auto kernel) -> int {
       const size_t lds = (size_t) 64 * C * nrows * 2;
       const int gst = kernel_grant_lds(kernel, lds);
@@ -718,16 +542,10 @@ int msv_wave_launch(const ArgRun<MsvWaveArgs> &a, int num_cu, hipStream_t st)
       default: break;
     }
   }
-  auto go = [&](auto kernel) -> int {
-    const size_t lds = msv_wave_lds_bytes(C, nrows);
-    int per_cu = 0;
-    const int pst = kernel_blocks_per_cu(kernel, kWsBlock, lds, &per_cu);
-    if (pst != P7X_OK) return pst;
-    hipLaunchKernelGGL(kernel, dim3(lane_grid(want, (long) num_cu * per_cu, a.n), (unsigned) a.n), dim3(kWsBlock), lds, st, a.ref());
-    P7X_HIP(hipGetLastError());
-    return P7X_OK;
-  };
-  return node_tier_dispatch(C, "no wave-per-target MSV kernel for this model length", [&](auto tier) { return go(msv_wave_kernel<decltype(tier)::value>); });
+  return node_tier_dispatch(C, "no wave-per-target MSV kernel for this model length", [&](auto tier) {
+    constexpr int CC = decltype(tier)::value;
+    return launch_ws(msv_wave_kernel<CC>, a, msv_wave_lds_bytes(CC, nrows), num_cu, st);
+  });
 }
 
 int fwd_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
@@ -736,7 +554,7 @@ int fwd_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
   const int C = a.at(0).C, nrows = a.at(0).nrows;
   return node_tier_dispatch(C, "model too long for the Forward/Backward kernels", [&](auto tier) {
     constexpr int CC = decltype(tier)::value;
-    return launch_ws(fwd_kernel<CC, (CC > 16)>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
+    return launch_ws(fwd_kernel<CC>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
   });
 }
 int bck_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
@@ -745,7 +563,7 @@ int bck_launch(const ArgRun<WaveSeqArgs> &a, int num_cu, hipStream_t st)
   const int C = a.at(0).C, nrows = a.at(0).nrows;
   return node_tier_dispatch(C, "model too long for the Forward/Backward kernels", [&](auto tier) {
     constexpr int CC = decltype(tier)::value;
-    return launch_ws(bck_kernel<CC, (CC > 16)>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
+    return launch_ws(bck_kernel<CC>, a, fwd_lds_bytes(CC, nrows), num_cu, st);
   });
 }
 

@@ -1,5 +1,9 @@
-// p7x_wave.hpp -- device helpers shared by the wave-per-sequence kernels (p7x_vitfwd.hip, p7x_envelope.hip):
-// DPP shifts and reductions over a 64-lane wavefront, scalar-uniform work-item loading, f32 transition records.
+// p7x_wave.hpp -- device helpers shared by the wave-per-sequence kernels: DPP shifts and reductions over a 64-lane
+// wavefront, scalar-uniform work-item loading, LDS staging, f32 transition records.  Included by
+//   p7x_waverows.hpp   the shared row bodies; through it p7x_vitfwd.hip, p7x_calibrate.hip, p7x_ensemble.hip and
+//                      p7x_envkernel.hpp (p7x_envelope.hip, p7x_align.hip)
+//   p7x_vitpk.hip, p7x_fwdpk.hip, p7x_ssvlong.hip, p7x_envscore.hip, p7x_pipeline.hip, p7x_oaguard.hpp and (host code:
+//   kWsBlock and the argument records) p7x_tracealign.cpp   directly
 #pragma once
 #include "p7x_device.hpp"
 #include "p7x_kernels.hpp"
@@ -116,6 +120,15 @@ __device__ __forceinline__ Item load_item(const WaveSeqArgs &a, int it)
   const int wave0_ = rfl((int) (blockIdx.x * (kWsBlock / 64) + (threadIdx.x >> 6)));                        \
   const int nwaves_ = (int) (gridDim.x * (kWsBlock / 64));                                                  \
   for (int it = wave0_; it < nlist; it += nwaves_)
+
+// Table staging: the block's kWsBlock threads copy <n> 16-byte units from global memory to LDS.  The caller says what it
+// stages and where, and synchronises the block afterwards.
+__device__ __forceinline__ void stage_lds(void *lds, const void *glob, int n)
+{
+  const uint4 *g = reinterpret_cast<const uint4 *>(glob);
+  uint4 *l = reinterpret_cast<uint4 *>(lds);
+  for (int i = threadIdx.x; i < n; i += kWsBlock) l[i] = g[i];
+}
 
 // Loops over the C nodes of a lane are unrolled (the row state then lives in registers) up to 32 nodes per lane; the
 // long-model instantiations beyond that (M > 2048) keep them rolled: the row state goes to scratch memory, the code

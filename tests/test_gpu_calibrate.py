@@ -55,7 +55,8 @@ def world(libp7x, oracle):
 
 def test_raw_scores_against_the_oracle_and_the_cascade_kernels(world):
     """xJ and xC bit for bit the oracle's and p7x_filters_batch's; Forward within DESIGN 3.3's tolerance of the oracle and equal
-    to p7x_filters_batch (fwd_kernel: the same operations in the same order)."""
+    to p7x_filters_batch.  The calibration kernels and the cascade kernels (msv_wave_kernel, vit_kernel, fwd_kernel) run one row
+    body each (p7x_waverows.hpp), so their equality compares two users of it; the oracle pins both."""
     for M, raw, cpu, par in zip(LENGTHS_M, world["raw"], world["cpu"], world["par"]):
         assert np.array_equal(raw[0], cpu["raw"][0]) and np.array_equal(raw[0], par["xJ"]), M
         assert np.array_equal(raw[1], cpu["raw"][1]) and np.array_equal(raw[1], par["xC"]), M
