@@ -10,14 +10,20 @@
 //     _mm_adds_epi16 / _mm_max_epi16 of impl_sse/vitfilter.c exactly);
 //   * transitions (8 x int16 per node: BM MM IM DM MD MI II DD) and emissions come from LDS as ds_read_b128,
 //     the DP rows (M, I, D) stay in 3P registers, two sets of them (a row reads one and writes the other);
-//   * xE / Dmax are 3- or 4-step DPP butterflies inside the group (T = 32, 64: one or two half exchanges between the
-//     16-lane rows on top, v_permlane16_swap / v_permlane32_swap), the special states are per-lane integers that
-//     are uniform within a group; targets that have ended are masked, the row loop runs to the longest target of
-//     the wavefront;
-//   * lazy F follows upstream: D gets only M->D unless Dmax + ddbound > xB for that target; then the D->D closure
-//     is evaluated in full: two packed ops per register walk every stripe, the carry into the next stripe is a
-//     stripe shift, passes repeat until nothing improves (two on average).
-// Results are bit-identical to p7x_vitfwd.hip::vit_kernel and to the oracle (tests/test_gpu_filters.py).
+//   * xE and Dmax share one 3- or 4-step DPP butterfly inside the group: each is folded to 16 bits and the two ride in
+//     the halves of one dword (T = 32, 64: one or two half exchanges between the 16-lane rows on top,
+//     v_permlane16_swap / v_permlane32_swap), the special states are per-lane integers that are uniform within a
+//     group; targets that have ended are masked, the row loop runs to the longest target of the wavefront;
+//   * lazy F follows upstream in what it decides (Dmax + ddbound > xB, per target), not in when the work is done: the
+//     first pass of the D->D closure, two packed ops per register down every stripe, is part of the register loop of
+//     every row, and the stripe shift that the row pays for anyway carries the stripe's D->D exit along with M->D.  A
+//     target that asks then enters the pass loop (push register 0 down its stripe, carry, repeat until nothing
+//     improves: 1.0 to 1.1 passes per row for P >= 8, 2.1 for P = 4), which reads the D->D transitions from LDS again.
+// Per row of <8, 8>: 128 packed operations, 37 other VALU, 22 LDS reads (the D->D transitions of the pass loop among
+// them); a pass of the closure loop 16 packed, 7 other VALU, 9 scalar (generated code, gfx950;
+// profiles/r22_vit_row.md has every instantiation).
+// Results are bit-identical to p7x_vitfwd.hip::vit_kernel and to the oracle (tests/test_gpu_filters.py,
+// tests/test_gpu_vit_row.py).
 #include "p7x_wave.hpp"
 #include "p7x_launch.hpp"
 
@@ -57,12 +63,19 @@ constexpr int vitpk_rowq(int T, int P)
   return T == 8 ? ((n & 15) == 8 ? n : n + 8) : n;
 }
 
-#define P7X_DPP_U(v, ctrl) ((uint32_t) __builtin_amdgcn_update_dpp((int) kNeg2, (int) (v), (ctrl), 0xf, 0xf, false))
+// DPP move.  Every use below either has a source lane for every lane (quad_perm, mirrors, wave_ror) or replaces the one lane
+// that has none (wave_shr:1, lane 0 of the wavefront: a group's first lane, which takes the `first` arm of the select in
+// stripe_shift).  With bound_ctrl and a zero `old` the move needs no v_mov to materialise the value of the lanes without
+// a source; with old = (-32768, -32768) the compiler emitted one in front of every move.
+#define P7X_DPP_U(v, ctrl) ((uint32_t) __builtin_amdgcn_update_dpp(0, (int) (v), (ctrl), 0xf, 0xf, true))
 
-// maximum over the T lanes of a group, every lane receives it.  Packed pairs in, one int out.
+// Maxima over the T lanes of a group of two packed pairs at once, every lane receives both: the halves of a are folded
+// into the low half of one dword and those of b into its high half (two v_perm_b32 and one packed max), so that one
+// butterfly of v_pk_max_i16 serves xE and Dmax.
 template <int T>
-__device__ __forceinline__ int group_max(uint32_t v)
+__device__ __forceinline__ void group_max2(uint32_t a, uint32_t b, int &amax, int &bmax)
 {
+  uint32_t v = pk_max(__builtin_amdgcn_perm(b, a, 0x05040100u), __builtin_amdgcn_perm(b, a, 0x07060302u));   // (a.lo, b.lo), (a.hi, b.hi)
   v = pk_max(v, P7X_DPP_U(v, 0xB1));      // quad_perm [1,0,3,2]
   v = pk_max(v, P7X_DPP_U(v, 0x4E));      // quad_perm [2,3,0,1]
   v = pk_max(v, P7X_DPP_U(v, 0x141));     // row_half_mirror: 8 lanes
@@ -75,8 +88,12 @@ __device__ __forceinline__ int group_max(uint32_t v)
     const auto x = __builtin_amdgcn_permlane32_swap(v, v, false, false);       // lanes 0-31 <-> 32-63
     v = pk_max(x[0], x[1]);
   }
-  return max(lo_of(v), hi_of(v));
+  amax = lo_of(v); bmax = hi_of(v);
 }
+
+#ifdef P7X_VITPK_COUNT
+__device__ unsigned long long vitpk_row_counts[3];
+#endif
 
 } // namespace
 
@@ -110,12 +127,13 @@ template <int T, int P>
 __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, const uint4 *trbl, const uint4 *er, bool first, bool hi,
                                         bool active, int xwm, const uint32_t (&mi)[P], const uint32_t (&ii)[P],
                                         const uint32_t (&di)[P], uint32_t (&mo_)[P], uint32_t (&io_)[P], uint32_t (&do_)[P],
-                                        const uint32_t (&tdd)[P], RowState &rs)
+                                        RowState &rs)
 {
   constexpr int PS = (P + 3) & ~3;
   const uint32_t xBv = splat16(rs.xB);
   uint32_t mp = stripe_shift<T>(mi[P - 1], first, hi), ip = stripe_shift<T>(ii[P - 1], first, hi), dp = stripe_shift<T>(di[P - 1], first, hi);
   uint32_t xEv = kNeg2, dmaxv = kNeg2, dcv = kNeg2;
+  uint32_t ddp = kNeg2;                    // D->D transition out of the register before this one
 #pragma unroll
   for (int j4 = 0; j4 < PS; j4 += 4) {
     const uint4 e4 = er[(j4 / 4) * T];
@@ -131,7 +149,12 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
         sv = pk_adds(sv, ev[jj]);
         xEv = pk_max(xEv, sv);
         mo_[q] = sv;
-        if (q > 0) do_[q] = dcv;                                 // M(i,k-1) -> D(i,k), D->D follows in the closure
+        // D(i,k) = max(M(i,k-1) + MD, D(i,k-1) + DD) down the stripe: the first pass of the D->D closure, two packed
+        // operations per register among the fourteen others, whether or not a target asks for the closure (below).
+        // Register 0 counts as -32768 here: what enters a stripe from the one before is known only after the loop.
+        if (q == 1) do_[1] = dcv;
+        if (q > 1) do_[q] = pk_max(dcv, pk_adds(do_[q - 1], ddp));
+        ddp = tb.w;
         dcv = pk_adds(sv, tb.x);
         dmaxv = pk_max(dmaxv, dcv);
         io_[q] = pk_max(pk_adds(mi[q], tb.y), pk_adds(ii[q], tb.z));
@@ -141,9 +164,10 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
     // keep the LDS loads of later registers behind this point: hoisting all 2P transition loads costs 8 VGPRs each
     asm volatile("" ::: "memory");
   }
-  do_[0] = stripe_shift<T>(dcv, first, hi);                      // the first node of a stripe follows the last of the one before
-  const int xE = group_max<T>(xEv);
-  const int Dmax = group_max<T>(dmaxv);
+  // the first node of a stripe follows the last of the one before: M->D, and the D->D exit of that stripe's first pass
+  do_[0] = stripe_shift<T>(pk_max(dcv, pk_adds(do_[P - 1], ddp)), first, hi);
+  int xE, Dmax;
+  group_max2<T>(xEv, dmaxv, xE, Dmax);
   if (active) {
     if (xE >= 32767) rs.overflow = true;
     rs.xC = max(rs.xC, xE + a.xw_e);               // xw[C][LOOP] = xw[J][LOOP] = xw[N][LOOP] = 0
@@ -151,15 +175,35 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
     rs.xB = max(rs.xJ + xwm, rs.xN + xwm);
   }
   const bool trig = active && (Dmax + a.ddbound > rs.xB);          // lazy F, per target
-#ifdef P7X_VITPK_NO_CLOSURE      // build-time experiment (timing only, wrong scores): what the D->D closure costs
+  // After the first pass every register but 0 is closed under D->D inside its stripe, and register 0 holds what the
+  // stripe before sends.  What remains is to push that value down its own stripe and to carry on from there: the pass
+  // loop as it was, entered from a row that is one pass further.  The fixed point of a max-plus relaxation does not
+  // depend on the order of the relaxations, so the loop ends where it ended when it started from M->D alone.
+  // (A test whether any register 0 of a target that asked beats its register 1, adds(do_[0], DD[0]) > do_[1], would
+  // show a row that is closed already.  Measured on 300-residue targets, M = 60 ... 500: it spared 0.0 % of the rows
+  // that enter, with 64 lanes there is always one.)
+#ifdef P7X_VITPK_COUNT           // build-time experiment: rows of all wavefronts, rows that enter the pass loop, passes
+  const bool count_lane = (threadIdx.x & 63) == 0;
+  if (count_lane) atomicAdd(&vitpk_row_counts[0], 1ull);
+#endif
+#ifdef P7X_VITPK_NO_CLOSURE      // build-time experiment (timing only, wrong scores): what the remaining passes cost
   if (false) {
 #else
   if (__any(trig)) {
 #endif
+#ifdef P7X_VITPK_COUNT
+    if (count_lane) atomicAdd(&vitpk_row_counts[1], 1ull);
+#endif
     // The registers of every target of the wavefront are walked, also of those that did not ask for the closure:
     // relaxing D->D edges of such a target cannot reach the next row's M (that is what the lazy-F bound says), so its
-    // score is the same with or without them.  Only the carry into the next stripe is restricted to the targets that
-    // asked, so that the others cannot prolong the loop.  Passes repeat until no stripe improves (2T at most).
+    // score is the same with or without them; the first pass above relies on the same bound.  Only the carry into the
+    // next stripe is restricted to the targets that asked, so that the others cannot prolong the loop.  Passes repeat
+    // until no stripe improves (2T at most).
+    // The D->D transitions come from LDS once more: the registers of the row just read are free here, whereas P
+    // registers held from row to row for this loop cost most instantiations a wavefront per SIMD.
+    uint32_t tdd[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) tdd[q] = trbl[q * T].w;
     int pass = 0;
     bool more;
     do {
@@ -171,6 +215,9 @@ __device__ __forceinline__ void vit_row(const VitPkArgs &a, const uint4 *tral, c
       const bool changed = d0 != do_[0];
       do_[0] = d0;
       more = __any(changed) && ++pass < 2 * T;
+#ifdef P7X_VITPK_COUNT
+      if (count_lane) atomicAdd(&vitpk_row_counts[2], 1ull);
+#endif
     } while (more);
   }
 }
@@ -188,8 +235,20 @@ constexpr int vitpk_waves(int T, int P)
   return 4;
 }
 
+// Wavefronts per SIMD that an instantiation is compiled for (the second launch bound): left alone, the register allocator
+// lands a few registers beyond a step of the occupancy table for some P and not for its neighbours (<8, 10> took 136
+// registers, <8, 12> 126).  These are the steps that the row loop's 6P registers and its temporaries fit; where the
+// step is tight (P = 8, 12, 17) one to three per-target values are spilled around the row loop, none inside it.
+// T = 32, 64: what vitpk_waves puts on a SIMD.
+constexpr int vitpk_simd_waves(int T, int P)
+{
+  if (T == 64) return P <= 12 ? 4 : 3;
+  if (T == 32) return P <= 12 ? 4 : P <= 16 ? 3 : 2;
+  return P <= 2 ? 8 : P <= 4 ? 7 : P <= 6 ? 6 : P <= 8 ? 5 : P <= 12 ? 4 : P <= 17 ? 3 : 2;
+}
+
 template <int T, int P>
-__global__ void __launch_bounds__(64 * vitpk_waves(T, P)) vitpk_kernel(const ArgRef ref)
+__global__ void __launch_bounds__(64 * vitpk_waves(T, P), vitpk_simd_waves(T, P)) vitpk_kernel(const ArgRef ref)
 {
   constexpr int G = 64 / T;                // targets per wavefront
   constexpr int NW = vitpk_waves(T, P), NT = 64 * NW;
@@ -220,10 +279,6 @@ __global__ void __launch_bounds__(64 * vitpk_waves(T, P)) vitpk_kernel(const Arg
   const int wave0 = rfl((int) (blockIdx.x * NW + (threadIdx.x >> 6)));
   const int nwaves = (int) gridDim.x * NW;
   const uint4 *tral = tra + s, *trbl = trb + s, *eml = em + s;
-  uint32_t tdd[P];                 // D->D transitions of this lane's nodes: row-invariant, kept in registers for the closure
-#pragma unroll
-  for (int q = 0; q < P; ++q) tdd[q] = trbl[q * T].w;
-
   for (int it0 = nskip + wave0 * G; it0 < nlist; it0 += nwaves * G) {
     const int it = it0 + g;
     const bool have = it < nlist;
@@ -252,17 +307,20 @@ __global__ void __launch_bounds__(64 * vitpk_waves(T, P)) vitpk_kernel(const Arg
         word |= x << (8 * b);
       }
       const int nrow = min(4 * T, Lmax - i0);
-      auto residue = [&](int r) -> uint32_t {
-        const uint32_t w = (uint32_t) __shfl((int) word, g * T + (r >> 2));
-        return (w >> (8 * (r & 3))) & 0xffu;
-      };
+      // The four residues of rows r .. r|3 come to the group from lane r/4 (one ds_bpermute); a pair of rows fetches the
+      // word of the pair after it, so that no row's emission address waits for that round trip.
+      auto fetch = [&](int r) -> uint32_t { return (uint32_t) __shfl((int) word, g * T + min(r >> 2, T - 1)); };
+      auto residue = [](uint32_t w, int r) -> uint32_t { return (w >> (8 * (r & 3))) & 0xffu; };
+      uint32_t w = fetch(0);
       int r = 0;
       for (; r + 1 < nrow; r += 2) {
-        vit_row<T, P>(a, tral, trbl, eml + residue(r) * ROWQ, first, hi, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, tdd, rs);
-        vit_row<T, P>(a, tral, trbl, eml + residue(r + 1) * ROWQ, first, hi, i0 + r + 1 < L, xwm, mB, iB, dB, mA, iA, dA, tdd, rs);
+        const uint32_t wn = fetch(r + 2);
+        vit_row<T, P>(a, tral, trbl, eml + residue(w, r) * ROWQ, first, hi, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, rs);
+        vit_row<T, P>(a, tral, trbl, eml + residue(w, r + 1) * ROWQ, first, hi, i0 + r + 1 < L, xwm, mB, iB, dB, mA, iA, dA, rs);
+        w = wn;
       }
       if (r < nrow) {     // odd row count (only the last block of a group): one more row, then back into set A
-        vit_row<T, P>(a, tral, trbl, eml + residue(r) * ROWQ, first, hi, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, tdd, rs);
+        vit_row<T, P>(a, tral, trbl, eml + residue(w, r) * ROWQ, first, hi, i0 + r < L, xwm, mA, iA, dA, mB, iB, dB, rs);
 #pragma unroll
         for (int j = 0; j < P; ++j) { mA[j] = mB[j]; iA[j] = iB[j]; dA[j] = dB[j]; }
       }
@@ -343,3 +401,13 @@ int vitpk_launch(int T, int P, const ArgRun<VitPkArgs> &a, int num_cu, hipStream
 }
 
 } // namespace p7x
+
+#ifdef P7X_VITPK_COUNT
+// out[0..2]: rows of all wavefronts since the library was loaded, those that entered the pass loop (a target asked for
+// the closure), passes of that loop (not part of the C-ABI: the symbol exists only in a build with the flag)
+extern "C" int p7x_vitpk_row_counts(unsigned long long *out)
+{
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(p7x::vitpk_row_counts), 3 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
+}
+#endif
