@@ -477,6 +477,14 @@ int      p7x_tophits_sort_by_seqidx(p7x_tophits *th);    /* p7_tophits_SortBySeq
 int      p7x_tophits_is_sorted(const p7x_tophits *th, int by_seqidx);   /* TopHits.is_sorted, plan7.pyx:9078-9118; 1 / 0 */
 /* Hit.reported / included / dropped / duplicate setters (plan7.pyx:2125-2235): replace the P7X_IS_* flag word of hit i. */
 int      p7x_tophits_set_hit_flags(p7x_tophits *th, int64_t i, uint32_t flags);
+/* p7_tophits_CompareRanking (TopHits.compare_ranking, plan7.pyx:8897-8930; what a jackhmmer round does with the hits of the
+ * round before): ranked[nranked] are the names of the hits the previous round included.  Walks the list in its current
+ * order: an included hit whose name is not among them gets P7X_IS_NEW and is counted, a hit that is not included and
+ * whose name is among them gets P7X_IS_DROPPED; no flag is cleared.  included[0 .. min(*nincluded, cap)) receive the
+ * positions of the included hits in list order (the next ranking), *nincluded their number.  Returns the number of new
+ * hits, -1 on bad arguments. */
+int64_t  p7x_tophits_compare_ranking(p7x_tophits *th, const char *const *ranked, size_t nranked, int64_t *included, size_t cap,
+                                     int64_t *nincluded);
 /* Hit.name / accession / description setters (plan7.pyx:1960-2050): which = 1 name (not NULL), 2 accession, 4 description
  * (NULL clears); pointers handed out earlier by p7x_tophits_get_hit for this hit are invalidated. */
 int      p7x_tophits_set_hit_text(p7x_tophits *th, int64_t i, int which, const char *value);
@@ -552,6 +560,11 @@ int64_t p7x_msa_alen(const p7x_msa *msa);
  * characters and returns the full length, -1 on bad arguments (MSA.alignment / TextMSA, easel.pyx MSA 5790-6400) */
 int64_t p7x_msa_get(const p7x_msa *msa, int64_t idx, int which, char *buf, size_t cap);
 void    p7x_msa_destroy(p7x_msa *msa);
+/* The rows of an alignment made with P7X_MSA_DIGITIZE as digital codes, out[n][alen] row-major (a residue in either case
+ * is its code, '-' and '.' the alphabet's gap code): what p7x_msa_counts takes, without a second pass over the text.
+ * Returns n * alen and writes the matrix when nbytes holds it; -1 for an alignment made without the flag, and under the
+ * test seam "msa_codes" = 0 (the caller then encodes the text rows, as it did before the matrix was kept). */
+int64_t p7x_msa_codes(const p7x_msa *msa, uint8_t *out, size_t nbytes);
 /* Stockholm text as Easel writes it (MSA.write(fh, "stockholm"), easel.pyx MSA.write; esl_msafile_stockholm.c): names
  * padded to the longest, 200 columns per block, #=GS AC / DE, #=GR PP per row, #=GC SS_cons / PP_cons / RF.  accs,
  * descs, pps and the annotation lines may be NULL (or hold NULL / ""); every row, and every PP / annotation line that is

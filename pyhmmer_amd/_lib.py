@@ -224,6 +224,7 @@ _SIGNATURES = {
     "p7x_tophits_is_sorted": (C.c_int, [_VP, C.c_int]),
     "p7x_tophits_set_hit_flags": (C.c_int, [_VP, C.c_int64, C.c_uint32]),
     "p7x_tophits_set_hit_text": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_char_p]),
+    "p7x_tophits_compare_ranking": (C.c_int64, [_VP, C.POINTER(C.c_char_p), C.c_size_t, _VP, C.c_size_t, C.POINTER(C.c_int64)]),
     "p7x_tophits_get_timings": (C.c_int, [_VP, C.POINTER(C.c_double), C.c_int]),
     "p7x_search_block_begin": (C.c_int, [C.POINTER(PipelineCfg), _VP, _VP, _VP, C.POINTER(_VP)]),
     "p7x_search_block_enqueue": (C.c_int, [C.POINTER(PipelineCfg), _VP, _VP, _VP, C.POINTER(_VP)]),
@@ -282,6 +283,7 @@ _SIGNATURES = {
     "p7x_msa_alen": (C.c_int64, [_VP]),
     "p7x_msa_get": (C.c_int64, [_VP, C.c_int64, C.c_int, C.c_char_p, C.c_size_t]),
     "p7x_msa_destroy": (None, [_VP]),
+    "p7x_msa_codes": (C.c_int64, [_VP, _VP, C.c_size_t]),
     "p7x_msa_write_stockholm": (C.c_int64, [C.c_size_t, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                             C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_char_p,
                                             C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),

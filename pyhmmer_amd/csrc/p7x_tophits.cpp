@@ -16,6 +16,7 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 
 namespace p7x {
 
@@ -910,6 +911,28 @@ int p7x_tophits_set_hit_flags(p7x_tophits *th, int64_t i, uint32_t flags)
   Hit &h = th->order.size() == th->hits.size() ? th->hits[th->order[i]] : th->hits[i];
   h.flags = flags;
   return P7X_OK;
+}
+
+// p7_tophits_CompareRanking (upstream p7_tophits.c; TopHits.compare_ranking): the keys of the previous round's included hits
+// against this list, in its current order
+int64_t p7x_tophits_compare_ranking(p7x_tophits *th, const char *const *ranked, size_t nranked, int64_t *included, size_t cap,
+                                    int64_t *nincluded)
+{
+  if (!th || (nranked && !ranked) || !nincluded) { set_error("p7x_tophits_compare_ranking: bad arguments"); return -1; }
+  std::unordered_set<std::string> seen;
+  for (size_t r = 0; r < nranked; ++r) if (ranked[r]) seen.insert(ranked[r]);
+  const size_t n = th->hits.size();
+  const bool ordered = th->order.size() == n;
+  int64_t nnew = 0, ninc = 0;
+  for (size_t i = 0; i < n; ++i) {
+    Hit &h = ordered ? th->hits[th->order[i]] : th->hits[i];
+    const bool was = seen.count(h.name) != 0, inc = (h.flags & P7X_IS_INCLUDED) != 0;
+    if (!was && inc) { h.flags |= P7X_IS_NEW; nnew++; }
+    else if (was && !inc) h.flags |= P7X_IS_DROPPED;
+    if (inc) { if (included && (size_t) ninc < cap) included[ninc] = (int64_t) i; ninc++; }
+  }
+  *nincluded = ninc;
+  return nnew;
 }
 
 // TopHits.merge (plan7.pyx:9172-9276): p7_tophits_Merge (concatenate, re-sort), p7_pipeline_Merge (add the

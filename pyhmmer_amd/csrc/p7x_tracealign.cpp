@@ -36,6 +36,7 @@ struct p7x_msa {
   std::string pp_cons, rf, ss_cons;
   std::vector<std::string> name, acc, desc;   // per row; filled by p7x_tophits_to_msa only
   std::string msa_name;
+  std::vector<uint8_t> codes;          // P7X_MSA_DIGITIZE: the rows as digital codes, [n][alen] (p7x_msa_codes)
 };
 
 namespace {
@@ -550,8 +551,26 @@ int p7x_msa_from_traces(int32_t M, size_t n, const int8_t *st, const int32_t *tk
       }
     }
   }
+  // P7X_MSA_DIGITIZE: the rows once more as digital codes (a residue in either case is its code, both gap characters the
+  // alphabet's gap code), so that a caller that counts over the alignment need not encode the text again
+  if (flags & P7X_MSA_DIGITIZE) {
+    uint8_t lut[256];
+    std::memset(lut, 255, sizeof lut);
+    for (int x = 0; x < abc.Kp; ++x) lut[(unsigned char) std::toupper(abc.sym[x])] = lut[(unsigned char) std::tolower(abc.sym[x])] = (uint8_t) x;
+    lut[(unsigned char) '.'] = lut[(unsigned char) '-'] = (uint8_t) abc.K;
+    msa->codes.resize(n * (size_t) alen);
+    for (size_t idx = 0; idx < n; ++idx)
+      for (int64_t c = 0; c < alen; ++c) msa->codes[idx * (size_t) alen + (size_t) c] = lut[(unsigned char) msa->aseq[idx][(size_t) c]];
+  }
   *out = msa.release();
   return P7X_OK;
+}
+
+int64_t p7x_msa_codes(const p7x_msa *msa, uint8_t *out, size_t nbytes)
+{
+  if (!msa || msa->codes.empty() || debug_opt(OPT_MSA_CODES) == 0) return -1;
+  if (out && nbytes >= msa->codes.size()) std::memcpy(out, msa->codes.data(), msa->codes.size());
+  return (int64_t) msa->codes.size();
 }
 
 int64_t p7x_msa_alen(const p7x_msa *msa) { return msa ? msa->alen : -1; }

@@ -22,7 +22,7 @@ import numpy as np
 
 __all__ = [
     "Alphabet", "Sequence", "TextSequence", "DigitalSequence",
-    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness",
+    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness", "KeyHash",
 ]
 
 _AMINO = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -639,6 +639,7 @@ class MSA:
     def __init__(self, name: Optional[str] = None, description: Optional[str] = None, accession: Optional[str] = None,
                  sequences: Optional[Iterable] = None):
         self.name, self.description, self.accession = name, description, accession
+        self.author: Optional[str] = None               # ``#=GF AU``: the program that made the alignment
         self._names: List[str] = []
         self._rows: List[str] = []
         self._descs: List[str] = []
@@ -769,13 +770,13 @@ class MSA:
         rows = np.arange(n) if sequences is None else mask(sequences, n)
         cols = None if columns is None else mask(columns, alen)
         cut = (lambda s: s) if cols is None else (
-            lambda s: None if s is None else np.frombuffer(s.encode("ascii"), dtype=np.uint8)[cols].tobytes().decode("ascii"))
+            lambda s: s if not s else np.frombuffer(s.encode("ascii"), dtype=np.uint8)[cols].tobytes().decode("ascii"))    # "": a row without a PP line
         pp = self.posterior_probabilities
         out = type(self)._from_rows([self._names[i] for i in rows], [cut(self._rows[i]) for i in rows],
                                     [self._descs[i] for i in rows], [self._accs[i] for i in rows],
                                     None if pp is None else [cut(pp[i]) for i in rows], cut(self.pp_consensus), cut(self.reference),
                                     cut(self.secondary_structure), alphabet=getattr(self, "alphabet", None))
-        out.name, out.description, out.accession = self.name, self.description, self.accession
+        out.name, out.description, out.accession, out.author = self.name, self.description, self.accession, self.author
         if self._weights is not None:
             out._weights = self._weights[rows].copy()
         return out
@@ -805,7 +806,7 @@ class MSA:
         fn(*args, buf, size + 1)
         text = buf.raw[:size].decode()
         # the per-file annotation of a named alignment (`TopHits.to_msa`), where Easel's writer puts it: after the header
-        gf = "".join(f"#=GF {tag} {v}\n" for tag, v in (("ID", self.name), ("AC", self.accession), ("DE", self.description)) if v)
+        gf = "".join(f"#=GF {tag} {v}\n" for tag, v in (("ID", self.name), ("AC", self.accession), ("DE", self.description), ("AU", self.author)) if v)
         head, sep, rest = text.partition("\n")
         return head + sep + gf + rest
 
@@ -1001,13 +1002,80 @@ class DigitalMSA(MSA):
 
     def _codes(self) -> np.ndarray:
         """The alignment as an ``(N, L)`` matrix of digital codes (every gap character is the alphabet's gap code):
-        what ``Builder.build_msa`` counts over."""
+        what ``Builder.build_msa`` counts over.  An alignment that came with its matrix (``TopHits.to_msa`` with
+        ``digitize``: ``p7x_msa_codes``) hands that out, read-only, for as long as its rows are the ones it was made of;
+        every other one encodes its text rows."""
+        kept = getattr(self, "_code_matrix", None)
+        if kept is not None:
+            ax, rows = kept
+            if len(rows) == len(self._rows) and all(a is b for a, b in zip(rows, self._rows)):
+                return ax
+            self._code_matrix = None             # the rows were replaced: the matrix is no longer theirs
+        return self._encode_rows()
+
+    def _keep_codes(self, ax: np.ndarray) -> None:
+        """Keep ``ax`` as the code matrix of the rows as they are now (strings are immutable: the same row objects are the
+        same text).  ``select`` / ``identity_filter`` / ``digitize`` / ``textize`` build new alignments, which start without one."""
+        ax.setflags(write=False)
+        self._code_matrix = (ax, tuple(self._rows))
+
+    def _encode_rows(self) -> np.ndarray:
+        """The text rows encoded: the ``(N, L)`` matrix of ``_codes`` from scratch."""
         n, alen = len(self._rows), len(self)
         out = self.alphabet._lut[np.frombuffer("".join(self._rows).encode("ascii"), dtype=np.uint8)].reshape(n, alen)
         if (out == 255).any():
             i, c = np.argwhere(out == 255)[0]
             raise ValueError(f"Invalid symbol {self._rows[i][c]!r} for alphabet {self.alphabet!r}")
         return out
+
+
+class KeyHash:
+    """A dynamic set of keys that remembers the order they came in (reference ``easel.pyx`` ``KeyHash``; ``ESL_KEYHASH``):
+    ``add`` returns the index of a key, new or not; ``key in kh``; ``kh[key]`` its index (`KeyError` when absent);
+    ``len``; iteration in insertion order; ``clear``; ``copy``.  What ``TopHits.compare_ranking`` keeps the included hits
+    of a jackhmmer round in."""
+
+    __slots__ = ("_index",)
+
+    def __init__(self):
+        self._index: dict = {}
+
+    def add(self, key: str) -> int:
+        if not isinstance(key, str):
+            raise TypeError(f"expected str, found {type(key).__name__}")
+        return self._index.setdefault(key, len(self._index))
+
+    def __contains__(self, key) -> bool:
+        return isinstance(key, str) and key in self._index
+
+    def __getitem__(self, key: str) -> int:
+        if not isinstance(key, str):
+            raise TypeError(f"expected str, found {type(key).__name__}")
+        return self._index[key]
+
+    def __len__(self) -> int:
+        return len(self._index)
+
+    def __iter__(self):
+        return iter(list(self._index))
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, KeyHash):
+            return NotImplemented
+        return list(self._index) == list(other._index)
+
+    def __repr__(self) -> str:
+        return f"<KeyHash of {len(self._index)} keys>"
+
+    def clear(self) -> None:
+        self._index.clear()
+
+    def copy(self) -> "KeyHash":
+        out = KeyHash()
+        out._index = dict(self._index)
+        return out
+
+    __copy__ = copy
 
 
 class MSAFile:

@@ -19,10 +19,12 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Union
 
 from . import _lib
-from .easel import Alphabet, DigitalSequence, DigitalSequenceBlock, SequenceFile
-from .plan7 import HMM, Builder, LongTargetsPipeline, OptimizedProfile, Pipeline, Profile, SequenceDatabase, TopHits
+from .easel import Alphabet, DigitalMSA, DigitalSequence, DigitalSequenceBlock, SequenceFile
+from .plan7 import (HMM, Builder, IterationResult, LongTargetsPipeline, OptimizedProfile, Pipeline, Profile, SequenceDatabase,
+                    TopHits)
 
-__all__ = ["hmmsearch", "phmmer", "hmmscan", "nhmmer", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase", "ReplicatedDatabase"]
+__all__ = ["hmmsearch", "phmmer", "jackhmmer", "hmmscan", "nhmmer", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase",
+           "ReplicatedDatabase"]
 
 
 def make_chunks(block: DigitalSequenceBlock, n: int) -> List[DigitalSequenceBlock]:
@@ -388,6 +390,193 @@ def phmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = 
         if callback is not None:
             callback(query, total)
         yield hits
+
+
+_LAST_ROUNDS: list = []
+
+
+def jackhmmer_rounds() -> list:
+    """Where the rounds of the last (finished) ``jackhmmer`` call of this process spent their time: one dict per round of
+    every batch of queries -- ``batch``, ``round``, ``queries`` (still running), ``search`` (the batched search, wall),
+    ``host_steps`` (sort, ``select_hits``, ``compare_ranking``, ``to_msa`` of every query), ``build_models`` (the counting
+    passes and priors of the alignments that go on) and ``calibrate`` (their one ``p7x_calibrate_batch``), in seconds, and
+    ``pipeline``: `pipeline_stats` of the round's search.  The models a round searches with are counted in the round
+    before it; ``round`` 0 of a batch holds only those of the sequence queries themselves.  With `PIPE_TRACE` every round is
+    also a line on stderr."""
+    return [dict(r) for r in _LAST_ROUNDS]
+
+
+def jackhmmer(queries, sequences, *, max_iterations: Optional[int] = 5, select_hits: Optional[Callable] = None,
+              checkpoints: bool = False, cpus: int = 0, backend: str = "threading", callback: Optional[Callable] = None,
+              builder: Optional[Builder] = None, devices: Optional[Sequence[int]] = None, pipeline_depth: int = 8, batch: int = 0,
+              **options) -> Iterator:
+    """Search protein sequences or HMMs against a sequence database, iteratively; yields, in query order, the
+    `~pyhmmer_amd.plan7.IterationResult` of every query's last round -- or, with ``checkpoints``, the list of all its rounds
+    (reference ``_jackhmmer.py:268-399``).
+
+    A query runs until it converges (a round that includes no new hit and aligns no more rows than the one before) or for
+    ``max_iterations`` rounds (`None`: until it converges).  The reference gives every query to a worker thread that runs
+    its rounds one small search after the other; here the queries travel ``_PHMMER_BATCH`` at a time and advance ROUND BY
+    ROUND: the models of all queries of a batch that are still running go through one pass of the machinery ``hmmsearch``
+    runs its queries through (batched cascades, overlapped host stages); then, per query and in query order, the host
+    steps of `~pyhmmer_amd.plan7.IterativeSearch` (``_advance``: sort, ``select_hits``, ``compare_ranking``, ``to_msa``)
+    run on the caller's thread; then the alignments of the queries that go on are built by one
+    ``Builder.build_msa_block``, which calibrates them in one ``p7x_calibrate_batch``.  The models of the sequence
+    queries of round 1 are built and calibrated together as ``phmmer`` does.  Every query sees what its own
+    ``Pipeline.iterate_seq`` / ``iterate_hmm`` would show it.
+
+    ``sequences``: a ``DigitalSequenceBlock``, any iterable of digital sequences, or a named digital ``SequenceFile``
+    (read as one block).  ``incE`` and ``incdomE`` default to 0.001, jackhmmer's own; the default ``builder`` is
+    ``Builder(alphabet, seed=options.get("seed", 42), architecture="hand")``.  ``callback(query, total)`` is called when
+    a query is finished; an exception from it, from ``select_hits`` or from a query itself (a type that is neither
+    ``DigitalSequence`` nor ``HMM``, another alphabet) surfaces at that query's ``next``, after the results before it.
+    ``cpus`` sets the host threads of the searches' host stage; ``backend`` is checked and otherwise unused."""
+    import itertools
+    from .plan7 import _calibrate
+    if backend not in ("threading", "multiprocessing"):
+        raise ValueError(f"Invalid backend for `jackhmmer`: {backend!r}")
+    options.setdefault("incE", 0.001)
+    options.setdefault("incdomE", 0.001)
+    alphabet: Optional[Alphabet] = options.pop("alphabet", None)
+    if isinstance(queries, (DigitalSequence, HMM)):
+        queries = (queries,)
+    elif not hasattr(queries, "__iter__"):
+        raise TypeError(f"Unsupported query type for `jackhmmer`: {type(queries).__name__}")
+    if isinstance(sequences, SequenceFile):
+        if sequences.name is None:
+            raise ValueError("expected named `SequenceFile` for targets")
+        if not sequences.digital:
+            raise ValueError("expected digital mode `SequenceFile` for targets")
+        targets = sequences.read_block()
+    elif isinstance(sequences, DigitalSequenceBlock):
+        targets = sequences
+    else:
+        seqs = list(sequences)
+        targets = DigitalSequenceBlock(alphabet or (seqs[0].alphabet if seqs else Alphabet.amino()), seqs)
+    alphabet = alphabet or targets.alphabet
+    if builder is None:
+        builder = Builder(alphabet, seed=options.get("seed", 42) or 0, architecture="hand")
+    total = None
+    try:
+        total = len(queries)          # type: ignore[arg-type]
+    except TypeError:
+        pass
+    it = iter(queries)
+    head = list(itertools.islice(it, 1))
+    del _LAST_ROUNDS[:]
+    if not head:
+        return                                   # no query: nothing to yield (and no device needed)
+    if _lib.lib().p7x_device_count() < 1:
+        from .errors import DeviceUnavailable
+        raise DeviceUnavailable("jackhmmer: no HIP device is usable and there is no CPU fallback")
+    db = ShardedDatabase(targets, list(devices) if devices else default_devices())
+    devs = db.devices
+    pipelines = [Pipeline(alphabet, device=d, host_threads=cpus, **options) for d in devs]
+    pipeline, background = pipelines[0], pipelines[0].background
+
+    def begin(query):
+        if isinstance(query, DigitalSequence):
+            return pipeline.iterate_seq(query, targets, builder, select_hits)
+        if isinstance(query, HMM):
+            return pipeline.iterate_hmm(query, targets, builder, select_hits)
+        raise TypeError(f"Unsupported query type for `jackhmmer`: {type(query).__name__}")
+
+    def build_block(searches):
+        """The models of the coming round, {position: (HMM, OptimizedProfile)}, each kind calibrated in one batch; a query
+        whose model cannot be built keeps its error."""
+        out: dict = {}
+        hmms = [(i, s) for i, s in searches if s._source() is None]
+        seqs = [(i, s) for i, s in searches if isinstance(s._source(), DigitalSequence)]
+        msas = [(i, s) for i, s in searches if isinstance(s._source(), DigitalMSA)]
+        for i, s in hmms:
+            out[i] = (s.query, OptimizedProfile(s.query, background, Pipeline.L_HINT))
+        t0 = time.perf_counter()
+        good = []
+        for i, s in seqs:                        # round 1 of the sequence queries: as phmmer builds them
+            try:
+                if len(s.query) > _lib.lib().p7x_max_model_length():
+                    raise ValueError(f"jackhmmer: query {s.query.name!r} has {len(s.query)} residues: model too long for the device kernels")
+                hmm = builder._model(s.query, background)
+                good.append((i, hmm, OptimizedProfile(hmm, background, Pipeline.L_HINT)))
+            except Exception as e:               # noqa: BLE001 - surfaces at the query's position
+                out[i] = e
+        t1 = time.perf_counter()
+        if good:
+            _calibrate([om for _, _, om in good], device=devs[0], seed=builder._calibration_seed())
+        for i, hmm, om in good:
+            out[i] = (hmm, om)
+        times = [t1 - t0, time.perf_counter() - t1]
+        if msas:
+            try:
+                built = builder.build_msa_block([s.msa for _, s in msas], background, device=devs[0])
+                times = [a + b for a, b in zip(times, builder._block_seconds)]
+            except Exception:                    # noqa: BLE001 - one alignment is refused: the others are still built, one by one
+                built = []
+                for _, s in msas:
+                    try:
+                        built.append(builder.build_msa_block([s.msa], background, device=devs[0])[0])
+                    except Exception as e:       # noqa: BLE001
+                        built.append(e)
+            for (i, _), b in zip(msas, built):
+                out[i] = b if isinstance(b, Exception) else (b[0], b[2])
+        return out, times
+
+    for nb, chunk in enumerate(_batches(itertools.chain(head, it), _PHMMER_BATCH)):
+        searches: list = []
+        failed: dict = {}                        # position in the chunk -> the error that ended that query
+        for i, q in enumerate(chunk):
+            try:
+                searches.append(begin(q))
+            except Exception as e:               # noqa: BLE001
+                searches.append(None)
+                failed[i] = e
+        rounds: List[List[IterationResult]] = [[] for _ in chunk]
+        running = [i for i in range(len(chunk)) if i not in failed]
+        models, times = build_block([(i, searches[i]) for i in running])
+        _LAST_ROUNDS.append({"batch": nb, "round": 0, "queries": len(running), "search": 0.0, "host_steps": 0.0, "pipeline": {},
+                             "build_models": times[0], "calibrate": times[1]})       # round 0: the models of the queries themselves
+        nround = 0
+        while running:
+            nround += 1
+            for i in running:
+                if isinstance(models[i], Exception):
+                    failed[i] = models[i]
+            running = [i for i in running if i not in failed]
+            if not running:
+                break
+            t0 = time.perf_counter()
+            found = [hits for _, hits in _run_queries(db, pipelines, [models[i][1] for i in running], pipeline_depth, 0, batch=batch)]
+            stats = pipeline_stats()
+            t1 = time.perf_counter()
+            going = []
+            for i, hits in zip(running, found):
+                hmm = models[i][0]
+                hits.query = hmm
+                try:
+                    result = searches[i]._advance(hmm, hits)
+                except Exception as e:           # noqa: BLE001 - select_hits, or nothing to align: at the query's position
+                    failed[i] = e
+                    continue
+                rounds[i].append(result)
+                if not result.converged and (max_iterations is None or result.iteration < max_iterations):
+                    going.append(i)
+            t2 = time.perf_counter()
+            record = {"batch": nb, "round": nround, "queries": len(running), "search": t1 - t0, "host_steps": t2 - t1,
+                      "pipeline": stats}
+            models, times = build_block([(i, searches[i]) for i in going]) if going else ({}, [0.0, 0.0])
+            record.update(build_models=times[0], calibrate=times[1])
+            _LAST_ROUNDS.append(record)
+            if PIPE_TRACE:
+                sys.stderr.write("[jackhmmer] batch %d round %d: %d queries, search %.1f ms, host steps %.1f ms, build %.1f ms, "
+                                 "calibrate %.1f ms (%d go on)\n" % (nb, nround, len(running), 1e3 * (t1 - t0), 1e3 * (t2 - t1),
+                                                                     1e3 * times[0], 1e3 * times[1], len(going)))
+            running = going
+        for i, q in enumerate(chunk):
+            if i in failed:
+                raise failed[i]
+            if callback is not None:
+                callback(q, total)
+            yield rounds[i] if checkpoints else rounds[i][-1]
 
 
 _FILE_SPAN = 2048          # queries that share one pass over a target file

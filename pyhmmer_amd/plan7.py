@@ -22,15 +22,15 @@ import threading
 import numpy as np
 
 from . import _lib
-from .easel import (Alphabet, DigitalMSA, DigitalSequence, DigitalSequenceBlock, Randomness, SequenceFile, eslAMINO, eslDNA,
-                    eslRNA)
+from .easel import (Alphabet, DigitalMSA, DigitalSequence, DigitalSequenceBlock, KeyHash, Randomness, SequenceFile, eslAMINO,
+                    eslDNA, eslRNA)
 from .errors import (AlphabetMismatch, AllocationError, InvalidParameter, MissingCutoffs,
                      UnexpectedError, status_to_exception)
 
 __all__ = [
     "HMM", "HMMFile", "HMMPressedFile", "Background", "Profile", "OptimizedProfile", "OptimizedProfileBlock", "EvalueParameters", "Cutoffs",
     "Builder", "Pipeline", "LongTargetsPipeline", "SequenceDatabase", "TopHits", "Hit", "Domain", "Domains", "Alignment",
-    "Trace", "Traces", "TraceAligner",
+    "Trace", "Traces", "TraceAligner", "IterationResult", "IterativeSearch",
 ]
 
 CUTOFF_UNSET = -99999.0
@@ -2121,6 +2121,28 @@ class TopHits:
             lib.p7x_msa_destroy(h)
         return msa
 
+    def compare_ranking(self, ranking: "KeyHash") -> int:
+        """Compare the hits to the ranking of the round before (reference ``plan7.pyx:8897-8930``; upstream
+        ``p7_tophits_CompareRanking``): in the list's current order, an included hit whose name ``ranking`` does not hold
+        is flagged ``new`` and counted, a hit that is not included and whose name it holds is flagged ``dropped``
+        (``p7x_tophits_compare_ranking``: the flags live in the list and travel with ``to_bytes``).  ``ranking`` is then
+        emptied and refilled with the names of the included hits in list order -- the same name twice is one key.
+        Returns the number of new hits."""
+        if not isinstance(ranking, KeyHash):
+            raise TypeError(f"expected KeyHash, found {type(ranking).__name__}")
+        keys = list(ranking)
+        n = len(self)
+        ranked = (C.c_char_p * max(len(keys), 1))(*[k.encode() for k in keys])
+        included = np.zeros(max(n, 1), dtype=np.int64)
+        ninc = C.c_int64()
+        n_new = int(_lib.lib().p7x_tophits_compare_ranking(self._handle, ranked, len(keys), included.ctypes.data, n, C.byref(ninc)))
+        if n_new < 0:
+            raise ValueError(_lib.last_error())
+        ranking.clear()
+        for i in included[:int(ninc.value)].tolist():
+            ranking.add(self[i].name)
+        return n_new
+
     def copy(self) -> "TopHits":
         h = _lib.lib().p7x_tophits_clone(self._handle)
         return TopHits(self.query, C.c_void_p(h))
@@ -2393,10 +2415,13 @@ class Builder:
     def build_msa_block(self, msas, background: Background, device: int = 0):
         """The models of several alignments (an extension): each as ``build_msa`` makes it, all calibrated in one batch on
         the device."""
+        t0 = time.perf_counter()
         hmms = [self._model_msa(msa, background, device) for msa in msas]
         oms = [OptimizedProfile(hmm, background, Pipeline.L_HINT) for hmm in hmms]
+        t1 = time.perf_counter()
         if oms:
             _calibrate(oms, device=device, seed=self._calibration_seed())
+        self._block_seconds = (t1 - t0, time.perf_counter() - t1)       # models (counting passes, priors), calibration: diagnostics
         out = []
         for hmm, om in zip(hmms, oms):
             profile = Profile(hmm.M, self.alphabet)
@@ -2580,6 +2605,51 @@ class Pipeline:
         hits._om = om                       # the alignments refer to the profile: keep it alive with the hits
         return hits
 
+    def search_msa(self, query: DigitalMSA, sequences, builder: Optional["Builder"] = None) -> TopHits:
+        """Run the pipeline with a query ALIGNMENT against every target of ``sequences`` (reference
+        ``plan7.pyx:6264-6329``): the model is built by ``builder.build_msa`` (default: ``Builder(alphabet, seed=self.seed)``)
+        and calibrated on this pipeline's device, then searched with as ``search_hmm`` does."""
+        if not isinstance(query, DigitalMSA):
+            raise TypeError(f"Expected DigitalMSA, found {type(query).__name__}")
+        if query.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, query.alphabet)
+        builder = Builder(self.alphabet, seed=self.seed or 0) if builder is None else builder
+        hmm, profile, om = builder.build_msa(query, self.background, device=self.device)
+        hits = self.search_hmm(om, sequences)
+        hits.query = query
+        hits._om = om                       # the alignments refer to the profile: keep it alive with the hits
+        return hits
+
+    def _iterate(self, query, sequences, builder, select_hits) -> "IterativeSearch":
+        if query.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, query.alphabet)
+        if sequences.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, sequences.alphabet)
+        if builder is None:
+            builder = Builder(self.alphabet, seed=self.seed or 0, architecture="hand")
+        elif builder.architecture != "hand":
+            raise ValueError("`iterate_seq` only supports a builder with 'hand' architecture")       # plan7.pyx:6802, 6904: both say iterate_seq
+        return IterativeSearch(self, builder, query, sequences, select_hits)
+
+    def iterate_seq(self, query: DigitalSequence, sequences: DigitalSequenceBlock, builder: Optional["Builder"] = None,
+                    select_hits=None) -> "IterativeSearch":
+        """An iterator over the rounds of ``jackhmmer`` with a query SEQUENCE against ``sequences`` (reference
+        ``plan7.pyx:6806-6906``): every ``next`` searches with the model of the round -- the query's own in round 1, then
+        the one ``builder`` (default: ``Builder(alphabet, seed=self.seed, architecture="hand")``; any other architecture
+        is a `ValueError`) makes of the alignment of the round before -- and returns an `IterationResult`.
+        ``select_hits(hits)``, if given, may change which hits are included before the alignment is made.  jackhmmer's
+        own thresholds are ``Pipeline(incE=0.001, incdomE=0.001)``."""
+        if not isinstance(query, DigitalSequence):
+            raise TypeError(f"Expected DigitalSequence, found {type(query).__name__}")
+        return self._iterate(query, sequences, builder, select_hits)
+
+    def iterate_hmm(self, query: "HMM", sequences: DigitalSequenceBlock, builder: Optional["Builder"] = None,
+                    select_hits=None) -> "IterativeSearch":
+        """As `iterate_seq` with a query HMM, which is the model of round 1 as it stands (reference ``plan7.pyx:6739-6804``)."""
+        if not isinstance(query, HMM):
+            raise TypeError(f"Expected HMM, found {type(query).__name__}")
+        return self._iterate(query, sequences, builder, select_hits)
+
     def scan_seq(self, query: DigitalSequence, optimized_profiles) -> TopHits:
         """Run the pipeline with one query sequence against a collection of profiles (reference
         ``plan7.pyx:6534-6622``).  See :func:`pyhmmer_amd.hmmer.hmmscan` for the batched form."""
@@ -2670,6 +2740,94 @@ class Pipeline:
         return TopHits(label if label is not None else query, out)
 
 
+class IterationResult:
+    """What one round of an `IterativeSearch` gives (reference ``plan7.pyx:4237-4270``): the model searched with, the hits,
+    the alignment of the included ones, whether the search has converged, the number of the round (from 1).  Unpacks in
+    that order."""
+
+    __slots__ = ("hmm", "hits", "msa", "converged", "iteration")
+
+    def __init__(self, hmm: HMM, hits: TopHits, msa: DigitalMSA, converged: bool, iteration: int):
+        self.hmm, self.hits, self.msa, self.converged, self.iteration = hmm, hits, msa, bool(converged), int(iteration)
+
+    def __iter__(self):
+        yield from (self.hmm, self.hits, self.msa, self.converged, self.iteration)
+
+    def __repr__(self) -> str:
+        return f"<IterationResult iteration={self.iteration} converged={self.converged} hits={len(self.hits)}>"
+
+
+class IterativeSearch:
+    """The rounds of ``jackhmmer`` for one query (reference ``plan7.pyx:4273-4389``); made by `Pipeline.iterate_seq` /
+    `Pipeline.iterate_hmm`.  ``next`` runs one round: the model (``_build``), the search (``_search_hmm``), then the host
+    steps from the hits to the next alignment (``_advance``).  The first two are what touches the device; ``hmmer.jackhmmer``
+    does them for a batch of queries at a time and calls ``_advance`` per query."""
+
+    def __init__(self, pipeline: Pipeline, builder: "Builder", query, targets: DigitalSequenceBlock, select_hits=None):
+        self.pipeline = pipeline
+        self.background = pipeline.background
+        self.builder = builder
+        self.query = query
+        self.converged = False
+        self.ranking = KeyHash()
+        self.msa: Optional[DigitalMSA] = None
+        self.iteration = 0
+        self.select_hits = select_hits
+        self.targets = targets
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> IterationResult:
+        if self.converged:
+            raise StopIteration
+        hmm = self._model()
+        return self._advance(hmm, self._search_hmm(hmm))
+
+    def _source(self):
+        """What the model of the coming round is made of: `None` when it is the query HMM itself, else the query sequence
+        (round 1) or the alignment of the round before."""
+        if self.iteration > 0:
+            return self.msa
+        return None if isinstance(self.query, HMM) else self.query
+
+    def _model(self) -> HMM:
+        source = self._source()
+        return self.query if source is None else self._build(source)
+
+    def _build(self, source) -> HMM:
+        """The calibrated model of a query sequence or of an alignment, on the pipeline's device."""
+        if isinstance(source, DigitalMSA):
+            return self.builder.build_msa(source, self.background, device=self.pipeline.device)[0]
+        return self.builder.build(source, self.background, device=self.pipeline.device)[0]
+
+    def _search_hmm(self, hmm: HMM) -> TopHits:
+        return self.pipeline.search_hmm(hmm, self.targets)
+
+    def _advance(self, hmm: HMM, hits: TopHits) -> IterationResult:
+        """From the hits of a round to its result and the alignment the next round is built from (``plan7.pyx:4364-4386``)."""
+        n_prev = 1 if self.iteration == 0 else len(self.msa.names)
+        extra_sequences = extra_traces = None
+        if not isinstance(self.query, HMM):
+            extra_sequences, extra_traces = [self.query], [Trace.from_sequence(self.query)]
+        hits.sort(by="key")
+        if self.select_hits is not None:
+            self.select_hits(hits)
+        n_new = hits.compare_ranking(self.ranking)
+        msa = hits.to_msa(self.pipeline.alphabet, sequences=extra_sequences, traces=extra_traces, all_consensus_cols=True,
+                          digitize=True)
+        msa.name = f"{self.query.name}-i{self.iteration + 1}"
+        msa.description = self.query.description or None
+        msa.accession = self.query.accession or None
+        msa.author = "jackhmmer (pyhmmer_amd)"
+        self.msa = msa
+        if n_new == 0 and len(msa.names) <= n_prev:
+            self.converged = True
+        self.pipeline.clear()
+        self.iteration += 1
+        return IterationResult(hmm, hits, msa, self.converged, self.iteration)
+
+
 class LongTargetsPipeline(Pipeline):
     """An HMMER3 pipeline tuned for long (nucleotide) targets: ``nhmmer`` (reference ``plan7.pyx:6917-7763``).
 
@@ -2718,6 +2876,18 @@ class LongTargetsPipeline(Pipeline):
     def search_seq(self, query, sequences, builder=None):
         """Not offered: a nucleotide sequence query needs the DNA score system of the builder (reference ``plan7.pyx:7420-7480``)."""
         raise NotImplementedError("LongTargetsPipeline.search_seq: there is no DNA score system to build a model from a sequence")
+
+    def search_msa(self, query, sequences, builder=None):
+        """Not offered: a nucleotide alignment query needs the DNA priors of the builder (reference ``plan7.pyx:7480``)."""
+        raise NotImplementedError("LongTargetsPipeline.search_msa: there is no DNA builder to build a model from an alignment")
+
+    def iterate_seq(self, query, sequences, builder=None, select_hits=None):
+        """Not offered: every round needs the DNA builder."""
+        raise NotImplementedError("LongTargetsPipeline.iterate_seq: there is no DNA builder to build the model of a round")
+
+    def iterate_hmm(self, query, sequences, builder=None, select_hits=None):
+        """Not offered: every round after the first needs the DNA builder."""
+        raise NotImplementedError("LongTargetsPipeline.iterate_hmm: there is no DNA builder to build the model of a round")
 
     def _windowed_om(self, query, L: int, cfg) -> "OptimizedProfile":
         """The optimized profile of ``query`` and the two window lengths of the search (reference ``plan7.pyx:7336-7354``):
@@ -3127,6 +3297,11 @@ def _msa_from_handle(h, cls, alphabet):
     msa = cls._from_rows(names, rows, descs, accs, pps if any(pps) else None, pp_cons or None, rf or None, ss or None,
                          alphabet=alphabet)
     msa.name = get(0, 8) or None
+    size = int(lib.p7x_msa_codes(h, None, 0))          # the rows as codes, for an alignment made with the digitize flag
+    if size == nseq * alen and size > 0 and hasattr(msa, "_keep_codes"):
+        ax = np.zeros((nseq, alen), dtype=np.uint8)
+        if lib.p7x_msa_codes(h, ax.ctypes.data, ax.nbytes) == size:
+            msa._keep_codes(ax)
     return msa
 
 
