@@ -488,11 +488,33 @@ int64_t  p7x_tophits_compare_ranking(p7x_tophits *th, const char *const *ranked,
 /* Hit.name / accession / description setters (plan7.pyx:1960-2050): which = 1 name (not NULL), 2 accession, 4 description
  * (NULL clears); pointers handed out earlier by p7x_tophits_get_hit for this hit are invalidated. */
 int      p7x_tophits_set_hit_text(p7x_tophits *th, int64_t i, int which, const char *value);
-/* per-stage device timings of the search that produced th, milliseconds (HIP events):
- * [0] msv + P-value pass [1] bias filter [2] viterbi [3] forward [4] forward rows for survivors [5] backward, then
- * overwritten by host domain definition wall time (including [8]) [6] whole call wall time [7] the MSV kernel alone
- * [8] device rescoring of domain envelopes (wall, with transfers) [9] host: multi-domain regions (overlaps [8])
- * [10] wall time of stage 1 (p7x_search_block_begin) [11] of stage 2 (_finish); [6] = [10] + [11].  n <= 12. */
+/* Timing slots of the search that produced a hit list, milliseconds unless noted; the lower-cased names are the keys of
+ * TopHits.timings_ms, in this order.  A query carries the timings of the batch it travelled in. */
+enum p7x_timing {
+  P7X_MS_MSV = 0,            /* HIP events: MSV kernels and the P-value pass.  Long targets: SSV scan and seeds, wall */
+  P7X_MS_BIAS,               /* HIP events: bias filter and the Viterbi work list.  Long targets: the windows' MSV / bias / Viterbi
+                              * batches on the device, wall */
+  P7X_MS_VITERBI,            /* HIP events: Viterbi filter and its P-value pass */
+  P7X_MS_FORWARD,            /* HIP events: Forward parser (scores only) and its P-value pass */
+  P7X_MS_FWD_ROWS,           /* HIP events: Forward with rows for the survivors (a stage-by-stage batch: their row layout only) */
+  P7X_MS_HOST_DOMAINDEF,     /* the host stage (domain definition), wall, P7X_MS_ENVELOPES included.  Long targets: everything
+                              * after the seeds, wall, P7X_MS_BIAS included */
+  P7X_MS_TOTAL,              /* P7X_MS_STAGE1 + P7X_MS_STAGE2 */
+  P7X_MS_MSV_KERNEL,         /* HIP events: the MSV kernels alone; a batch of several kernel classes: its largest fast-MSV launch.
+                              * Long targets: the SSV scan kernels */
+  P7X_MS_ENVELOPES,          /* device rescoring of domain envelopes: wall from the first launch to the last result, transfers included */
+  P7X_MS_HOST_MULTI,         /* the host's own share of the multi-domain regions (overlaps P7X_MS_ENVELOPES) */
+  P7X_MS_STAGE1,             /* wall of stage 1 (p7x_search_batch_enqueue until _wait returns) */
+  P7X_MS_STAGE2,             /* wall of stage 2 (p7x_search_batch_finish) */
+  P7X_MS_HOST_STAGE_BUSY,    /* max(0, P7X_MS_HOST_DOMAINDEF - P7X_MS_ENSEMBLE_WAIT - P7X_MS_ENVELOPE_WAIT) */
+  P7X_MS_ENSEMBLE_WAIT,      /* of the host stage: waiting for the ensemble kernels */
+  P7X_MS_ENVELOPE_WAIT,      /* of the host stage: waiting for the two envelope rounds */
+  P7X_MS_BATCH_QUERIES,      /* a count: queries of the batch */
+  P7X_MS_MSV_LAUNCH_LANES,   /* a count: lanes (queries) that the launch timed in P7X_MS_MSV_KERNEL covered */
+  P7X_MS_MSV_LAUNCH_NODES,   /* a count: model nodes of those lanes */
+  P7X_MS_COUNT
+};
+/* ms[0 .. min(n, P7X_MS_COUNT)) = the slots above */
 int      p7x_tophits_get_timings(const p7x_tophits *th, double *ms, int n);
 /* how often the two guards acted in the search that produced <th>: targets the F3 guard took back out of the device's
  * survivor list, device envelopes the optimal-accuracy near-tie guard repeated on the host (0 after a merge /
@@ -639,8 +661,15 @@ int p7x_calibration_redraw(int32_t abc_type, const float *bg_f, uint32_t seed, i
  * <skipped> (increasing) when that sample overflows in its turn. */
 int32_t p7x_calibration_draw_of(int32_t kept, const int32_t *skipped, int nskipped);
 /* Raw filter results of the MSV and Viterbi samples -> scores in nats as the filters report them under the length model
- * of 200 residues: sc[2 * P7X_CAL_N], overflow[2 * P7X_CAL_N] (xJ < 0, xC = 32767). */
+ * of 200 residues: sc[2 * P7X_CAL_N], overflow[2 * P7X_CAL_N] (xJ < 0, xC = 32767).  The score of an overflowed sample is
+ * +inf, as the filters report it; p7x_calibration_fit refuses a marked sample before it reads a score. */
 int p7x_calibration_scores(const p7x_oprofile *om, const int32_t *xJ, const int32_t *xC, float *sc, uint8_t *overflow);
+/* Test seam: the length model and the score units of the integer filters as every caller in the library takes them.  For
+ * each target length L[l]: tjb[l] and xw_move[l], the N/C/J move cost in the MSV filter's bytes and the Viterbi filter's
+ * words; usc[l * nJ + i] and vfsc[l * nC + i], the scores in nats of the raw filter results xJ[i] (negative: overflow, +inf)
+ * and xC[i] (32767: overflow, +inf; -32768: -inf) under that length.  nJ / nC may be 0. */
+int p7x_debug_score_units(const p7x_oprofile *om, const int32_t *L, size_t nL, int32_t *tjb, int32_t *xw_move,
+                          const int32_t *xJ, size_t nJ, const int32_t *xC, size_t nC, float *usc, float *vfsc);
 /* The fits (p7_Lambda, p7_MSVMu, p7_ViterbiMu, p7_Tau; esl_gumbel_FitCompleteLoc / FitComplete, tail mass 0.04), in double:
  * sc[3 * P7X_CAL_N] scores in nats (MSV, Viterbi, Forward; they enter as (sc - null1(L)) / ln 2), mh = M times the mean
  * match relative entropy in bits (p7x_oprofile_match_relent), out_evparam[6] in the order of P7X_MMU...  overflow

@@ -301,6 +301,7 @@ _SIGNATURES = {
     "p7x_calibration_redraw": (C.c_int, [C.c_int32, _VP, C.c_uint32, C.c_int, _VP, C.c_int, _VP]),
     "p7x_calibration_draw_of": (C.c_int32, [C.c_int32, _VP, C.c_int]),
     "p7x_calibration_scores": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "p7x_debug_score_units": (C.c_int, [_VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_size_t, _VP, C.c_size_t, _VP, _VP]),
     "p7x_calibration_fit": (C.c_int, [_VP, _VP, C.c_double, _VP]),
     "p7x_oprofile_match_relent": (C.c_double, [_VP]),
     "p7x_calibrate_batch": (C.c_int, [C.POINTER(_VP), C.c_size_t, C.c_int, C.c_uint32, _VP, _VP]),

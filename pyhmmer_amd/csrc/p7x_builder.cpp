@@ -317,16 +317,25 @@ int p7x_calibration_scores(const p7x_oprofile *om, const int32_t *xJ, const int3
 {
   if (!om || !xJ || !xC || !sc || !overflow) { set_error("p7x_calibration_scores: bad arguments"); return P7X_EINVAL; }
   const Profile &p = om->p;
-  const float pmove = 3.0f / ((float) kCalL[0] + 3.0f);
-  const uint8_t tjb = unbiased_byteify(p.scale_b, logf(pmove));
-  const int16_t xwm = wordify(p.scale_w, logf(3.0f / ((float) kCalL[1] + 3.0f)));
-  for (int i = 0; i < kCalN; ++i) {
+  const uint8_t tjb = tjb_of(p.scale_b, kCalL[0]);
+  const int16_t xwm = xw_move_of(p.scale_w, kCalL[1]);
+  for (int i = 0; i < kCalN; ++i) {      // (an overflowed sample's score is +inf; p7x_calibration_fit stops at its mark)
     overflow[i] = xJ[i] < 0;
-    float v = ((float) (xJ[i] - tjb) - (float) p.base_b); v /= p.scale_b; v -= 3.0;
-    sc[i] = v;
+    sc[i] = msv_score_nats(xJ[i], tjb, p.base_b, p.scale_b);
     overflow[kCalN + i] = xC[i] >= 32767;
-    if (xC[i] > -32768) { float w = (float) xC[i] + (float) xwm - (float) p.base_w; w /= p.scale_w; w -= 3.0; sc[kCalN + i] = w; }
-    else sc[kCalN + i] = -INFINITY;
+    sc[kCalN + i] = vit_score_nats(xC[i], xwm, p.base_w, p.scale_w);
+  }
+  return P7X_OK;
+}
+
+int p7x_debug_score_units(const p7x_oprofile *om, const int32_t *L, size_t nL, int32_t *tjb, int32_t *xw_move, const int32_t *xJ, size_t nJ, const int32_t *xC, size_t nC, float *usc, float *vfsc)
+{
+  if (!om || !L || !tjb || !xw_move || (nJ && (!xJ || !usc)) || (nC && (!xC || !vfsc))) { set_error("p7x_debug_score_units: bad arguments"); return P7X_EINVAL; }
+  const Profile &p = om->p;
+  for (size_t l = 0; l < nL; ++l) {
+    tjb[l] = tjb_of(p.scale_b, L[l]); xw_move[l] = xw_move_of(p.scale_w, L[l]);
+    for (size_t i = 0; i < nJ; ++i) usc[l * nJ + i] = msv_score_nats(xJ[i], tjb[l], p.base_b, p.scale_b);
+    for (size_t i = 0; i < nC; ++i) vfsc[l * nC + i] = vit_score_nats(xC[i], xw_move[l], p.base_w, p.scale_w);
   }
   return P7X_OK;
 }

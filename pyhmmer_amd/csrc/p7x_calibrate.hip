@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(kWsBlock) cal_fwd_kernel(const ArgRef ref, con
   const int lane = threadIdx.x & 63;
   const int s = cal_sample();
   const uint8_t *sq = stream + kCalOffFwd + (size_t) s * L;
-  const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f), ploop = 1.0f - pmove;
+  const float pmove = length_pmove((float) L), ploop = 1.0f - pmove;
   float mm[C], im[C], dm[C];
   ForwardRow<C, unroll_c(C), ForwardRefs<C>> f{{mm, im, dm}};
   f.init(tr, lane, pmove);
@@ -183,8 +183,8 @@ static CalArgs cal_args(const Profile &p, const DevProfile *dp, int32_t *d_out)
   a.M = p.M; a.C = dp->vitC; a.K = p.K;
   a.msv_emis = dp->msvw_emis; a.vit_trans = dp->vit_trans; a.vit_emis = dp->vit_emis; a.fwd_trans = dp->fwd_trans; a.fwd_emis = dp->fwd_emis;
   a.base_b = p.base_b; a.bias_b = p.bias_b; a.tec_b = p.tec_b;
-  a.tjbm = (int) unbiased_byteify(p.scale_b, logf(3.0f / (float) (kCalLmsv + 3))) + (int) p.tbm_b;
-  a.xwm = wordify(p.scale_w, logf((2.0f + 1.0f) / ((float) kCalLvit + 2.0f + 1.0f)));
+  a.tjbm = (int) tjb_of(p.scale_b, kCalLmsv) + (int) p.tbm_b;
+  a.xwm = xw_move_of(p.scale_w, kCalLvit);
   a.base_w = p.base_w; a.xw_e = p.xw[XE][MOVE]; a.ddbound = p.ddbound_w;
   a.xf_e_move = p.xf[XE][MOVE]; a.xf_e_loop = p.xf[XE][LOOP];
   a.out = d_out;

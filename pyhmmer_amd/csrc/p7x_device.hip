@@ -99,9 +99,8 @@ int get_ctx(int device, DeviceCtx **out)
   std::vector<float> n1(kMaxL + 1);
   const float scale_b = 3.0 / kLog2, scale_w = 500.0 / kLog2;
   for (int L = 0; L <= kMaxL; ++L) {
-    tjb[L] = unbiased_byteify(scale_b, logf(3.0f / (float) (L + 3)));
-    const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f);
-    xwm[L] = wordify(scale_w, logf(pmove));
+    tjb[L] = tjb_of(scale_b, L);
+    xwm[L] = xw_move_of(scale_w, L);
     n1[L] = null1_score(L);
   }
   P7X_HIP(hipMalloc(&ctx->lt.tjb, tjb.size()));

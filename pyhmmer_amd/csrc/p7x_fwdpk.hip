@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(256) fwdg_kernel(const ArgRef ref)
           L = a.slot_len[slot];
           sq = a.dsq + a.slot_off[slot];
           i = 0;
-          pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f); ploop = 1.0f - pmove;
+          pmove = length_pmove((float) L); ploop = 1.0f - pmove;
 #pragma unroll
           for (int c = 0; c < C; ++c) mm[c] = im[c] = dm[c] = 0.0f;
           xN = 1.0f; xB = pmove; xJ = 0.0f; xC = 0.0f; totscale = 0.0f;

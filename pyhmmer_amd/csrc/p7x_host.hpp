@@ -145,13 +145,8 @@ struct Hit {                  // P7_HIT, p7_hit.pxd:27-58
 // The searched block as the host sees it: residues of target t are dsq[off[t] .. off[t]+len[t]-1], off[t] >= 1.
 struct HostTargets { int64_t n = 0, nres = 0; const int32_t *len = nullptr; const int64_t *off = nullptr; const uint8_t *dsq = nullptr; };
 
-// counts[4] = n_past_{msv,bias,vit,fwd}; targets[] = indices of the Forward survivors; fwdsc / xmx blocks per survivor.
-int host_finish_search(const p7x_pipeline_cfg &cfg, const p7x_oprofile *om, const HostTargets &tg,
-                       const char *const *names, const char *const *accs, const char *const *descs,
-                       const std::vector<int32_t> &targets, const float *fwdsc,
-                       const float *fwd_xmx, const float *bck_xmx, const int64_t *xmx_off,
-                       const uint64_t *counts, const double *ms, p7x_tophits **out, EnvelopeScorer *scorer = nullptr,
-                       const DeviceRegions *regions = nullptr);
+// targets that passed each filter (p7x_counters::n_past_*), in the order of p7x_postprocess_targets' stage_counts
+enum PastStage { kPastMsv = 0, kPastBias, kPastVit, kPastFwd, kPastStages };
 // One query of a batch as the host stage receives it from the device stage.
 struct FinishItem {
   const p7x_oprofile *om = nullptr;
@@ -160,8 +155,8 @@ struct FinishItem {
   const std::vector<char> *near = nullptr;            // which survivors the first stage saw inside the F3 guard band (empty: none;
                                                       // nullptr: not known, the host stage checks every survivor itself)
   const float *fwd_xmx = nullptr, *bck_xmx = nullptr; const int64_t *xmx_off = nullptr;   // parser rows (when regions == nullptr)
-  uint64_t counts[4] = { 0, 0, 0, 0 };                // n_past_{msv,bias,vit,fwd}
-  const double *ms = nullptr; int nms = 8;            // 0-7 as TopHits.timings_ms; 8-10 (nms >= 11): queries of the batch, lanes and nodes of its largest MSV launch
+  uint64_t n_past[kPastStages] = { 0, 0, 0, 0 };      // by PastStage
+  const double *ms = nullptr;                         // [P7X_MS_COUNT] by p7x_timing: what stage 1 measured (nullptr: nothing)
   const DeviceRegions *regions = nullptr;             // region lists found on the device
   bool device_envelopes = false;                      // single-domain envelopes go to the scorer
 };
@@ -241,8 +236,8 @@ struct p7x_tophits {
   bool q_has_acc = false, q_has_desc = false;
   int M = 0;
   int abc_type = 0;                   // alphabet of the query (P7X_AMINO / _DNA / _RNA; 0: not known), for TopHits.to_msa
-  static constexpr int kMs = 20;
-  double ms[kMs]{};           // see TopHits.timings_ms (plan7.py) for the slots
+  static constexpr int kMs = 20; static_assert(P7X_MS_COUNT <= kMs, "the serialised timing array holds every slot");
+  double ms[kMs]{};           // by p7x_timing (include/p7x.h): P7X_MS_COUNT slots in use; kMs is the serialised length
   bool sorted_by_key = false;
   bool scan_collected = false;        // built by p7x_scan_collect(): one query sequence, hits are models
   std::vector<uint8_t> stage;         // scan mode, per-model result: last filter passed by each target (not serialised)

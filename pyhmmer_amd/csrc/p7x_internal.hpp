@@ -1,9 +1,17 @@
 // p7x_internal.hpp -- shared declarations of libp7x (product code; never includes oracle/).
 #pragma once
 #include "../../include/p7x.h"
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
+
+// functions that device code calls as well: nothing under a plain C++ compiler
+#if defined(__HIPCC__)
+#define P7X_HD __host__ __device__
+#else
+#define P7X_HD
+#endif
 
 namespace p7x {
 
@@ -64,6 +72,35 @@ struct Profile {
 float  sse_expf(float x);                               // Easel esl_sse_expf, one lane
 uint8_t unbiased_byteify(float scale_b, float sc);
 int16_t wordify(float scale_w, float sc);
+
+// ---- the length model and the score units of the integer filters, each written once (host and device code)
+// multihit move probability of N / C / J for a target of L residues, 3 / (L + 3), in upstream's spelling with nj = 1
+// (p7_oprofile_ReconfigRestLength, p7_ReconfigLength)
+P7X_HD inline float length_pmove(float L) { return (2.0f + 1.0f) / (L + 2.0f + 1.0f); }
+// its cost in the MSV filter's bytes (p7_oprofile_ReconfigMSVLength) and the Viterbi filter's words
+inline uint8_t tjb_of(float scale_b, int64_t L) { return unbiased_byteify(scale_b, logf(length_pmove((float) L))); }
+inline int16_t xw_move_of(float scale_w, int64_t L) { return wordify(scale_w, logf(length_pmove((float) L))); }
+// xJ of the MSV filter (negative: it overflowed) -> nats, p7_MSVFilter's last lines.  The quotient is a float below 2^17 in
+// magnitude: upstream's subtraction of 3.0 in double is exact and rounds once, to the float that a float subtraction gives.
+P7X_HD inline float msv_score_nats(int xJ, int tjb, int base_b, float scale_b)
+{
+  if (xJ < 0) return __builtin_inff();
+  float sc = ((float) (xJ - tjb) - (float) base_b);
+  sc /= scale_b;
+  sc -= 3.0;
+  return sc;
+}
+// xC of the Viterbi filter (32767: overflow, -32768: no path) -> nats, p7_ViterbiFilter's last lines
+P7X_HD inline float vit_score_nats(int xC, int xw_move, int base_w, float scale_w)
+{
+  if (xC >= 32767) return __builtin_inff();
+  if (xC <= -32768) return -__builtin_inff();
+  float sc = (float) xC + (float) xw_move - (float) base_w;
+  sc /= scale_w;
+  sc -= 3.0;
+  return sc;
+}
+
 double gumbel_surv(double x, double mu, double lambda);
 double exp_surv(double x, double mu, double lambda);
 double exp_logsurv(double x, double mu, double lambda);

@@ -284,17 +284,8 @@ struct DeviceWindowScorer final : LongTargetWindowScorer {
     (void) L; (void) F1;
     const auto t0 = std::chrono::steady_clock::now();
     const Profile &p = om->p;
-    size_t tot = 1;
-    for (size_t q = 0; q < nw; ++q) tot += (size_t) w[q].length + 1;
-    std::vector<uint8_t> dsq(tot, 255);
-    std::vector<int64_t> off(nw); std::vector<int32_t> len(nw);
-    size_t pos = 1;
-    for (size_t q = 0; q < nw; ++q) {
-      off[q] = (int64_t) pos; len[q] = (int32_t) w[q].length;
-      if (w[q].strand == 0) std::memcpy(dsq.data() + pos, seq1 + w[q].start, (size_t) w[q].length);
-      else for (int64_t r = 0; r < w[q].length; ++r) dsq[pos + (size_t) r] = comp[seq1[w[q].start - r]];
-      pos += (size_t) w[q].length + 1;
-    }
+    std::vector<uint8_t> dsq; std::vector<int64_t> off; std::vector<int32_t> len;
+    pack_windows(seq1, comp, w, nw, dsq, off, len);
     if (db) { p7x_seqdb_destroy(db); db = nullptr; }
     int st = p7x_seqdb_create(device, p.abc_type, dsq.data(), off.data(), len.data(), nw, &db);
     if (st != P7X_OK) return st;
@@ -302,16 +293,9 @@ struct DeviceWindowScorer final : LongTargetWindowScorer {
     st = p7x_filters_batch(om, db, xJ.data(), xC.data(), nullptr, do_bias ? bias.data() : nullptr);
     if (st != P7X_OK) return st;
     for (size_t q = 0; q < nw; ++q) {
-      const int Lw = len[q];
-      const float pm = logf(3.0f / (float) (Lw + 3));
-      float usc;
-      if (xJ[q] < 0) usc = INFINITY;
-      else { const uint8_t tjb = unbiased_byteify(p.scale_b, pm); usc = ((float) (xJ[q] - tjb) - (float) p.base_b); usc /= p.scale_b; usc -= 3.0f; }
-      float vf;
-      if (xC[q] >= 32767) vf = INFINITY;
-      else if (xC[q] > -32768) { vf = (float) xC[q] + (float) wordify(p.scale_w, pm) - (float) p.base_w; vf /= p.scale_w; vf -= 3.0f; }
-      else vf = -INFINITY;
-      sc[q].usc = usc; sc[q].bias_filtersc = do_bias ? bias[q] : 0.0f; sc[q].vfsc = vf; sc[q].have_vit = 1;
+      sc[q].usc = msv_score_nats(xJ[q], tjb_of(p.scale_b, len[q]), p.base_b, p.scale_b);
+      sc[q].vfsc = vit_score_nats(xC[q], xw_move_of(p.scale_w, len[q]), p.base_w, p.scale_w);
+      sc[q].bias_filtersc = do_bias ? bias[q] : 0.0f; sc[q].have_vit = 1;
     }
     ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     nwindows += nw;
@@ -564,10 +548,10 @@ int p7x_search_longtargets(const p7x_pipeline_cfg *cfg, const p7x_oprofile *om, 
   DeviceWindowScorer scorer(om, device, cfg->oa_guard);
   st = longtarget_run_host(*cfg, om, dsq, offsets, lengths, n, names, accs, descs, seeds, out, &scorer);
   if (st == P7X_OK && *out) {
-    (*out)->ms[7] = scan_ms;                                   // the SSV scan kernels (HIP events)
-    (*out)->ms[0] = std::chrono::duration<double, std::milli>(t_host - t_begin).count();      // scan + seeds, wall
-    (*out)->ms[1] = scorer.ms;                                 // window MSV / bias / Viterbi batch on the device, wall
-    (*out)->ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();   // host tail incl. [1]
+    (*out)->ms[P7X_MS_MSV_KERNEL] = scan_ms;                   // (enum p7x_timing, the long-target meanings) the SSV scan kernels (HIP events)
+    (*out)->ms[P7X_MS_MSV] = std::chrono::duration<double, std::milli>(t_host - t_begin).count();      // scan + seeds, wall
+    (*out)->ms[P7X_MS_BIAS] = scorer.ms;                       // window MSV / bias / Viterbi batch on the device, wall
+    (*out)->ms[P7X_MS_HOST_DOMAINDEF] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();   // host tail incl. P7X_MS_BIAS
   }
   return st;
 }

@@ -33,7 +33,7 @@ struct LtLengthModel { uint8_t tjb_b; int16_t xw_move; float nullsc; };
 static float lt_msv(const Profile &p, const uint8_t *dsq, int64_t L)
 {
   const int M = p.M;
-  const int tjb = unbiased_byteify(p.scale_b, logf(3.0f / (float) (L + 3)));
+  const int tjb = tjb_of(p.scale_b, L);
   const int bias = p.bias_b, base = p.base_b, tjbm = tjb + p.tbm_b, tec = p.tec_b;
   std::vector<int> row(M + 1, 0), nxt(M + 1, 0);
   int xJ = 0, xB = std::max(base - tjbm, 0);
@@ -53,10 +53,7 @@ static float lt_msv(const Profile &p, const uint8_t *dsq, int64_t L)
     xB = std::max(std::max(base, xJ) - tjbm, 0);
     row.swap(nxt);
   }
-  float sc = ((float) (xJ - tjb) - (float) p.base_b);
-  sc /= p.scale_b;
-  sc -= 3.0f;
-  return sc;
+  return msv_score_nats(xJ, tjb, p.base_b, p.scale_b);
 }
 
 static inline int16_t sat16(int v) { return (int16_t) std::max(-32768, std::min(32767, v)); }
@@ -64,7 +61,7 @@ static inline int16_t sat16(int v) { return (int16_t) std::max(-32768, std::min(
 // the row score that corresponds to P = F2 for a window of length L with bias-adjusted null score <filtersc>
 static int lt_viterbi_threshold(const Profile &p, int64_t L, float filtersc, double F2)
 {
-  const int16_t xw_move = wordify(p.scale_w, logf(3.0f / (float) (L + 3)));
+  const int16_t xw_move = xw_move_of(p.scale_w, L);
   const double invP = p.evparam[P7X_VMU] - std::log(-1.0 * std::log(1.0 - F2)) / p.evparam[P7X_VLAMBDA];     // esl_gumbel_invsurv
   return (int) std::ceil(((filtersc + (float) (kLog2 * invP) + 3.0) * p.scale_w) - (float) p.xw[XE][MOVE] - (float) xw_move + (float) p.base_w);
 }
@@ -75,7 +72,7 @@ static int lt_viterbi_threshold(const Profile &p, int64_t L, float filtersc, dou
 static void lt_viterbi_longtarget(const Profile &p, const uint8_t *dsq, int64_t L, float filtersc, double F2, std::vector<LtWindow> &out)
 {
   const int M = p.M;
-  const int16_t xw_move = wordify(p.scale_w, logf(3.0f / (float) (L + 3)));
+  const int16_t xw_move = xw_move_of(p.scale_w, L);
   const int16_t xw_e_move = p.xw[XE][MOVE], xw_e_loop = p.xw[XE][LOOP];
   const int sc_thresh = lt_viterbi_threshold(p, L, filtersc, F2);
   auto tw = [&](int t, int k) -> int { return p.tw[(size_t) t * (M + 1) + k]; };
@@ -165,7 +162,7 @@ static void lt_ssv_threshold(const Profile &p, int max_length, double F1, int *s
 {
   const double invP = lt_gumbel_invsurv(F1, p.evparam[P7X_MMU], p.evparam[P7X_MLAMBDA]);
   const float nullsc = null1_score(max_length);
-  const int tjb_b = unbiased_byteify(p.scale_b, logf(3.0f / (float) (max_length + 3)));
+  const int tjb_b = tjb_of(p.scale_b, max_length);
   *sc_thresh = (int) std::ceil(((nullsc + (invP * kLog2) + 3.0) * p.scale_b) + p.base_b + p.tec_b + tjb_b);
   *xB = std::max((int) p.base_b - tjb_b - (int) p.tbm_b, 0);
   *tjb = tjb_b;

@@ -19,6 +19,23 @@
 namespace p7x {
 
 // ---------------------------------------------------------------------------- small per-target kernels
+// Counters of a lane (one query of a batch), in device memory and mirrored to the host (Workspace::h_counts) after the cascade.
+enum LaneCounter {
+  kCtrMsvGroups = 0,          // work counter: 64-target groups taken by the fast (or exact-over-everything) MSV kernel
+  kCtrBias = 1,               // n(list_bias) = targets past MSV
+  kCtrVit = 2,                // n(list_vit)
+  kCtrFwd = 3,                // n(list_fwd) = targets past the Viterbi filter (or excused from it)
+  kCtrFin = 4,                // n(list_fin) = targets past Forward
+  kCtrFwdGroupedWork = 5,     // work counter of the grouped Forward parser
+  kCtrPastBias = 8,           // targets past the bias filter
+  kCtrAmbGroups = 10,         // n(amb_groups()): groups the fast MSV kernel left to the exact one
+  kCtrAmbGroupsTaken = 11,    // work counter of the exact MSV kernel over them
+  kCtrRowsTooSmall = 12,      // flag: the survivors' row buffers were too small for this lane (redone on its own)
+  kCtrVitLong = 13,           // length of the prefix of list_vit that holds the longest targets (wave-per-target Viterbi)
+  kCtrNear = 14,              // n(near_list()): Forward survivors inside the F3 guard band
+  kLaneCounters = 16
+};
+
 struct StageBufs {            // all indexed by slot unless noted
   int16_t *xJ;                // [ngroups*64]
   float *usc, *filtersc, *vfsc, *fwdsc;
@@ -26,8 +43,12 @@ struct StageBufs {            // all indexed by slot unless noted
   float *fwd_by_item;         // [nslots] by Forward work-list position
   int32_t *list_bias, *list_vit, *list_fwd, *list_fin;
   uint8_t *stage;             // [nslots] last filter passed: 1 MSV, 2 bias, 3 Viterbi, 4 Forward (scan mode accounting)
-  int *counters;              // [0] msv groups [1] n_bias(list_bias) [2] n_vit [3] n_fwd [4] n_fin [5..7] work counters
-                              // [8] n_past_bias [9] n_past_vit(reach Forward) [14] Forward survivors inside the F3 guard band
+  int *counters;              // [kLaneCounters], by LaneCounter
+  // Two lists serve twice.  list_bias is free once the bias filter has read it: decide_fwd_kernel lists the survivors
+  // inside the F3 guard band there.  list_fin is free until decide_fwd_kernel writes it: the fast MSV kernel lists its
+  // ambiguous groups there for the exact one.
+  P7X_HD int32_t *near_list() const { return list_bias; }
+  P7X_HD int32_t *amb_groups() const { return list_fin; }
 };
 
 struct StageParams {
@@ -86,13 +107,8 @@ __global__ void decide_msv_kernel(const ArgRef ref)
   if (s < a.nslots) {
     const int L = a.slot_len[s];
     const int xJ = b.xJ[s];
-    float usc;
-    if (xJ < 0) usc = __builtin_inff();
-    else {
-      usc = ((float) (xJ - (int) a.tjb_tab[L]) - (float) p.base_b);
-      usc /= p.scale_b;
-      usc -= 3.0f;
-    }
+    // (asked here as well, so that the table and the profile's constants are read only for a score that exists)
+    const float usc = xJ < 0 ? __builtin_inff() : msv_score_nats(xJ, a.tjb_tab[L], p.base_b, p.scale_b);
     b.usc[s] = usc;
     const float seq_score = (float) ((double) (usc - a.null1_tab[L]) / kLog2);
     // 98 % of the targets end here: the survival function falls with the score, so a score a thousandth of a bit below the
@@ -104,7 +120,7 @@ __global__ void decide_msv_kernel(const ArgRef ref)
     }
     b.stage[s] = take ? 1 : 0;
   }
-  wave_append(&b.counters[1], b.list_bias, take, (int32_t) s);
+  wave_append(&b.counters[kCtrBias], b.list_bias, take, (int32_t) s);
 }
 
 // (float) log((double) x) of a positive normal float, as the reference's scaled Forward takes it at every residue:
@@ -154,7 +170,7 @@ __global__ void bias_kernel(const ArgRef ref)
   for (int z = (int) threadIdx.x; z < 256; z += (int) blockDim.x) s_logtab[z] = a.logtab[z];
   for (int z = (int) threadIdx.x; z < kTabRows * 2; z += (int) blockDim.x) s_eo[z] = eo[z];
   __syncthreads();
-  const int n = b.counters[1];
+  const int n = b.counters[kCtrBias];
   for (int it0 = blockIdx.x * blockDim.x; it0 < n; it0 += gridDim.x * blockDim.x) {     // uniform trip count per wavefront
     const int it = it0 + (int) threadIdx.x;
     bool to_vit = false, to_fwd = false;
@@ -231,10 +247,10 @@ __global__ void bias_kernel(const ArgRef ref)
     to_fwd = pass && !(P > p.F2);
     if (pass) b.stage[s] = to_fwd ? 3 : 2;     // P <= F2 already: the Viterbi filter is skipped and counts as passed
     }
-    wave_count(&b.counters[8], to_vit || to_fwd);
+    wave_count(&b.counters[kCtrPastBias], to_vit || to_fwd);
     // targets for the Viterbi filter are marked stage == 2; their work list is built by vit_compact_* below, in slot
     // order (= by decreasing length), instead of in the order in which the threads here happen to finish
-    wave_append(&b.counters[3], b.list_fwd, to_fwd, s);
+    wave_append(&b.counters[kCtrFwd], b.list_fwd, to_fwd, s);
   }
 }
 
@@ -243,28 +259,21 @@ __global__ void decide_vit_kernel(const ArgRef ref)
 {
   const DecideArgs a = load_args<DecideArgs>(ref);
   const StageBufs &b = a.b; const StageParams &p = a.p;
-  const int n = b.counters[2];
+  const int n = b.counters[kCtrVit];
   for (int it0 = blockIdx.x * blockDim.x; it0 < n; it0 += gridDim.x * blockDim.x) {
     const int it = it0 + (int) threadIdx.x;
     bool take = false; int s = 0;
     if (it < n) {
     s = b.list_vit[it];
     const int L = a.slot_len[s];
-    const int xC = b.xC[it];
-    float vfsc;
-    if (xC >= 32767) vfsc = __builtin_inff();
-    else if (xC > -32768) {
-      vfsc = (float) xC + (float) a.xwmove_tab[L] - (float) p.base_w;
-      vfsc /= p.scale_w;
-      vfsc -= 3.0f;
-    } else vfsc = -__builtin_inff();
+    const float vfsc = vit_score_nats(b.xC[it], a.xwmove_tab[L], p.base_w, p.scale_w);
     b.vfsc[s] = vfsc;
     const float seq_score = (float) ((double) (vfsc - b.filtersc[s]) / kLog2);
     const double P = d_gumbel_surv((double) seq_score, (double) p.vmu, (double) p.vlambda);
     take = !(P > p.F2);
     if (take) b.stage[s] = 3;
     }
-    wave_append(&b.counters[3], b.list_fwd, take, s);
+    wave_append(&b.counters[kCtrFwd], b.list_fwd, take, s);
   }
 }
 
@@ -273,7 +282,7 @@ __global__ void decide_fwd_kernel(const ArgRef ref)
 {
   const DecideArgs a = load_args<DecideArgs>(ref);
   const StageBufs &b = a.b; const StageParams &p = a.p;
-  const int n = b.counters[3];
+  const int n = b.counters[kCtrFwd];
   for (int it0 = blockIdx.x * blockDim.x; it0 < n; it0 += gridDim.x * blockDim.x) {
     const int it = it0 + (int) threadIdx.x;
     bool take = false, near = false; int s = 0;
@@ -287,8 +296,8 @@ __global__ void decide_fwd_kernel(const ArgRef ref)
       near = take && (P > p.F3_near);
       if (take) b.stage[s] = 4;
     }
-    wave_append(&b.counters[4], b.list_fin, take, s);
-    wave_append(&b.counters[14], b.list_bias, near, s);
+    wave_append(&b.counters[kCtrFin], b.list_fin, take, s);
+    wave_append(&b.counters[kCtrNear], b.near_list(), near, s);
   }
 }
 
@@ -296,7 +305,7 @@ __global__ void decide_fwd_kernel(const ArgRef ref)
 // Slots are sorted by decreasing target length, so the list of slots with stage == 2 in slot order is the Viterbi
 // work list sorted by decreasing length: the 8 (or 4) targets that share a wavefront of the packed kernel then have
 // about the same length (a wavefront runs to its longest target), and the longest targets -- the first <long_slots>
-// slots -- form a prefix of the list that goes to the wave-per-target kernel instead (counters[13] = its length).
+// slots -- form a prefix of the list that goes to the wave-per-target kernel instead (kCtrVitLong = its length).
 constexpr int kCompactChunk = 4096;       // slots per block
 struct CompactArgs {
   const uint8_t *stage; int32_t *list; int *chunk_cnt; int *counters;
@@ -363,13 +372,13 @@ __global__ void __launch_bounds__(256) vit_compact_write_kernel(const ArgRef ref
     const int64_t cut = a.long_slots - lo;             // slots of this thread below the cut
     int below = cut >= 16 ? c : (cut <= 0 ? 0 : __popc(mask & ((1u << cut) - 1u)));
     below = (int) wave_sum_i32(below);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&a.counters[13], below);
-    if (threadIdx.x == 0) atomicAdd(&a.counters[13], base_s);
+    if ((threadIdx.x & 63) == 0) atomicAdd(&a.counters[kCtrVitLong], below);
+    if (threadIdx.x == 0) atomicAdd(&a.counters[kCtrVitLong], base_s);
   }
   if (chunk_lo + kCompactChunk >= a.nslots && threadIdx.x == 255) {      // last chunk: the list's length
     const int total = base_s + scan[255];
-    a.counters[2] = total;
-    if (a.long_slots >= a.nslots) a.counters[13] = total;
+    a.counters[kCtrVit] = total;
+    if (a.long_slots >= a.nslots) a.counters[kCtrVitLong] = total;
   }
 }
 
@@ -445,7 +454,7 @@ __global__ void __launch_bounds__(256) regions_kernel(const ArgRef ref)
     const long long off = a.xmx_off[it];
     const float *fx = a.fx + off, *bx = a.bx + off;
     float *tb = a.scratch + off, *te = tb + (L + 1), *tm = te + (L + 1), *pb = tm + (L + 1), *pe = pb + (L + 1);
-    const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f), ploop = 1.0f - pmove;      // multihit, full length
+    const float pmove = length_pmove((float) L), ploop = 1.0f - pmove;      // multihit, full length
     const float scaleproduct = (float) (1.0 / (double) bx[1]);
     for (int i = 1 + lane; i <= L; i += 64) {
       const float *f0 = fx + (size_t) (i - 1) * 6, *f1 = fx + (size_t) i * 6, *b0 = bx + (size_t) (i - 1) * 6, *b1 = bx + (size_t) i * 6;
@@ -519,10 +528,19 @@ struct LaneArgs {
   LayoutArgs lay;
   RegionArgs reg;
 };
-constexpr int kLaneCounters = 16;
-// counters of a lane: [0] msv groups taken [1] n(list_bias) [2] n(list_vit) [3] n(list_fwd) [4] n(list_fin)
-// [5] work counter of the grouped Forward parser [8] n_past_bias [10] ambiguous MSV groups [11] exact-MSV groups taken [12] flag: survivor buffers too small
-// [13] length of the prefix of list_vit that holds the longest targets (wave-per-target Viterbi)
+
+// What the cascade records on the workspace's stream (Workspace::ev); cascade_collect times the pairs.
+enum StageEvent {
+  kEvMsvBegin = 0,            // before the first MSV kernel
+  kEvMsvDecided,              // after decide_msv_kernel
+  kEvBiasDone,                // after the bias filter and the compaction of the Viterbi work list
+  kEvVitDecided,              // after decide_vit_kernel
+  kEvFwdDecided,              // after decide_fwd_kernel
+  kEvRows,                    // class by class: after the survivors' Forward rows; stage by stage: after their row layout
+  kEvRegionsDone,             // after Backward and the region scan
+  kEvMsvKernels,              // after the MSV kernels, before decide_msv_kernel
+  kStageEvents
+};
 
 // A workspace serves a batch of up to <nlanes> queries against a block of up to <cap_slots> targets: per-lane
 // score / list arrays, one row arena shared by the lanes, the lanes' argument records, one stream.
@@ -541,7 +559,7 @@ struct Workspace {
   int64_t fin_cap = 0;
   // one lane at a time, when the shared buffers were too small for it (rare)
   DeviceBuf rt_xmx_off, rt_reg_out, rt_bck_sc; int64_t rt_cap = 0;
-  hipEvent_t ev[8]{};
+  hipEvent_t ev[kStageEvents]{};
   hipEvent_t ev_sync = nullptr;
   hipStream_t stream = nullptr;     // one stream per cascade in flight: concurrent searches overlap on the device
   // The lanes of a batch fall into classes that share every kernel instantiation; each class runs its cascade on its
@@ -746,9 +764,9 @@ static void fill_msv_args(LaneArgs &la, const Profile &p, const DevProfile *dp, 
   a.tab = dp->msv_tab; a.tiles = db->d_tiles; a.grp_off = db->d_grp_off; a.grp_nblk = db->d_grp_nblk;
   a.slot_len = db->d_slot_len; a.tjb_tab = ctx->lt.tjb; a.ngroups = (int) db->ngroups;
   a.base = p.base_b; a.bias = p.bias_b; a.tec = p.tec_b; a.tbm = p.tbm_b;
-  a.counter = &b.counters[0]; a.out_xJ = b.xJ;
-  a.amb_count = &b.counters[10]; a.counter2 = &b.counters[11];
-  a.amb_groups = msv_exact_only() ? nullptr : b.list_fin;     // list_fin is free until the Forward stage
+  a.counter = &b.counters[kCtrMsvGroups]; a.out_xJ = b.xJ;
+  a.amb_count = &b.counters[kCtrAmbGroups]; a.counter2 = &b.counters[kCtrAmbGroupsTaken];
+  a.amb_groups = msv_exact_only() ? nullptr : b.amb_groups();
   a.R = dp->msvR;
   la.msv = a;
   MsvArgs x = a;
@@ -772,6 +790,24 @@ static void fill_vit_args(LaneArgs &la, const Profile &p, const DevProfile *dp, 
   a.xwmove_tab = ctx->lt.xwmove; a.base_w = p.base_w; a.xw_e = p.xw[XE][MOVE]; a.ddbound = p.ddbound_w;
   a.out_xC = out_xC;
   la.vitpk = a;
+}
+
+// what the decision kernels and the bias filter read
+static void fill_decide_args(LaneArgs &la, const Profile &p, const DevProfile *dp, const p7x_seqdb *db, DeviceCtx *ctx, const StageBufs &b, const p7x_pipeline_cfg &cfg)
+{
+  DecideArgs d{};
+  d.b = b; d.p = make_params(p, cfg);
+  d.slot_len = db->d_slot_len; d.tjb_tab = ctx->lt.tjb; d.null1_tab = ctx->lt.null1; d.xwmove_tab = ctx->lt.xwmove; d.logtab = ctx->lt.logtab;
+  d.dsq = db->d_dsq; d.slot_off = db->d_slot_off; d.eo = dp->bias_eo; d.nslots = db->nslots;
+  la.dec = d;
+}
+
+// the Forward parser of the first pass (scores only, by work-list position) over <list>; nullptr: over every slot
+static void fill_fwd_args(LaneArgs &la, const Profile &p, const DevProfile *dp, const p7x_seqdb *db, DeviceCtx *ctx, const StageBufs &b, const int32_t *list, int nlist, const int *nlist_ptr)
+{
+  WaveSeqArgs a = ws_args(p, dp, db, ctx);
+  a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = list; a.nlist = nlist; a.nlist_ptr = nlist_ptr; a.out_sc = b.fwd_by_item;
+  la.fwd = a;
 }
 
 template <class A> static ArgRun<A> lane_run(const Workspace *ws, A LaneArgs::*member, int first, int n)
@@ -873,8 +909,8 @@ struct CascadeOut {
   std::vector<char> near;                 // per survivor: inside the F3 guard band (empty: none)
   bool have_xmx = false;
   std::vector<uint8_t> stage;             // scan mode: last filter passed, per target (caller order)
-  int counts[16]{};
-  double ms[12]{};                        // 0-5 stage events, 6 wall, 7 the MSV launch, 8 queries of the batch, 9 / 10 lanes and nodes of that launch
+  int counts[kLaneCounters]{};            // by LaneCounter
+  double ms[P7X_MS_COUNT]{};              // by p7x_timing: the slots that stage 1 knows
 };
 
 // One batched cascade in flight: the enqueue half queues every kernel of stage 1 for all lanes on the workspace's
@@ -912,8 +948,8 @@ struct PackArgs {
 __global__ void pack_survivors_kernel(const PackArgs a)
 {
   const int l = (int) blockIdx.y;
-  const int nfin = a.counters[(size_t) l * kLaneCounters + 4];
-  if (a.counters[(size_t) l * kLaneCounters + 12] != 0) return;          // flagged lane: redone on its own
+  const int nfin = a.counters[(size_t) l * kLaneCounters + kCtrFin];
+  if (a.counters[(size_t) l * kLaneCounters + kCtrRowsTooSmall] != 0) return;          // flagged lane: redone on its own
   const int32_t *reg_l = a.reg_out + (size_t) l * (size_t) a.cap * (kRegionCap * 3 + 2);
   for (int i = (int) (blockIdx.x * blockDim.x + threadIdx.x); i < nfin; i += (int) (gridDim.x * blockDim.x)) {
     const int64_t t = (int64_t) a.lane_base[l] + i;
@@ -943,7 +979,7 @@ __global__ void __launch_bounds__(1024) lane_base_kernel(const int *counters, in
 {
   __shared__ int part[1024];
   const int t = (int) threadIdx.x, per = (nq + 1023) / 1024;
-  auto count_of = [&](int l) { return counters[(size_t) l * kLaneCounters + 12] != 0 ? 0 : counters[(size_t) l * kLaneCounters + 4]; };
+  auto count_of = [&](int l) { return counters[(size_t) l * kLaneCounters + kCtrRowsTooSmall] != 0 ? 0 : counters[(size_t) l * kLaneCounters + kCtrFin]; };
   int sum = 0;
   for (int i = 0; i < per; ++i) { const int l = t * per + i; if (l < nq) sum += count_of(l); }
   part[t] = sum;
@@ -1024,20 +1060,20 @@ static int fill_survivor_args(CascadeRun &r, int first, int n, bool retry, int n
     int32_t *reg_out = retry ? ws->rt_reg_out.as<int32_t>() : ws->reg_out.as<int32_t>() + (size_t) l * cap * (kRegionCap * 3 + 2);
     float *bck_sc = retry ? ws->rt_bck_sc.as<float>() : ws->bck_sc.as<float>() + (size_t) l * cap;
     LayoutArgs lay{};
-    lay.nfin_ptr = &b.counters[4]; lay.list_fin = b.list_fin; lay.slot_len = db->d_slot_len; lay.xmx_off = xmx_off;
+    lay.nfin_ptr = &b.counters[kCtrFin]; lay.list_fin = b.list_fin; lay.slot_len = db->d_slot_len; lay.xmx_off = xmx_off;
     lay.cap_items = (int) std::min<int64_t>(cap, INT_MAX); lay.cap_floats = (long long) ws->xmx_cap; lay.cursor = ws->cursor();
-    lay.flags = &b.counters[12];
+    lay.flags = &b.counters[kCtrRowsTooSmall];
     la.lay = lay;
     WaveSeqArgs a = ws_args(p, dp, db, ctx);
-    a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = b.list_fin; a.nlist_ptr = &b.counters[4];
+    a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = b.list_fin; a.nlist_ptr = &b.counters[kCtrFin];
     a.nlist = (int) std::min<int64_t>(cap, retry ? std::max(nfin, 1) : std::max(r.est_fin, 1));          // sizes the grid only
     a.out_sc = b.fwd_by_item; a.xmx = ws->xmx_f.as<float>(); a.xmx_off = xmx_off;
-    a.abort_flag = &b.counters[12];
+    a.abort_flag = &b.counters[kCtrRowsTooSmall];
     la.rows = a;
     a.out_sc = bck_sc; a.xmx = ws->xmx_b.as<float>(); a.fwd_xmx = ws->xmx_f.as<float>();
     la.bck = a;
     RegionArgs ra{};
-    ra.nitems_ptr = &b.counters[4]; ra.abort_flag = &b.counters[12];
+    ra.nitems_ptr = &b.counters[kCtrFin]; ra.abort_flag = &b.counters[kCtrRowsTooSmall];
     ra.list = b.list_fin; ra.slot_len = db->d_slot_len; ra.fx = ws->xmx_f.as<float>(); ra.bx = ws->xmx_b.as<float>();
     ra.xmx_off = xmx_off; ra.scratch = ws->xmx_s.as<float>();
     ra.out_regs = reg_out; ra.out_n = reg_out + (size_t) cap * kRegionCap * 3;
@@ -1059,7 +1095,7 @@ static int launch_survivor_passes(CascadeRun &r, const LaneClass &c, hipStream_t
   hipLaunchKernelGGL(layout_rows_kernel, dim3(1, (unsigned) c.n), dim3(256), 0, s, lane_run(ws, &LaneArgs::lay, c.first, c.n).ref());
   P7X_HIP(hipGetLastError());
   if ((st = class_wave(c, ws, &LaneArgs::rows, false, ctx, s)) != P7X_OK) return st;
-  if (record_events) P7X_HIP(hipEventRecord(ws->ev[5], s));
+  if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvRows], s));
   if ((st = class_wave(c, ws, &LaneArgs::bck, true, ctx, s)) != P7X_OK) return st;
   {   // posterior decoding of the special states and the region scan, on the rows where they are
     const int64_t items = std::min<int64_t>(cap, retry ? cap : std::max(r.est_fin, 1));
@@ -1067,7 +1103,7 @@ static int launch_survivor_passes(CascadeRun &r, const LaneClass &c, hipStream_t
     hipLaunchKernelGGL(regions_kernel, dim3(gx, (unsigned) c.n), dim3(256), 0, s, lane_run(ws, &LaneArgs::reg, c.first, c.n).ref());
     P7X_HIP(hipGetLastError());
   }
-  if (record_events) P7X_HIP(hipEventRecord(ws->ev[6], s));
+  if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvRegionsDone], s));
   return P7X_OK;
 }
 
@@ -1090,19 +1126,19 @@ static int class_cascade(CascadeRun &r, const LaneClass &c, hipStream_t s, bool 
     // down); small blocks -- a scan's query sequences -- leave most of the device idle and run side by side instead
     std::lock_guard<std::mutex> lk(ctx->msv_mu);          // enqueue order == chain order
     if (ctx->msv_last >= 0) P7X_HIP(hipStreamWaitEvent(s, ctx->msv_done[ctx->msv_last], 0));
-    if (record_events) P7X_HIP(hipEventRecord(ws->ev[0], s));
+    if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvMsvBegin], s));
     if ((st = class_msv(c, r.lm, ctx, ws, s)) != P7X_OK) return st;
-    if (record_events) P7X_HIP(hipEventRecord(ws->ev[7], s));
+    if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvMsvKernels], s));
     ctx->msv_last = (ctx->msv_last + 1) & 1;
     P7X_HIP(hipEventRecord(ctx->msv_done[ctx->msv_last], s));
   } else {
-    if (record_events) P7X_HIP(hipEventRecord(ws->ev[0], s));
+    if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvMsvBegin], s));
     if ((st = msv_by_tier ? class_msv_rest(c, r.lm, ctx, ws, s) : class_msv(c, r.lm, ctx, ws, s)) != P7X_OK) return st;
-    if (record_events) P7X_HIP(hipEventRecord(ws->ev[7], s));
+    if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvMsvKernels], s));
   }
   const ArgRef dec = lane_run(ws, &LaneArgs::dec, c.first, c.n).ref();
   hipLaunchKernelGGL(decide_msv_kernel, dim3((unsigned) ((db->nslots + 255) / 256), (unsigned) c.n), dim3(256), 0, s, dec);
-  if (record_events) P7X_HIP(hipEventRecord(ws->ev[1], s));
+  if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvMsvDecided], s));
   hipLaunchKernelGGL(bias_kernel, dim3(lane_grid((r.est_bias + 63) / 64, ctx->num_cu * 4, c.n), (unsigned) c.n), dim3(64), 0, s, dec);
   {   // the Viterbi work list, in slot order
     const unsigned nchunks = (unsigned) ((db->nslots + kCompactChunk - 1) / kCompactChunk);
@@ -1110,22 +1146,30 @@ static int class_cascade(CascadeRun &r, const LaneClass &c, hipStream_t s, bool 
     hipLaunchKernelGGL(vit_compact_count_kernel, dim3(nchunks, (unsigned) c.n), dim3(256), 0, s, cmp);
     hipLaunchKernelGGL(vit_compact_write_kernel, dim3(nchunks, (unsigned) c.n), dim3(256), 0, s, cmp);
   }
-  if (record_events) P7X_HIP(hipEventRecord(ws->ev[2], s));
+  if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvBiasDone], s));
   if ((st = class_viterbi(c, r.lm, ctx, ws, s)) != P7X_OK) return st;
   hipLaunchKernelGGL(decide_vit_kernel, dim3(lane_grid((r.est_vit + 255) / 256, ctx->num_cu, c.n), (unsigned) c.n), dim3(256), 0, s, dec);
-  if (record_events) P7X_HIP(hipEventRecord(ws->ev[3], s));
+  if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvVitDecided], s));
   if (fwd_grouped(db) && r.lm[c.first].dp->fwdgT > 0) {       // scores only: several targets per wavefront (p7x_fwdpk.hip)
     if ((st = fwdg_launch(lane_run(ws, &LaneArgs::fwd, c.first, c.n), ctx->num_cu, s)) != P7X_OK) return st;
   } else if ((st = class_wave(c, ws, &LaneArgs::fwd, false, ctx, s)) != P7X_OK) return st;
   hipLaunchKernelGGL(decide_fwd_kernel, dim3(lane_grid((r.est_fwd + 255) / 256, ctx->num_cu, c.n), (unsigned) c.n), dim3(256), 0, s, dec);
   P7X_HIP(hipGetLastError());
-  if (record_events) P7X_HIP(hipEventRecord(ws->ev[4], s));
+  if (record_events) P7X_HIP(hipEventRecord(ws->ev[kEvFwdDecided], s));
   return launch_survivor_passes(r, c, s, false, record_events);
 }
 
-struct CascadeRun;
-struct PackLayout;
 static int queue_pack(CascadeRun &r, const PackLayout &lay, int64_t T, const int32_t *lane_base, int max_nfin);
+
+// Item n = 0, 1, 2 ... of a deal over the workspace's stream (turn 0) and its first <nside> side streams (turn k: side[k - 1]),
+// back and forth: in one direction the first stream would get the heaviest item of every round.
+static int deal_turn(size_t n, int nside)
+{
+  constexpr size_t kStreams = Workspace::kSide + 1;
+  int turn = (int) (n % kStreams);
+  if ((n / kStreams) & 1) turn = (int) kStreams - 1 - turn;
+  return std::min(turn, nside);
+}
 
 // The batch stage by stage instead of class by class (multi-class batches against a small block: the scan orientation).
 // The kernels that are the same for every lane -- the MSV decision, the bias filter, the compaction of the Viterbi work
@@ -1139,12 +1183,9 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
 {
   const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get(); DeviceCtx *ctx = r.ctx;
   const int nq = (int) r.lm.size();
-  constexpr int kStreams = Workspace::kSide + 1;
   int st = P7X_OK;
   auto stream_of = [&](size_t n) -> hipStream_t {
-    int turn = (int) (n % (size_t) kStreams);
-    if ((n / (size_t) kStreams) & 1) turn = kStreams - 1 - turn;
-    turn = std::min(turn, nside);
+    const int turn = deal_turn(n, nside);
     return turn == 0 ? s : ws->side[turn - 1];
   };
   auto fork = [&]() -> int {
@@ -1171,7 +1212,7 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
   };
   // stage A: MSV.  The tier launches are already queued (run_of); what is left per class is the exact kernel over the
   // ambiguous groups, or the whole MSV stage of the classes outside the tiers (wave-per-target kernels).
-  P7X_HIP(hipEventRecord(ws->ev[0], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvMsvBegin], s));
   for (size_t n = 0; n < classes.size(); ++n) {
     const size_t c = classes.size() - 1 - n;
     hipStream_t cs = stream_of(n);
@@ -1179,10 +1220,10 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
     if ((st = run_of[c] >= 0 ? class_msv_rest(classes[c], r.lm, ctx, ws, cs) : class_msv(classes[c], r.lm, ctx, ws, cs)) != P7X_OK) return st;
   }
   if ((st = join()) != P7X_OK) return st;
-  P7X_HIP(hipEventRecord(ws->ev[7], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvMsvKernels], s));
   const ArgRef dec = lane_run(ws, &LaneArgs::dec, 0, nq).ref();
   hipLaunchKernelGGL(decide_msv_kernel, dim3((unsigned) ((db->nslots + 255) / 256), (unsigned) nq), dim3(256), 0, s, dec);
-  P7X_HIP(hipEventRecord(ws->ev[1], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvMsvDecided], s));
   hipLaunchKernelGGL(bias_kernel, dim3(lane_grid((r.est_bias + 63) / 64, ctx->num_cu * 4, nq), (unsigned) nq), dim3(64), 0, s, dec);
   {
     const unsigned nchunks = (unsigned) ((db->nslots + kCompactChunk - 1) / kCompactChunk);
@@ -1191,7 +1232,7 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
     hipLaunchKernelGGL(vit_compact_write_kernel, dim3(nchunks, (unsigned) nq), dim3(256), 0, s, cmp);
   }
   P7X_HIP(hipGetLastError());
-  P7X_HIP(hipEventRecord(ws->ev[2], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvBiasDone], s));
   // stage B: Viterbi, by (kernel instantiation, nodes per lane)
   if ((st = fork()) != P7X_OK) return st;
   {
@@ -1201,7 +1242,7 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
   }
   if ((st = join()) != P7X_OK) return st;
   hipLaunchKernelGGL(decide_vit_kernel, dim3(lane_grid((r.est_vit + 255) / 256, ctx->num_cu, nq), (unsigned) nq), dim3(256), 0, s, dec);
-  P7X_HIP(hipEventRecord(ws->ev[3], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvVitDecided], s));
   // stage C: the Forward parser, by nodes per lane
   const std::vector<LaneClass> by_C = runs_by([](const LaneClass &a, const LaneClass &b) { return a.C == b.C; });
   if ((st = fork()) != P7X_OK) return st;
@@ -1209,10 +1250,10 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
     if ((st = class_wave(by_C[n], ws, &LaneArgs::fwd, false, ctx, stream_of(n))) != P7X_OK) return st;
   if ((st = join()) != P7X_OK) return st;
   hipLaunchKernelGGL(decide_fwd_kernel, dim3(lane_grid((r.est_fwd + 255) / 256, ctx->num_cu, nq), (unsigned) nq), dim3(256), 0, s, dec);
-  P7X_HIP(hipEventRecord(ws->ev[4], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvFwdDecided], s));
   hipLaunchKernelGGL(layout_rows_kernel, dim3(1, (unsigned) nq), dim3(256), 0, s, lane_run(ws, &LaneArgs::lay, 0, nq).ref());
   P7X_HIP(hipGetLastError());
-  P7X_HIP(hipEventRecord(ws->ev[5], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvRows], s));
   // stage D: Forward rows and Backward of the survivors, by nodes per lane; then the region scan of all lanes
   if ((st = fork()) != P7X_OK) return st;
   for (size_t n = 0; n < by_C.size(); ++n) {
@@ -1227,7 +1268,7 @@ static int staged_cascade(CascadeRun &r, const std::vector<LaneClass> &classes, 
     hipLaunchKernelGGL(regions_kernel, dim3(gx, (unsigned) nq), dim3(256), 0, s, lane_run(ws, &LaneArgs::reg, 0, nq).ref());
     P7X_HIP(hipGetLastError());
   }
-  P7X_HIP(hipEventRecord(ws->ev[6], s));
+  P7X_HIP(hipEventRecord(ws->ev[kEvRegionsDone], s));
   return P7X_OK;
 }
 
@@ -1288,24 +1329,17 @@ static int cascade_enqueue(CascadeRun &r)
     const Profile &p = r.lm[l].om->p; const DevProfile *dp = r.lm[l].dp;
     LaneArgs &la = ws->h_args.as<LaneArgs>()[l];
     const StageBufs b = ws->lane_bufs(l);
-    DecideArgs d{};
-    d.b = b; d.p = make_params(p, cfg);
-    d.slot_len = db->d_slot_len; d.tjb_tab = ctx->lt.tjb; d.null1_tab = ctx->lt.null1; d.xwmove_tab = ctx->lt.xwmove; d.logtab = ctx->lt.logtab;
-    d.dsq = db->d_dsq; d.slot_off = db->d_slot_off; d.eo = dp->bias_eo; d.nslots = db->nslots;
-    la.dec = d;
+    fill_decide_args(la, p, dp, db, ctx, b, cfg);
     fill_msv_args(la, p, dp, db, ctx, b, nlong_of[(size_t) l]);
     const int64_t vit_long = vit_long_of[(size_t) l];
-    fill_vit_args(la, p, dp, db, ctx, b.list_vit, est.vit, &b.counters[2], b.xC,
-                  vit_long > 0 ? &b.counters[13] : nullptr, (int) std::min<int64_t>(vit_long, (int64_t) est.vit));
+    fill_vit_args(la, p, dp, db, ctx, b.list_vit, est.vit, &b.counters[kCtrVit], b.xC,
+                  vit_long > 0 ? &b.counters[kCtrVitLong] : nullptr, (int) std::min<int64_t>(vit_long, (int64_t) est.vit));
     CompactArgs ca{};
     ca.stage = b.stage; ca.list = b.list_vit; ca.chunk_cnt = ws->chunk_cnt.as<int>() + (size_t) l * (size_t) ws->chunks_per_lane; ca.counters = b.counters;
     ca.nslots = db->nslots; ca.long_slots = vit_long;
     la.cmp = ca;
-    WaveSeqArgs a = ws_args(p, dp, db, ctx);
-    a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = b.list_fwd; a.nlist = est.fwd; a.nlist_ptr = &b.counters[3];
-    a.out_sc = b.fwd_by_item;
-    if (fwd_grouped(db) && dp->fwdgT > 0) { a.trans = dp->fwdg_trans; a.emis = dp->fwdg_emis; a.C = dp->fwdgT * 256 + dp->fwdgC; a.counter = &b.counters[5]; }
-    la.fwd = a;
+    fill_fwd_args(la, p, dp, db, ctx, b, b.list_fwd, est.fwd, &b.counters[kCtrFwd]);
+    if (fwd_grouped(db) && dp->fwdgT > 0) { WaveSeqArgs &a = la.fwd; a.trans = dp->fwdg_trans; a.emis = dp->fwdg_emis; a.C = dp->fwdgT * 256 + dp->fwdgC; a.counter = &b.counters[kCtrFwdGroupedWork]; }
   }
   tick("args");
   if ((st = fill_survivor_args(r, 0, nq, false, 0)) != P7X_OK) return st;
@@ -1374,9 +1408,7 @@ static int cascade_enqueue(CascadeRun &r)
       // the classes of the longest models first (their chains are the longest: started last they would end the batch alone),
       // dealt back and forth (in one direction the first stream would get the heaviest class of every round)
       const size_t c = classes.size() - 1 - n;
-      constexpr int kStreams = Workspace::kSide + 1;
-      int turn = (int) (n % (size_t) kStreams);
-      if ((n / (size_t) kStreams) & 1) turn = kStreams - 1 - turn;
+      const int turn = deal_turn(n, nside);
       hipStream_t cs = turn == 0 ? s : ws->side[turn - 1];
       if (few) cs = nstreams == 1 ? s : (split || (n & 1) ? partner : s);
       if (run_of[c] >= 0) P7X_HIP(hipStreamWaitEvent(cs, ws->ev_tier[run_of[c]], 0));
@@ -1421,7 +1453,7 @@ static int retry_survivor_passes(CascadeRun &r, int l, int nfin)
   int st = fill_survivor_args(r, l, 1, true, nfin);
   if (st != P7X_OK) return st;
   if ((st = upload_args(ws, l, 1, s)) != P7X_OK) return st;
-  P7X_HIP(hipMemsetAsync(&ws->lane_bufs(l).counters[12], 0, 4, s));
+  P7X_HIP(hipMemsetAsync(&ws->lane_bufs(l).counters[kCtrRowsTooSmall], 0, 4, s));
   P7X_HIP(hipMemsetAsync(ws->cursor(), 0, 8, s));
   LaneClass c; c.first = l; c.n = 1; c.C = r.lm[l].dp->vitC;
   if ((st = launch_survivor_passes(r, c, s, true, false)) != P7X_OK) return st;
@@ -1434,7 +1466,7 @@ static int retry_survivor_passes(CascadeRun &r, int l, int nfin)
 static int fetch_lane(CascadeRun &r, int l, bool retry, CascadeOut &out)
 {
   Workspace *ws = r.ws.get(); hipStream_t s = ws->stream;
-  const int nfin = out.counts[4];
+  const int nfin = out.counts[kCtrFin];
   out.fin_slots.resize(nfin); out.fwdsc.resize(nfin); out.xmx_off.resize(nfin);
   if (nfin == 0) return P7X_OK;
   const StageBufs b = ws->lane_bufs(l);
@@ -1456,7 +1488,7 @@ static int fetch_lane(CascadeRun &r, int l, bool retry, CascadeOut &out)
 static int fetch_lane_rows(CascadeRun &r, CascadeOut &out)
 {
   const p7x_seqdb *db = r.db; Workspace *ws = r.ws.get();
-  const int nfin = out.counts[4];
+  const int nfin = out.counts[kCtrFin];
   if (nfin == 0) return P7X_OK;
   bool overflow = r.cfg.host_regions != 0;
   for (int i = 0; i < nfin; ++i) if (out.reg_n[i] == -2) overflow = true;
@@ -1536,8 +1568,8 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
     CascadeOut &out = outs[(size_t) r.query_of[l]];
     std::memcpy(out.counts, ws->h_counts.as<int>() + (size_t) l * kLaneCounters, kLaneCounters * 4);
     lane_base[(size_t) l] = (int32_t) T;
-    if (out.counts[12] != 0) flagged.push_back(l);
-    else { T += out.counts[4]; max_nfin = std::max(max_nfin, out.counts[4]); }
+    if (out.counts[kCtrRowsTooSmall] != 0) flagged.push_back(l);
+    else { T += out.counts[kCtrFin]; max_nfin = std::max(max_nfin, out.counts[kCtrFin]); }
   }
   // One gather kernel and one copy bring the survivors' results of all lanes to the host (pinned): the region scan's
   // own array has kRegionCap slots per survivor, and lane-by-lane or strided copies of it were most of this call.
@@ -1563,8 +1595,8 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
     const int64_t *h_off = reinterpret_cast<const int64_t *>(ph + o_off);
     for (int l = 0; l < nq; ++l) {
       CascadeOut &out = outs[(size_t) r.query_of[l]];
-      const int nfin = out.counts[4];
-      if (out.counts[12] != 0 || nfin == 0) continue;
+      const int nfin = out.counts[kCtrFin];
+      if (out.counts[kCtrRowsTooSmall] != 0 || nfin == 0) continue;
       const size_t base = (size_t) lane_base[(size_t) l];
       out.fin_slots.assign(h_fin + base, h_fin + base + nfin);
       out.fwdsc.assign(h_fwd + base, h_fwd + base + nfin);
@@ -1590,16 +1622,16 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
   }
   for (int l = 0; l < nq; ++l) {
     CascadeOut &out = outs[(size_t) r.query_of[l]];
-    if (out.counts[12] == 0 && (st = fetch_lane_rows(r, out)) != P7X_OK) return st;
+    if (out.counts[kCtrRowsTooSmall] == 0 && (st = fetch_lane_rows(r, out)) != P7X_OK) return st;
   }
   // lanes whose survivors did not fit (more of them than the shared buffers were sized for): one at a time, with
   // buffers sized for the lane's own count
   for (int l : flagged) {
     CascadeOut &out = outs[(size_t) r.query_of[l]];
-    if ((st = retry_survivor_passes(r, l, out.counts[4])) != P7X_OK) return st;
+    if ((st = retry_survivor_passes(r, l, out.counts[kCtrFin])) != P7X_OK) return st;
     P7X_HIP(hipEventSynchronize(ws->ev_sync));
     std::memcpy(out.counts, ws->h_counts.as<int>() + (size_t) l * kLaneCounters, kLaneCounters * 4);
-    if (out.counts[12] != 0) { set_error("row buffers could not be sized for the Forward survivors"); return P7X_EMEM; }
+    if (out.counts[kCtrRowsTooSmall] != 0) { set_error("row buffers could not be sized for the Forward survivors"); return P7X_EMEM; }
     if ((st = fetch_lane(r, l, true, out)) != P7X_OK) return st;
     P7X_HIP(hipEventRecord(ws->ev_sync, s)); P7X_HIP(hipEventSynchronize(ws->ev_sync));
     if ((st = fetch_lane_rows(r, out)) != P7X_OK) return st;
@@ -1607,32 +1639,37 @@ static int cascade_collect(CascadeRun &r, std::vector<CascadeOut> &outs)
   // Forward survivors inside the F3 guard band (normally none): their slots, matched against the survivor list
   for (int l = 0; l < nq; ++l) {
     CascadeOut &out = outs[(size_t) r.query_of[l]];
-    const int nnear = out.counts[14];
+    const int nnear = out.counts[kCtrNear];
     if (nnear <= 0 || out.fin_slots.empty()) continue;
     std::vector<int32_t> slots((size_t) nnear);
-    P7X_HIP(hipMemcpy(slots.data(), ws->lane_bufs(l).list_bias, (size_t) nnear * 4, hipMemcpyDeviceToHost));
+    P7X_HIP(hipMemcpy(slots.data(), ws->lane_bufs(l).near_list(), (size_t) nnear * 4, hipMemcpyDeviceToHost));
     std::sort(slots.begin(), slots.end());
     out.near.assign(out.fin_slots.size(), 0);
     for (size_t i = 0; i < out.fin_slots.size(); ++i) out.near[i] = std::binary_search(slots.begin(), slots.end(), out.fin_slots[i]) ? 1 : 0;
   }
-  double ms[12]{};
-  for (int i = 0; i < 6; ++i) { float t = 0; (void) hipEventElapsedTime(&t, ws->ev[i], ws->ev[i + 1]); ms[i] = t; }
-  { float t = 0; (void) hipEventElapsedTime(&t, ws->ev[0], ws->ev[7]); ms[7] = t; }
-  ms[8] = nq; ms[9] = nq; ms[10] = 0.0;
-  for (int l = 0; l < nq; ++l) ms[10] += r.lm[l].om->p.M;
+  auto between = [&](StageEvent a, StageEvent b) { float t = 0; (void) hipEventElapsedTime(&t, ws->ev[a], ws->ev[b]); return (double) t; };
+  double ms[P7X_MS_COUNT]{};
+  ms[P7X_MS_MSV] = between(kEvMsvBegin, kEvMsvDecided); ms[P7X_MS_BIAS] = between(kEvMsvDecided, kEvBiasDone);
+  ms[P7X_MS_VITERBI] = between(kEvBiasDone, kEvVitDecided); ms[P7X_MS_FORWARD] = between(kEvVitDecided, kEvFwdDecided);
+  ms[P7X_MS_FWD_ROWS] = between(kEvFwdDecided, kEvRows); ms[P7X_MS_MSV_KERNEL] = between(kEvMsvBegin, kEvMsvKernels);
+  ms[P7X_MS_BATCH_QUERIES] = nq; ms[P7X_MS_MSV_LAUNCH_LANES] = nq;
+  for (int l = 0; l < nq; ++l) ms[P7X_MS_MSV_LAUNCH_NODES] += r.lm[l].om->p.M;
   if (ws->ntier_runs > 0) {
-    // a batch of several classes: slot 7 is the batch's LARGEST fast-MSV launch (a tier of register tiles, p7x_msv.hip), by its own events
+    // a batch of several classes: the batch's LARGEST fast-MSV launch (a tier of register tiles, p7x_msv.hip), by its own events
     int big = 0;
     for (int k = 1; k < ws->ntier_runs; ++k) if (ws->tier_nodes[k] > ws->tier_nodes[big]) big = k;
     float t = 0;
-    if (hipEventElapsedTime(&t, ws->ev_tier0[big], ws->ev_tier[big]) == hipSuccess) { ms[7] = t; ms[9] = ws->tier_lanes[big]; ms[10] = (double) ws->tier_nodes[big]; }
+    if (hipEventElapsedTime(&t, ws->ev_tier0[big], ws->ev_tier[big]) == hipSuccess) {
+      ms[P7X_MS_MSV_KERNEL] = t; ms[P7X_MS_MSV_LAUNCH_LANES] = ws->tier_lanes[big]; ms[P7X_MS_MSV_LAUNCH_NODES] = (double) ws->tier_nodes[big];
+    }
   }
   if (debug) {
     const auto tc2 = std::chrono::steady_clock::now();
-    long long nfin_tot = 0; for (const CascadeOut &o : outs) nfin_tot += o.counts[4];
+    long long nfin_tot = 0; for (const CascadeOut &o : outs) nfin_tot += o.counts[kCtrFin];
     std::fprintf(stderr, "[collect] nq %d survivors %lld flagged %zu: device wait %.2f fetch %.2f ms; events msv %.2f bias %.2f vit %.2f fwd %.2f rows %.2f bck+regions %.2f (msv kernel %.2f)\n",
                  nq, nfin_tot, flagged.size(), std::chrono::duration<double, std::milli>(tc1 - tc0).count(),
-                 std::chrono::duration<double, std::milli>(tc2 - tc1).count(), ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[7]);
+                 std::chrono::duration<double, std::milli>(tc2 - tc1).count(), ms[P7X_MS_MSV], ms[P7X_MS_BIAS], ms[P7X_MS_VITERBI], ms[P7X_MS_FORWARD],
+                 ms[P7X_MS_FWD_ROWS], between(kEvRows, kEvRegionsDone), ms[P7X_MS_MSV_KERNEL]);
   }
   for (int l = 0; l < nq; ++l) {
     CascadeOut &out = outs[(size_t) r.query_of[l]];
@@ -1688,26 +1725,18 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
   const StageBufs b = ws->lane_bufs(0);
   LaneArgs &la = ws->h_args.as<LaneArgs>()[0];
   p7x_pipeline_cfg cfg; p7x_pipeline_cfg_default(&cfg);
-  {
-    DecideArgs d{};
-    d.b = b; d.p = make_params(p, cfg);
-    d.p.F1 = 2.0; d.p.F2 = 2.0;              // the bias pass below scores every target
-    d.slot_len = db->d_slot_len; d.tjb_tab = ctx->lt.tjb; d.null1_tab = ctx->lt.null1; d.xwmove_tab = ctx->lt.xwmove; d.logtab = ctx->lt.logtab;
-    d.dsq = db->d_dsq; d.slot_off = db->d_slot_off; d.eo = dp->bias_eo; d.nslots = ns;
-    la.dec = d;
-    fill_msv_args(la, p, dp, db, ctx, b, cls.nlong);
-    if (dp->vitC > 0) {
-      fill_vit_args(la, p, dp, db, ctx, nullptr, (int) ns, nullptr, b.xC, cls.vit_long > 0 ? &b.counters[13] : nullptr, (int) cls.vit_long);
-      WaveSeqArgs a = ws_args(p, dp, db, ctx);
-      a.trans = dp->fwd_trans; a.emis = dp->fwd_emis; a.list = nullptr; a.nlist = (int) ns; a.nlist_ptr = nullptr; a.out_sc = b.fwd_by_item;
-      la.fwd = a;
-    }
+  fill_decide_args(la, p, dp, db, ctx, b, cfg);
+  la.dec.p.F1 = 2.0; la.dec.p.F2 = 2.0;      // the bias pass below scores every target
+  fill_msv_args(la, p, dp, db, ctx, b, cls.nlong);
+  if (dp->vitC > 0) {                        // the work lists are every slot
+    fill_vit_args(la, p, dp, db, ctx, nullptr, (int) ns, nullptr, b.xC, cls.vit_long > 0 ? &b.counters[kCtrVitLong] : nullptr, (int) cls.vit_long);
+    fill_fwd_args(la, p, dp, db, ctx, b, nullptr, (int) ns, nullptr);
   }
   if ((st = upload_args(ws, 0, 1, s)) != P7X_OK) return st;
   P7X_HIP(hipMemsetAsync(ws->counters.as<int>(), 0, ws->counters_bytes(), s));
   if (cls.vit_long > 0) {     // the work list is every slot: its long prefix is the database's (the cascade counts it on the device)
     const int nlong = (int) cls.vit_long;
-    P7X_HIP(hipMemcpyAsync(&b.counters[13], &nlong, 4, hipMemcpyHostToDevice, s));
+    P7X_HIP(hipMemcpyAsync(&b.counters[kCtrVitLong], &nlong, 4, hipMemcpyHostToDevice, s));
   }
   if (xJ) {
     if ((st = class_msv(cls, lm, ctx, ws, s)) != P7X_OK) return st;
@@ -1739,7 +1768,7 @@ int p7x_filters_batch(const p7x_oprofile *om, const p7x_seqdb *db, int32_t *xJ, 
     for (int64_t i = 0; i < ns; ++i) ident[i] = (int32_t) i;
     P7X_HIP(hipMemcpyAsync(b.list_bias, ident.data(), (size_t) ns * 4, hipMemcpyHostToDevice, s));
     int cnt = (int) ns;
-    P7X_HIP(hipMemcpyAsync(&b.counters[1], &cnt, 4, hipMemcpyHostToDevice, s));
+    P7X_HIP(hipMemcpyAsync(&b.counters[kCtrBias], &cnt, 4, hipMemcpyHostToDevice, s));
     std::vector<float> zero((size_t) ns, 0.0f);
     P7X_HIP(hipMemcpyAsync(b.usc, zero.data(), (size_t) ns * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(bias_kernel, dim3(ctx->num_cu * 4), dim3(64), 0, s, lane_run(ws, &LaneArgs::dec, 0, 1).ref());
@@ -1778,20 +1807,14 @@ static int one_seq(const p7x_oprofile *om, int device, const uint8_t *dsq, int32
   if (which == 0) {
     st = p7x_filters_batch(om, db, &xJ, nullptr, nullptr, nullptr);
     if (st == P7X_OK) {
-      if (xJ < 0) { *sc = INFINITY; st = P7X_ERANGE; }
-      else {
-        const uint8_t tjb = unbiased_byteify(p.scale_b, logf(3.0f / (float) (L + 3)));
-        float v = ((float) (xJ - tjb) - (float) p.base_b); v /= p.scale_b; v -= 3.0; *sc = v;
-      }
+      *sc = msv_score_nats(xJ, tjb_of(p.scale_b, L), p.base_b, p.scale_b);
+      if (xJ < 0) st = P7X_ERANGE;
     }
   } else if (which == 1) {
     st = p7x_filters_batch(om, db, nullptr, &xC, nullptr, nullptr);
     if (st == P7X_OK) {
-      if (xC >= 32767) { *sc = INFINITY; st = P7X_ERANGE; }
-      else if (xC > -32768) {
-        const float pmove = 3.0f / ((float) L + 3.0f);
-        float v = (float) xC + (float) wordify(p.scale_w, logf(pmove)) - (float) p.base_w; v /= p.scale_w; v -= 3.0; *sc = v;
-      } else *sc = -INFINITY;
+      *sc = vit_score_nats(xC, xw_move_of(p.scale_w, L), p.base_w, p.scale_w);
+      if (xC >= 32767) st = P7X_ERANGE;
     }
   } else if (which == 2) {
     st = p7x_filters_batch(om, db, nullptr, nullptr, &f, nullptr);
@@ -1910,7 +1933,7 @@ int p7x_search_batch_raw(const p7x_pipeline_cfg *cfg, const p7x_oprofile *const 
       for (int64_t sl = 0; sl < ns; ++sl) xJ[q * (size_t) n + (size_t) db->h_order[sl]] = hj[(size_t) sl];
     }
     if (xC) {
-      const int nv = counters[2];
+      const int nv = counters[kCtrVit];
       P7X_HIP(hipMemcpy(hl.data(), b.list_vit, (size_t) nv * 4, hipMemcpyDeviceToHost));
       P7X_HIP(hipMemcpy(hc.data(), b.xC, (size_t) nv * 4, hipMemcpyDeviceToHost));
       for (int it = 0; it < nv; ++it) xC[q * (size_t) n + (size_t) db->h_order[hl[(size_t) it]]] = hc[(size_t) it];
@@ -1938,7 +1961,7 @@ int p7x_search_block_wait(p7x_pending *pd)
   if (st != P7X_OK) return st;
   pd->waited = true;
   const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pd->t0).count();   // stage 1 wall
-  for (auto &c : pd->co) c.ms[6] = wall;
+  for (auto &c : pd->co) c.ms[P7X_MS_STAGE1] = wall;
   return P7X_OK;
 }
 
@@ -1980,8 +2003,9 @@ int p7x_search_batch_finish(p7x_pending *pd, const char *const *names, const cha
     it.om = om; it.targets = &targets[q]; it.fwdsc = co.fwdsc.data();
     it.near = &co.near;
     it.fwd_xmx = co.fwd_xmx.data(); it.bck_xmx = co.bck_xmx.data(); it.xmx_off = co.xmx_off.data();
-    it.counts[0] = (uint64_t) co.counts[1]; it.counts[1] = (uint64_t) co.counts[8]; it.counts[2] = (uint64_t) co.counts[3]; it.counts[3] = (uint64_t) co.counts[4];
-    it.ms = co.ms; it.nms = 12;
+    it.n_past[kPastMsv] = (uint64_t) co.counts[kCtrBias]; it.n_past[kPastBias] = (uint64_t) co.counts[kCtrPastBias];
+    it.n_past[kPastVit] = (uint64_t) co.counts[kCtrFwd]; it.n_past[kPastFwd] = (uint64_t) co.counts[kCtrFin];
+    it.ms = co.ms;
     if (!co.have_xmx && !targets[q].empty()) { dr[q].n = co.reg_n.data(); dr[q].regs = co.regs.data(); dr[q].nexpected = co.nexpected.data(); dr[q].cap = kRegionCap;
       dr[q].start = co.reg_start.empty() ? nullptr : co.reg_start.data(); it.regions = &dr[q]; }
     it.device_envelopes = !pd->cfg.host_envelopes && !targets[q].empty();
@@ -2007,7 +2031,7 @@ int p7x_search_batch_finish(p7x_pending *pd, const char *const *names, const cha
   for (size_t q = 0; q < nq; ++q) {
     CascadeOut &co = pd->co[q];
     if (!co.stage.empty()) tophits_set_stages(outs[q], std::move(co.stage));
-    tophits_set_total_ms(outs[q], co.ms[6], stage2);
+    tophits_set_total_ms(outs[q], co.ms[P7X_MS_STAGE1], stage2);
   }
   if (debug_opt(OPT_TRACE_FINISH) > 0) {       // where the call spends its time, the teardown of its helpers included
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

@@ -197,7 +197,7 @@ static void convert_msv(Profile &p)
       p.rb[(size_t) x * (M + 1) + k] = biased_byteify(p.scale_b, p.bias_b, p.msc[(size_t) x * (M + 1) + k]);
   p.tbm_b = unbiased_byteify(p.scale_b, logf(2.0f / ((float) M * (float) (M + 1))));
   p.tec_b = unbiased_byteify(p.scale_b, logf(0.5f));
-  p.tjb_b = unbiased_byteify(p.scale_b, logf(3.0f / (float) (p.L + 3)));
+  p.tjb_b = tjb_of(p.scale_b, p.L);
 }
 
 static void convert_viterbi(Profile &p)

@@ -293,10 +293,9 @@ int host_finish_batch(const p7x_pipeline_cfg &cfg_in, const std::vector<FinishIt
     th->M = p.M; th->abc_type = p.abc_type;
     th->ctr.nmodels = 1; th->ctr.nnodes = (uint64_t) p.M;
     th->ctr.nseqs = (uint64_t) tg.n; th->ctr.nres = (uint64_t) tg.nres;
-    th->ctr.n_past_msv = it.counts[0]; th->ctr.n_past_bias = it.counts[1];
-    th->ctr.n_past_vit = it.counts[2]; th->ctr.n_past_fwd = it.counts[3];
-    if (it.ms) for (int i = 0; i < 8; ++i) th->ms[i] = it.ms[i];
-    if (it.ms && it.nms >= 11) { th->ms[15] = it.ms[8]; th->ms[16] = it.ms[9]; th->ms[17] = it.ms[10]; }
+    th->ctr.n_past_msv = it.n_past[kPastMsv]; th->ctr.n_past_bias = it.n_past[kPastBias];
+    th->ctr.n_past_vit = it.n_past[kPastVit]; th->ctr.n_past_fwd = it.n_past[kPastFwd];
+    if (it.ms) std::copy(it.ms, it.ms + P7X_MS_COUNT, th->ms);
     ths[(size_t) q] = std::move(th);
     first[(size_t) q + 1] = first[(size_t) q] + (int) it.targets->size();
   }
@@ -541,9 +540,9 @@ int host_finish_batch(const p7x_pipeline_cfg &cfg_in, const std::vector<FinishIt
       if (descs && descs[t] && descs[t][0]) { h.desc = descs[t]; h.has_desc = true; }
       th.hits.push_back(std::move(h));
     }
-    th.ms[5] = ms_host; th.ms[8] = ms_env; th.ms[9] = ms_multi;
-    th.ms[13] = ms_ens_wait; th.ms[14] = ms_env_wait;
-    th.ms[12] = std::max(0.0, ms_host - ms_ens_wait - ms_env_wait);       // the host stage without its waits for the device
+    th.ms[P7X_MS_HOST_DOMAINDEF] = ms_host; th.ms[P7X_MS_ENVELOPES] = ms_env; th.ms[P7X_MS_HOST_MULTI] = ms_multi;
+    th.ms[P7X_MS_ENSEMBLE_WAIT] = ms_ens_wait; th.ms[P7X_MS_ENVELOPE_WAIT] = ms_env_wait;
+    th.ms[P7X_MS_HOST_STAGE_BUSY] = std::max(0.0, ms_host - ms_ens_wait - ms_env_wait);       // the host stage without its waits for the device
     // Z for E-values: number of targets seen (p7_pli_NewSeq), unless set by the caller
     if (th.cfg.Z_setby == P7X_ZSETBY_NTARGETS) th.cfg.Z = (double) tg.n;
     sort_by_key(th);
@@ -553,21 +552,6 @@ int host_finish_batch(const p7x_pipeline_cfg &cfg_in, const std::vector<FinishIt
   if (debug) std::fprintf(stderr, "[finish] nq %d survivors %d threads %d:%s ms\n", nq, S, nthreads, dbg.c_str());
   for (int q = 0; q < nq; ++q) outs[q] = ths[(size_t) q].release();
   return P7X_OK;
-}
-
-int host_finish_search(const p7x_pipeline_cfg &cfg_in, const p7x_oprofile *om, const HostTargets &tg,
-                       const char *const *names, const char *const *accs, const char *const *descs,
-                       const std::vector<int32_t> &tgt, const float *fwdsc,
-                       const float *fwd_xmx, const float *bck_xmx, const int64_t *xmx_off,
-                       const uint64_t *counts, const double *ms, p7x_tophits **out, EnvelopeScorer *scorer,
-                       const DeviceRegions *dregs)
-{
-  std::vector<FinishItem> items(1);
-  FinishItem &it = items[0];
-  it.om = om; it.targets = &tgt; it.fwdsc = fwdsc; it.fwd_xmx = fwd_xmx; it.bck_xmx = bck_xmx; it.xmx_off = xmx_off;
-  for (int i = 0; i < 4; ++i) it.counts[i] = counts[i];
-  it.ms = ms; it.regions = dregs; it.device_envelopes = scorer != nullptr;
-  return host_finish_batch(cfg_in, items, tg, names, accs, descs, out, scorer);
 }
 
 void tophits_sort_by_key(p7x_tophits &th) { sort_by_key(th); }
@@ -585,7 +569,7 @@ void tophits_set_stages(p7x_tophits *th, std::vector<uint8_t> &&stage)
   th->stage = std::move(stage);
   for (int32_t t : th->guard_dropped) if ((size_t) t < th->stage.size() && th->stage[(size_t) t] == 4) th->stage[(size_t) t] = 3;
 }
-void tophits_set_total_ms(p7x_tophits *th, double stage1, double stage2) { th->ms[6] = stage1 + stage2; th->ms[10] = stage1; th->ms[11] = stage2; }
+void tophits_set_total_ms(p7x_tophits *th, double stage1, double stage2) { th->ms[P7X_MS_TOTAL] = stage1 + stage2; th->ms[P7X_MS_STAGE1] = stage1; th->ms[P7X_MS_STAGE2] = stage2; }
 
 } // namespace p7x
 
@@ -606,9 +590,11 @@ int p7x_postprocess_targets(const p7x_pipeline_cfg *cfg, const p7x_oprofile *om,
   tg.n = (int64_t) n; tg.len = lengths; tg.off = offsets; tg.dsq = dsq;
   for (size_t t = 0; t < n; ++t) tg.nres += lengths[t];
   std::vector<int32_t> targets(surv, surv + nsurv);
-  const uint64_t zero[4] = {0, 0, 0, 0};
-  return host_finish_search(*cfg, om, tg, names, accs, descs, targets, fwdsc, fwd_xmx, bck_xmx, xmx_off,
-                            stage_counts ? stage_counts : zero, nullptr, out);
+  std::vector<FinishItem> items(1);
+  FinishItem &it = items[0];
+  it.om = om; it.targets = &targets; it.fwdsc = fwdsc; it.fwd_xmx = fwd_xmx; it.bck_xmx = bck_xmx; it.xmx_off = xmx_off;
+  if (stage_counts) std::copy(stage_counts, stage_counts + kPastStages, it.n_past);
+  return host_finish_batch(*cfg, items, tg, names, accs, descs, out);
 }
 
 void p7x_tophits_destroy(p7x_tophits *th) { delete th; }
@@ -1181,7 +1167,7 @@ int p7x_tophits_get_ensemble_counts(const p7x_tophits *th, int64_t *sampled_on_d
 int p7x_tophits_get_timings(const p7x_tophits *th, double *ms, int n)
 {
   if (!th || !ms) return P7X_EINVAL;
-  for (int i = 0; i < n && i < p7x_tophits::kMs; ++i) ms[i] = th->ms[i];
+  for (int i = 0; i < n && i < P7X_MS_COUNT; ++i) ms[i] = th->ms[i];
   return P7X_OK;
 }
 

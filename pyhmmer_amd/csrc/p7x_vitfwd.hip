@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(kWsBlock) fwd_kernel(const ArgRef ref)
     const int L = item.L;
     const uint8_t *sq = item.sq;
     float *xo = a.xmx ? a.xmx + a.xmx_off[it] : nullptr;
-    const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f), ploop = 1.0f - pmove;
+    const float pmove = length_pmove((float) L), ploop = 1.0f - pmove;
 
     float mm[C], im[C], dm[C];
     ForwardRow<C, unroll_c(C), ForwardRefs<C>> f{{mm, im, dm}};
@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(kWsBlock) bck_kernel(const ArgRef ref)
     const uint8_t *sq = item.sq;
     const float *fx = a.fwd_xmx + a.xmx_off[it];
     float *xo = a.xmx + a.xmx_off[it];
-    const float pmove = (2.0f + 1.0f) / ((float) L + 2.0f + 1.0f), ploop = 1.0f - pmove;
+    const float pmove = length_pmove((float) L), ploop = 1.0f - pmove;
 
     // per-lane constants: transitions leaving node (c) and entering node (c+1) [next node]
     float tmd[C], tdd[C], tmi[C], tii[C];       // leaving node k

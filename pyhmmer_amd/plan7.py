@@ -36,6 +36,11 @@ __all__ = [
 CUTOFF_UNSET = -99999.0
 EVPARAM_UNSET = -99999.0
 
+# keys of TopHits.timings_ms: enum p7x_timing of include/p7x.h (P7X_MS_*), lower-cased, in its order
+TIMING_NAMES = ("msv", "bias", "viterbi", "forward", "fwd_rows", "host_domaindef", "total", "msv_kernel",
+                "envelopes", "host_multi", "stage1", "stage2", "host_stage_busy", "ensemble_wait", "envelope_wait",
+                "batch_queries", "msv_launch_lanes", "msv_launch_nodes")
+
 # p7_AminoFrequencies (upstream p7_bg.c; cross-checked against the insert emissions of
 # tests/golden/hmms/Thioesterase.hmm) -- SURVEY.md section 8 row a5
 _AMINO_BG = np.array([
@@ -1871,13 +1876,12 @@ class TopHits:
         ``ensemble_wait`` and ``envelope_wait`` were spent waiting for the device (ensemble kernels; the two envelope rounds)
         and ``host_stage_busy`` is the rest -- what the host itself did (region bookkeeping, clustering, alignments, hit
         lists).  ``host_multi``: the host's own share of the multi-domain regions (clustering; sampling too when the ensembles
-        stay on the host).  ``envelopes``: wall from the first launch of the stage to the last result."""
-        buf = (C.c_double * 20)()
-        _lib.lib().p7x_tophits_get_timings(self._handle, buf, 20)
-        return dict(zip(("msv", "bias", "viterbi", "forward", "fwd_rows", "host_domaindef", "total", "msv_kernel",
-                         "envelopes", "host_multi", "stage1", "stage2", "host_stage_busy", "ensemble_wait", "envelope_wait",
-                         # msv_kernel is the batch's largest fast-MSV launch by its own HIP events; what it covered:
-                         "batch_queries", "msv_launch_lanes", "msv_launch_nodes"), buf))
+        stay on the host).  ``envelopes``: wall from the first launch of the stage to the last result.  ``msv_kernel``: the
+        batch's largest fast-MSV launch by its own HIP events; ``msv_launch_lanes`` and ``msv_launch_nodes`` are what it
+        covered.  Every slot is documented at ``enum p7x_timing`` (``include/p7x.h``)."""
+        buf = (C.c_double * len(TIMING_NAMES))()
+        _lib.lib().p7x_tophits_get_timings(self._handle, buf, len(TIMING_NAMES))
+        return dict(zip(TIMING_NAMES, buf))
 
     @property
     def reported(self):
