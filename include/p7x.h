@@ -364,6 +364,22 @@ int64_t p7x_debug_ssv_merge_rows(int Q16, size_t n, const int64_t *pos, const in
 int  p7x_debug_set_option(const char *name, int value);
 int  p7x_debug_ensemble(const p7x_oprofile *om, const p7x_seqdb *db, int64_t target, int32_t i, int32_t j, uint32_t seed,
                         int use_device, int32_t *ndom, int32_t *dom, int32_t dom_cap, float *n2, int32_t *status);
+/* Test seams of the float64 reference of the ensembles (tests/ensemble_reference.py); additions, the ABI number stays.
+ * p7x_debug_ensemble_traces: host code, no device.  The 200 paths the host twin samples from region i..j of dsq1[1..L] in
+ *   the "host_order" option's summation order: step s of sample t is st / k / pos[off201[t] + s] (p7T_* state code, node,
+ *   residue inside the region; S first, T last), *nsteps steps in all (at most step_cap are written); dom / ndom / n2 as
+ *   p7x_debug_ensemble returns them for the host twin.
+ * p7x_debug_ensemble_records: the choice records of every cell and row of the region (p7x_choice.hpp: 8 words per cell,
+ *   cells[(j-i+2)][M+1][8], and 8 per row, rows[j-i+2][8]) as the Forward fill kernel wrote them (use_device != 0: the region
+ *   of target <target> of <db>; what the kernel leaves untouched -- row 0 of the cells, node 0 -- is zero) or as the host
+ *   twin forms them for every cell (use_device == 0; with db == NULL the region is of dsq1[1..L], else dsq1 / L are ignored).
+ *   md (may be NULL): md[(j-i+2)][M+1][2], the scaled Forward values M(r, k) and D(r, k) kept beside the records: the E
+ *   state chooses among them, each times the row's factor (float) (1 / xE) in word 4 of its row record. */
+int  p7x_debug_ensemble_traces(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t i, int32_t j, uint32_t seed,
+                               int8_t *st, int32_t *k, int32_t *pos, int64_t step_cap, int32_t *off201, int64_t *nsteps,
+                               int32_t *ndom, int32_t *dom, int32_t dom_cap, float *n2);
+int  p7x_debug_ensemble_records(const p7x_oprofile *om, const p7x_seqdb *db, int64_t target, const uint8_t *dsq1, int32_t L,
+                                int32_t i, int32_t j, int use_device, uint32_t *cells, uint32_t *rows, float *md);
 /* Parity seam of the batched cascade (the multi-profile twin of p7x_filters_batch): runs stage 1 exactly as
  * p7x_search_batch_enqueue queues it -- profiles grouped into kernel classes, the hybrid lane / wave MSV split, the work
  * lists -- and returns what the stages left behind, [nq][ntargets] in caller order of both: xJ (every target; -1

@@ -1257,6 +1257,13 @@ int domaindef_multi_region(const Profile &p, const uint8_t *dsq, int L, int i, i
     for (int t = 0; t < nsamples; ++t) {
       { ProfScope ps(2); if (stochastic_trace(rng, om, ws.fwd, Lr, ws.tr) != P7X_OK) return P7X_EINVAL; }
       ws.tr.index();
+      if (ens && ens->raw_out && ens->raw_out->want_traces) {      // test seam: the path itself
+        EnsembleRaw &raw = *ens->raw_out;
+        raw.off.push_back((int32_t) raw.st.size());
+        raw.st.insert(raw.st.end(), ws.tr.st.begin(), ws.tr.st.end());
+        raw.k.insert(raw.k.end(), ws.tr.k.begin(), ws.tr.k.end());
+        raw.i.insert(raw.i.end(), ws.tr.i.begin(), ws.tr.i.end());
+      }
       int pos = 1;
       for (int d = 0; d < ws.tr.ndom; ++d) {
         sp.push_back(SpCoord{ t, ws.tr.sqfrom[d] + i - 1, ws.tr.sqto[d] + i - 1, ws.tr.hmmfrom[d], ws.tr.hmmto[d], 0.0f });
@@ -1660,6 +1667,80 @@ extern "C" int p7x_debug_order_spread(const p7x_oprofile *om, const uint8_t *dsq
         note(ta, tb);
       }
     }
+  return P7X_OK;
+}
+
+// Test seam: the choice records of every cell and row of region i..j of dsq1[1..L] as the host twin forms them, in the
+// summation order of the "host_order" option -- the operands of stochastic_trace()'s choices, in the layout and with the
+// operations of ens_forward_kernel (p7x_choice.hpp).  cells: [(Lr + 1)][M + 1] records (row 0 and node 0 stay zero),
+// rows: [Lr + 1]; md (may be NULL): [(Lr + 1)][M + 1][2], the scaled Forward values M(r, k), D(r, k) the E state chooses from.
+namespace p7x {
+int host_choice_records(const Profile &p, const uint8_t *dsq1, int L, int i, int j, ChoiceCell *cells, ChoiceRow *rows, float *md)
+{
+  Model om{ &p, p.M, {} };
+  om.prepare();
+  om.configure(true, L);
+  Matrix fx;
+  const int Lr = j - i + 1, M = p.M, Mrow = M + 1;
+  forward_full(om, dsq1 + i - 1, Lr, fx, nullptr);
+  std::memset(cells, 0, (size_t) (Lr + 1) * Mrow * sizeof(ChoiceCell));
+  std::memset(rows, 0, (size_t) (Lr + 1) * sizeof(ChoiceRow));
+  if (md) std::memset(md, 0, (size_t) (Lr + 1) * Mrow * 2 * sizeof(float));
+  const float *bm = om.tf(0), *tMM = om.tf(1), *tIM = om.tf(2), *tDM = om.tf(3), *tMD = om.tf(4), *tMI = om.tf(5), *tII = om.tf(6), *tDD = om.tf(7);
+  { uint32_t T, b; choice_pair(fx.X(0, xN_) * om.xf[XN][MOVE], fx.X(0, xJ_) * om.xf[XJ][MOVE], &T, &b); rows[0].x[2] = T; rows[0].x[3] = b << 4; }
+  for (int r = 1; r <= Lr; ++r) {
+    for (int k = 1; k <= M; ++k) {
+      ChoiceCell &c = cells[(size_t) r * Mrow + k];
+      uint32_t bi, bd;
+      choice_cell_m(fx.X(r - 1, xB_) * bm[k], fx.M_(r - 1)[k - 1] * tMM[k], fx.I_(r - 1)[k - 1] * tIM[k], fx.D_(r - 1)[k - 1] * tDM[k], c.m);
+      choice_pair(fx.M_(r - 1)[k] * tMI[k], fx.I_(r - 1)[k] * tII[k], &c.id[0], &bi);
+      if (k > 1) choice_pair(fx.M_(r)[k - 1] * tMD[k - 1], fx.D_(r)[k - 1] * tDD[k - 1], &c.id[1], &bd);
+      else       choice_pair(0.0f, 0.0f, &c.id[1], &bd);             // no node before the first: both weights are zero
+      c.id[2] = bi | (bd << 2); c.id[3] = 0;
+      if (md) { md[((size_t) r * Mrow + k) * 2] = fx.M_(r)[k]; md[((size_t) r * Mrow + k) * 2 + 1] = fx.D_(r)[k]; }
+    }
+    ChoiceRow &w = rows[r];
+    uint32_t bc, bj, bb;
+    choice_pair(fx.X(r - 1, xC_) * om.xf[XC][LOOP], fx.X(r, xE_) * om.xf[XE][MOVE] * fx.X(r, xS_), &w.x[0], &bc);
+    choice_pair(fx.X(r - 1, xJ_) * om.xf[XJ][LOOP], fx.X(r, xE_) * om.xf[XE][LOOP] * fx.X(r, xS_), &w.x[1], &bj);
+    choice_pair(fx.X(r, xN_) * om.xf[XN][MOVE], fx.X(r, xJ_) * om.xf[XJ][MOVE], &w.x[2], &bb);
+    w.x[3] = bc | (bj << 2) | (bb << 4);
+    const float norm = (float) (1.0 / fx.X(r, xE_));
+    std::memcpy(&w.e[0], &norm, 4);
+  }
+  return P7X_OK;
+}
+} // namespace p7x
+
+// Test seam: the 200 sampled paths of region i..j of dsq1[1..L] as the host twin walks them (in the "host_order" option's
+// summation order), with the twin's ensemble in p7x_debug_ensemble's format.  Host code, no device.
+extern "C" int p7x_debug_ensemble_traces(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t i, int32_t j, uint32_t seed,
+                                         int8_t *st, int32_t *k, int32_t *pos, int64_t step_cap, int32_t *off201, int64_t *nsteps,
+                                         int32_t *ndom, int32_t *dom, int32_t dom_cap, float *n2)
+{
+  using namespace p7x;
+  if (!om || !dsq1 || !st || !k || !pos || !off201 || !nsteps || !ndom || !dom || !n2 || i < 1 || j < i || j > L || step_cap < 0 || dom_cap < 0) {
+    set_error("p7x_debug_ensemble_traces: bad arguments"); return P7X_EINVAL;
+  }
+  EnsembleRaw raw;
+  raw.want_traces = true;
+  EnsembleResult e; e.status = -1; e.raw_out = &raw;
+  DomainDefResult dd;
+  dd.n2sc.assign((size_t) L + 1, 0.0f);
+  std::vector<Domain> out;
+  std::vector<EnvelopeRequest> defer2;
+  MultiRegionState state;
+  const int status = domaindef_multi_region(om->p, dsq1, L, i, j, seed, true, state, dd, out, &defer2, 0, &e);
+  if (status != P7X_OK) return status;
+  if (raw.off.size() != 200) { set_error("p7x_debug_ensemble_traces: the twin did not sample 200 paths"); return P7X_EINVAL; }
+  raw.off.push_back((int32_t) raw.st.size());
+  *nsteps = (int64_t) raw.st.size();
+  std::memcpy(off201, raw.off.data(), 201 * sizeof(int32_t));
+  const size_t n = (size_t) std::min<int64_t>(*nsteps, step_cap);
+  std::memcpy(st, raw.st.data(), n); std::memcpy(k, raw.k.data(), n * 4); std::memcpy(pos, raw.i.data(), n * 4);
+  *ndom = (int32_t) (raw.dom.size() / 5);
+  std::memcpy(dom, raw.dom.data(), std::min(raw.dom.size(), (size_t) dom_cap * 5) * 4);
+  std::memcpy(n2, raw.n2.data(), (size_t) (j - i + 2) * 4);
   return P7X_OK;
 }
 

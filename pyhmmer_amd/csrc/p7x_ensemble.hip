@@ -636,6 +636,19 @@ public:
     return P7X_OK;
   }
 
+  // Test seam (p7x_debug_ensemble_records): the workspace is zeroed before the fill, and after wait() the records of the
+  // first launched region are copied back, (Lr + 1) x (M + 1) cells and Lr + 1 rows.
+  void zero_workspace_first() { zero_work_ = true; }
+  int copy_records(int Lr, int M, ChoiceCell *cells, ChoiceRow *rows, float *md)
+  {
+    if (nlaunched_ < 1 || !d_cells_ || !d_rows_ || regs_.empty() || regs_[0].Lr != Lr) { set_error("ensemble records: the region was not sampled on the device"); return P7X_EINVAL; }
+    P7X_HIP(hipSetDevice(db_->device));
+    P7X_HIP(hipMemcpy(cells, d_cells_ + regs_[0].cell0, (size_t) (Lr + 1) * (M + 1) * sizeof(ChoiceCell), hipMemcpyDeviceToHost));
+    P7X_HIP(hipMemcpy(rows, d_rows_ + regs_[0].row0, (size_t) (Lr + 1) * sizeof(ChoiceRow), hipMemcpyDeviceToHost));
+    if (md) P7X_HIP(hipMemcpy(md, d_md_ + regs_[0].cell0, (size_t) (Lr + 1) * (M + 1) * sizeof(float2), hipMemcpyDeviceToHost));
+    return P7X_OK;
+  }
+
 private:
   int begin_on_device(const std::vector<EnvelopeJob> &jobs, uint32_t seed_state, int nsamples)
   {
@@ -757,6 +770,7 @@ private:
     { int at = 0; for (auto &kv : by_class) { std::copy(kv.second.begin(), kv.second.end(), h_lists + at); runs.push_back({ kv.first, { at, (int) kv.second.size() } }); at += (int) kv.second.size(); } }
     hipStream_t s = eb->stream;
     P7X_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
+    if (zero_work_) P7X_HIP(hipMemsetAsync(work, 0, work_bytes, s));      // test seam: a record the fill leaves untouched reads as zeros
     EnsArgs a{};
     a.jobs = reinterpret_cast<const EnsJob *>(d_in + o_jobs);
     a.regions = reinterpret_cast<const EnsRegion *>(d_in + o_regs);
@@ -789,6 +803,7 @@ private:
     if ((st = ens_walk_launch(a, s)) != P7X_OK) return st;
     P7X_HIP(hipMemcpyAsync(eb->h_out.as<void>(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
     regs_ = std::move(regs);
+    d_cells_ = a.cells; d_rows_ = a.rows; d_md_ = a.md;
     return P7X_OK;
   }
 
@@ -801,6 +816,8 @@ private:
   int64_t nreg_ = 0; int nlaunched_ = 0;
   Lease<EnsBuffers> lease_;
   size_t o_ndom_ = 0, o_status_ = 0, o_dom_ = 0, o_n2_ = 0;
+  bool zero_work_ = false;
+  const ChoiceCell *d_cells_ = nullptr; const ChoiceRow *d_rows_ = nullptr; const float2 *d_md_ = nullptr;
 };
 
 std::unique_ptr<EnsembleRunner> make_device_ensemble_runner(DeviceCtx *ctx, const p7x_seqdb *db, float guard)
@@ -861,6 +878,38 @@ extern "C" int p7x_debug_ensemble(const p7x_oprofile *om, const p7x_seqdb *db, i
   std::memcpy(dom, raw.dom.data(), std::min(raw.dom.size(), (size_t) dom_cap * 5) * 4);
   std::memcpy(n2, raw.n2.data(), (size_t) (Lr + 1) * 4);
   return P7X_OK;
+}
+
+// Test seam: the choice records of region i..j -- 32 bytes per cell, [(j-i+2)][M+1], and 32 per row, [j-i+2] -- as
+// ens_forward_kernel wrote them (use_device != 0: the region of target <target> of <db>, copied back after the fill; what
+// the fill does not write is zero) or as the host twin forms them for every cell in the "host_order" option's summation
+// order (use_device == 0: db may be NULL, the region is then of dsq1[1..L]).  md (may be NULL): [(j-i+2)][M+1][2], the scaled
+// Forward values (M, D) of every cell beside its records, which the E state's choice reads.
+extern "C" int p7x_debug_ensemble_records(const p7x_oprofile *om, const p7x_seqdb *db, int64_t target, const uint8_t *dsq1, int32_t L,
+                                          int32_t i, int32_t j, int use_device, uint32_t *cells, uint32_t *rows, float *md)
+{
+  using namespace p7x;
+  if (db) {
+    if (target < 0 || target >= db->n) { set_error("p7x_debug_ensemble_records: bad arguments"); return P7X_EINVAL; }
+    L = db->h_len[(size_t) target];
+    dsq1 = db->h_dsq.data() + db->h_off[(size_t) target] - 1;
+  }
+  if (!om || !cells || !rows || !dsq1 || (use_device && !db) || i < 1 || j < i || j > L) { set_error("p7x_debug_ensemble_records: bad arguments"); return P7X_EINVAL; }
+  ChoiceCell *oc = reinterpret_cast<ChoiceCell *>(cells);
+  ChoiceRow *orw = reinterpret_cast<ChoiceRow *>(rows);
+  if (!use_device) return host_choice_records(om->p, dsq1, L, i, j, oc, orw, md);
+  DeviceCtx *ctx = nullptr;
+  int st = get_ctx(db->device, &ctx);
+  if (st != P7X_OK) return st;
+  DeviceEnsembleRunner runner(ctx, db, 0.0f);
+  runner.zero_workspace_first();
+  std::vector<EnvelopeRequest> req{ EnvelopeRequest{ 0, i, j } };
+  std::vector<int32_t> targets{ (int32_t) target };
+  std::vector<EnvelopeJob> jobs{ EnvelopeJob{ om, &req, &targets } };
+  if ((st = runner.begin(jobs, fast_rng_state(42), 200)) != P7X_OK) return st;
+  std::vector<std::vector<EnsembleResult>> res;
+  if ((st = runner.wait(res)) != P7X_OK) return st;
+  return runner.copy_records(j - i + 1, om->p.M, oc, orw, md);
 }
 
 #ifdef P7X_ENS_PROFILE

@@ -66,7 +66,11 @@ struct EnvelopeScorer {
 // The stochastic traceback ensembles of multi-domain regions can be handed to the device as well (p7x_ensemble.hip): a
 // request is region i..j of survivor <item> (EnvelopeRequest), the answer the sampled domains' end points and the
 // per-residue sums of their null2 odds; clustering and everything after it stays with the host stage.
-struct EnsembleRaw { std::vector<int32_t> dom; std::vector<float> n2; };      // test seam: a host-sampled ensemble in the device's format
+struct EnsembleRaw {                  // test seam: a host-sampled ensemble in the device's format
+  std::vector<int32_t> dom; std::vector<float> n2;
+  bool want_traces = false;           // ... and the sampled paths themselves: sample t is steps off[t] .. off[t + 1] - 1, S first
+  std::vector<int8_t> st; std::vector<int32_t> k, i, off;
+};
 struct EnsembleResult {
   int status = -1;                      // 0: done; anything else: the host resolves the region itself
   int ndom = 0;                         // sampled domains, all samples together
@@ -103,6 +107,10 @@ struct Region { int i, j; bool multi; };
 // regs[(first(i) + r)*3 ..] = first residue, last residue, is_multidomain_region, with first(i) = start[i] (packed), or
 // i*cap when <start> is null; nexpected[i] = expected number of domains.
 struct DeviceRegions { const int32_t *n = nullptr; const int32_t *regs = nullptr; const float *nexpected = nullptr; int cap = 0; const int32_t *start = nullptr; };
+struct ChoiceCell; struct ChoiceRow;  // p7x_choice.hpp
+// test seam: the choice records of region i..j of dsq1[1..L] as the host twin forms them, cells [(j-i+2)][M+1], rows [j-i+2], and
+// (md != NULL) the scaled Forward values (M, D) of every cell, which the E state chooses from
+int host_choice_records(const Profile &p, const uint8_t *dsq1, int L, int i, int j, ChoiceCell *cells, ChoiceRow *rows, float *md);
 struct MultiRegionState { bool started = false; uint32_t rng_seed = 42, rng_x = 0; };   // RNG carried between the regions of one target
 int domaindef_regions(const Profile &p, int L, const float *fwd_xmx, const float *bck_xmx, DomainDefResult &dd, std::vector<Region> &regs);
 // <defer2>: the clustered envelopes are queued there (tagged <item>) for a second round of device rescoring instead of being

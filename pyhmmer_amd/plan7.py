@@ -3551,3 +3551,44 @@ class TraceAligner:
         return cls._from_rows([s.name for s in sequences], rows, [s.description or "" for s in sequences],
                               [s.accession or "" for s in sequences], pps if any(pps) else None, pp_cons or None, rf or None,
                               ss or None, alphabet=hmm.alphabet if digitize else None)
+
+
+def ensemble_traces(om: "OptimizedProfile", residues, start: int, end: int, *, seed: int = 42):
+    """Test seam (``p7x_debug_ensemble_traces``, host code): the 200 paths the host twin samples from region ``start..end``
+    (1-based) of the target ``residues`` (digital codes), in the summation order of the ``host_order`` debug option.  Returns
+    ``(st, k, i, offsets[201], domains[n, 5], null2_sums[Lr + 1])``: step ``s`` of sample ``t`` is index ``offsets[t] + s`` of
+    the state codes ``st`` (p7T_*), nodes ``k`` and residues ``i`` (inside the region); the last two as `SequenceDatabase.ensemble`."""
+    seq = np.concatenate([[255], np.asarray(residues, dtype=np.uint8)]).astype(np.uint8)
+    L, Lr = len(seq) - 1, end - start + 1
+    cap, dom_cap = 200 * (3 * Lr + 3 * om.M + 16), 200 * 64
+    st, k, pos = np.zeros(cap, dtype=np.int8), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    off, nsteps, ndom = np.zeros(201, dtype=np.int32), C.c_int64(0), C.c_int32(0)
+    dom, n2 = np.zeros((dom_cap, 5), dtype=np.int32), np.zeros(Lr + 1, dtype=np.float32)
+    rc = _lib.lib().p7x_debug_ensemble_traces(om._handle, seq.ctypes.data, L, int(start), int(end), int(seed), st.ctypes.data, k.ctypes.data,
+                                              pos.ctypes.data, cap, off.ctypes.data, C.byref(nsteps), C.byref(ndom), dom.ctypes.data,
+                                              dom_cap, n2.ctypes.data)
+    if rc != 0:
+        raise status_to_exception(rc, "p7x_debug_ensemble_traces", _lib.last_error())
+    if nsteps.value > cap or ndom.value > dom_cap:
+        raise ValueError("p7x_debug_ensemble_traces: more steps or domains than the buffers hold")
+    n = nsteps.value
+    return st[:n].copy(), k[:n].copy(), pos[:n].copy(), off, dom[:ndom.value].copy(), n2
+
+
+def ensemble_records(om: "OptimizedProfile", start: int, end: int, *, residues=None, db: "SequenceDatabase" = None, target: int = 0,
+                     device: bool = False):
+    """Test seam (``p7x_debug_ensemble_records``): the choice records of region ``start..end`` -- ``cells[Lr + 1, M + 1, 8]`` and
+    ``rows[Lr + 1, 8]`` 32-bit words (``p7x_choice.hpp``), and ``md[Lr + 1, M + 1, 2]``, the scaled Forward values M and D the E
+    state chooses among -- as the device's Forward fill wrote them (``device=True``, target
+    ``target`` of ``db``) or as the host twin forms them (of ``db``'s target, or of the digital codes ``residues``)."""
+    Lr = end - start + 1
+    cells, rows = np.zeros((Lr + 1, om.M + 1, 8), dtype=np.uint32), np.zeros((Lr + 1, 8), dtype=np.uint32)
+    md = np.zeros((Lr + 1, om.M + 1, 2), dtype=np.float32)
+    seq = None if residues is None else np.concatenate([[255], np.asarray(residues, dtype=np.uint8)]).astype(np.uint8)
+    rc = _lib.lib().p7x_debug_ensemble_records(om._handle, None if db is None else db._handle, int(target),
+                                               None if seq is None else seq.ctypes.data, 0 if seq is None else len(seq) - 1,
+                                               int(start), int(end), int(bool(device)), cells.ctypes.data, rows.ctypes.data,
+                                               md.ctypes.data)
+    if rc != 0:
+        raise status_to_exception(rc, "p7x_debug_ensemble_records", _lib.last_error())
+    return cells, rows, md

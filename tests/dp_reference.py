@@ -75,7 +75,8 @@ def length_model(L, multihit):
 
 class RefResult:
     """fwd / bck: totals in nats.  fx / bx: (L + 1) x 5 logs of E N J B C per row (the oracle's column order).  With
-    cells: fM fI bM bI (L + 1) x (M + 2) logs, from which the posteriors come."""
+    cells: fM fI fD bM bI bD (L + 1) x (M + 2) logs, from which the posteriors come (fD / bD: the delete cells, which emit nothing
+    and have no part in posteriors(); tests/ensemble_reference.py states the traceback choices from them)."""
 
     def posteriors(self):
         """ppM, ppI: (L + 1) x (M + 2); ppN, ppJ, ppC: (L + 1), the probability that residue i is emitted there."""
@@ -118,6 +119,7 @@ def forward_backward(model, seq, multihit, cells=False, length=None, backward=Tr
     if cells:
         r.fM, r.fI = np.full((L + 1, M + 2), NEG), np.full((L + 1, M + 2), NEG)
         r.bM, r.bI = np.full((L + 1, M + 2), NEG), np.full((L + 1, M + 2), NEG)
+        r.fD, r.bD = np.full((L + 1, M + 2), NEG), np.full((L + 1, M + 2), NEG)
 
     # ---- Forward
     fx[0, N], fx[0, B] = 0.0, move
@@ -141,7 +143,7 @@ def forward_backward(model, seq, multihit, cells=False, length=None, backward=Tr
         fx[i, J] = lae(fx[i - 1, J] + loop, xE + eloop)
         fx[i, B] = lae(fx[i, J] + move, fx[i, N] + move)
         if cells:
-            r.fM[i], r.fI[i] = Mc, Ic
+            r.fM[i], r.fI[i], r.fD[i] = Mc, Ic, Dc
         Mp, Ip, Dp = Mc, Ic, Dc
     r.fwd = float(fx[L, C] + move)
     if not backward:
@@ -169,7 +171,7 @@ def forward_backward(model, seq, multihit, cells=False, length=None, backward=Tr
         Mn, Dn = close_row(bx[L, E], none, none)
         In = none.copy()
         if cells:
-            r.bM[L], r.bI[L] = Mn, In
+            r.bM[L], r.bI[L], r.bD[L] = Mn, In, Dn
         for i in range(L - 1, -1, -1):
             e = m.e[seq[i]]                    # residue i + 1
             em = np.full(M + 2, NEG)
@@ -190,7 +192,7 @@ def forward_backward(model, seq, multihit, cells=False, length=None, backward=Tr
             Mn, Dn = close_row(bx[i, E], a_m, a_d)
             In = Ic
             if cells:
-                r.bM[i], r.bI[i] = Mn, In
+                r.bM[i], r.bI[i], r.bD[i] = Mn, In, Dn
         r.bck = float(bx[0, N])
     else:
         r.bck = r.fwd

@@ -36,10 +36,17 @@ def null2_by_expectation(model, ref, degeneracy):
     rest = (ppI[1:, 1:M + 1].sum() + pN[1:].sum() + pJ[1:].sum() + pC[1:].sum()) / Ld
     null2 = np.ones(model.Kp)
     null2[:K] = np.exp(model.e[:K, 1:M + 1]) @ occ + rest
-    for x in range(K, model.Kp):
+    return finish_null2(null2, degeneracy)
+
+
+def finish_null2(null2, degeneracy):
+    """The degenerate codes of a null2 vector whose K canonical entries are set: the mean over the residues a code stands
+    for; gap, '*' and missing data stay 1 (tests/ensemble_reference.py's null2 by trace ends the same way)."""
+    degeneracy = np.asarray(degeneracy, dtype=np.float64)
+    K = degeneracy.shape[1]
+    for x in range(K, len(null2)):
         members = degeneracy[x] > 0
-        if members.any():
-            null2[x] = null2[:K][members].mean()
+        null2[x] = null2[:K][members].mean() if members.any() else 1.0
     return null2
 
 
