@@ -99,6 +99,10 @@ constexpr int msv_even_imm_c(int R, int K) { return K == 1 ? kTabRows * msv_row_
 constexpr int msv_even_add_c(int R, int K) { return (K == 1 || msv_uniform_c(K)) ? 0 : kTabRows * msv_row_stride_c(R, K) * 4; }
 constexpr int msv_block_c(int K) { return K == 1 ? 256 : 512; }                            // threads per block: K > 1 tables are big, more
                                                                                            // wavefronts share one copy
+// The tiles that run two wavefronts per SIMD (one lane beyond 136 registers, two lanes, four lanes) take the row without
+// hipcc's pad states behind its asm statements (lds_wait4, RowChunks::pair): alone they run 2-3 % faster for it, the tiles
+// with three or four wavefronts per SIMD and the uniform rows of K = 8 not at all (profiles/r27_msv_row.md).
+constexpr bool msv_padfree_c(int R, int K) { return K == 1 ? R > 136 : !msv_uniform_c(K); }
 // maximum over the K lanes of a target (K = 1, 2, 4, 8; lanes of a target are consecutive)
 template <int K, bool H = false> __device__ __forceinline__ s2 target_max(s2 m)
 {
@@ -139,23 +143,31 @@ __device__ __forceinline__ void lds_issue2(uint32_t addr, Chunk &c)
                : "=&v"(c.e0), "=&v"(c.e1)
                : "v"(addr), "i"(OFF), "i"(OFF + 8));
 }
-template <int PENDING>
+// Waiting for a chunk.  TIED: the statement names the chunk's registers "+v", which keeps every consumer behind it by data
+// dependence -- and makes hipcc put its fixed pad state (s_nop 0) between the statement and the first packed operation that
+// reads them.  Not TIED (the fast flavours' rows in the tiles of msv_padfree_c): a wait-only statement and a scheduling
+// barrier keep the same order without operands, so without the pad; scripts/check_lds_asm.py checks the listing either way.
+template <int PENDING, bool TIED>
 __device__ __forceinline__ void lds_wait4(Chunk &c)
 {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(c.e0), "+v"(c.e1), "+v"(c.e2), "+v"(c.e3) : "i"(PENDING));
+  if constexpr (TIED) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(c.e0), "+v"(c.e1), "+v"(c.e2), "+v"(c.e3) : "i"(PENDING));
+  else { asm volatile("s_waitcnt lgkmcnt(%0)" : : "i"(PENDING)); __builtin_amdgcn_sched_barrier(0); }
 }
-template <int PENDING>
+template <int PENDING, bool TIED>
 __device__ __forceinline__ void lds_wait2(Chunk &c)
 {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(c.e0), "+v"(c.e1) : "i"(PENDING));
+  if constexpr (TIED) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(c.e0), "+v"(c.e1) : "i"(PENDING));
+  else { asm volatile("s_waitcnt lgkmcnt(%0)" : : "i"(PENDING)); __builtin_amdgcn_sched_barrier(0); }
 }
 
 // One DP row over the register file: chunks of four register pairs (8 registers, 16 cells); when R is not a multiple
 // of 8 the top chunk holds two pairs.
-template <int R, int TB, bool ODD, int T, int FAST = 0, bool U = false>   // TB = byte offset of the row's parity table that goes into the
-struct RowChunks {                                        // instructions' immediate; T = chunk index being computed;
+template <int R, int TB, bool ODD, int T, int FAST = 0, bool U = false, bool TIED = true>   // TB = byte offset of the row's parity table that
+struct RowChunks {                                        // goes into the instructions' immediate; T = chunk index being computed;
                                                           // FAST: 0 = the recurrence as written, 1 = floored int16, 2 = floored half
                                                           // U: the uniform row (one alignment, one table; walked downwards: ODD = true)
+                                                          // TIED: asm statements with "+v" operands (lds_wait4); else the pad-free forms
+  static_assert(TIED || (FAST != 0 && !U), "the pad-free forms are those of the fast flavours' parity rows");
   static_assert(!U || ODD, "the uniform row reads the register below: it is walked from the top register down");
   static_assert(R % 4 == 0, "a row is walked in chunks of 8 registers and a last one of 4: the register count must be a multiple of 4");
   static constexpr int NT = (R + 7) / 8;
@@ -204,8 +216,15 @@ struct RowChunks {                                        // instructions' immed
         v[2 * JJ] = h_adds(v[2 * JJ], as_s2(e.x));
         v[2 * JJ + 1] = h_adds(v[2 * JJ + 1], as_s2(e.y));
       }
-      if constexpr (JJ & 1) { accB = h_max3(accB, v[2 * JJ], v[2 * JJ + 1]); asm volatile("" : "+v"(accB)); }
-      else { accA = h_max3(accA, v[2 * JJ], v[2 * JJ + 1]); asm volatile("" : "+v"(accA)); }
+      // Pin the accumulator update here (see the integer flavour below).  Not TIED: an empty asm that only READS it holds
+      // the maximum3 in its chunk like a "+v" one, and hipcc pads no state behind a statement without outputs.
+      if constexpr (JJ & 1) {
+        accB = h_max3(accB, v[2 * JJ], v[2 * JJ + 1]);
+        if constexpr (TIED) asm volatile("" : "+v"(accB)); else asm volatile("" : : "v"(accB));
+      } else {
+        accA = h_max3(accA, v[2 * JJ], v[2 * JJ + 1]);
+        if constexpr (TIED) asm volatile("" : "+v"(accA)); else asm volatile("" : : "v"(accA));
+      }
     } else if constexpr (FAST == 1) {       // floored representation: the saturating add *is* max(., xB) (see msv_fast_kernel)
       if constexpr (ODD) {
         v[2 * JJ + 1] = pk_adds(v[2 * JJ], as_s2(e.y));
@@ -220,7 +239,7 @@ struct RowChunks {                                        // instructions' immed
       accB = pk_max(accB, v[2 * JJ + 1]);
       // Pin the two accumulator updates here (empty asm = opaque use).  Otherwise LLVM sinks the whole max chain to
       // the end of the row, where back-to-back dependent VOP3P ops each need a wait state on gfx950 (s_nop per op).
-      asm volatile("" : "+v"(accA), "+v"(accB));
+      if constexpr (TIED) asm volatile("" : "+v"(accA), "+v"(accB)); else asm volatile("" : : "v"(accA), "v"(accB));
     } else if constexpr (ODD) {        // register j <- cells (2j-1, 2j), read from register j-1 of the previous (even) row
       const s2 t1 = pk_max(v[2 * JJ], xB);
       v[2 * JJ + 1] = t1 + as_s2(e.y);
@@ -245,9 +264,9 @@ struct RowChunks {                                        // instructions' immed
     constexpr int np = pairs(T);
     if constexpr (!last) {
       issue<TN>(addr, nxt);
-      if constexpr (np == 4) lds_wait4<pairs(TN)>(cur); else lds_wait2<pairs(TN)>(cur);
+      if constexpr (np == 4) lds_wait4<pairs(TN), TIED>(cur); else lds_wait2<pairs(TN), TIED>(cur);
     } else {
-      if constexpr (np == 4) lds_wait4<0>(cur); else lds_wait2<0>(cur);
+      if constexpr (np == 4) lds_wait4<0, TIED>(cur); else lds_wait2<0, TIED>(cur);
     }
     if constexpr (ODD) {
       if constexpr (np == 4) {
@@ -264,7 +283,7 @@ struct RowChunks {                                        // instructions' immed
         pair<4 * T + 3>(v, cur.e3, xB, carry, accA, accB);
       }
     }
-    if constexpr (!last) RowChunks<R, TB, ODD, TN, FAST, U>::run(v, addr, nxt, cur, xB, carry, accA, accB);
+    if constexpr (!last) RowChunks<R, TB, ODD, TN, FAST, U, TIED>::run(v, addr, nxt, cur, xB, carry, accA, accB);
   }
 };
 
@@ -386,6 +405,7 @@ __device__ __forceinline__ void msv_fast_body(const MsvArgs &a, uint32_t *lds)
 {
   constexpr int S = msv_row_stride_c(R, K), Rs = msv_lane_stride_c(R, K), BLK = msv_block_c(K);
   constexpr int MODE = H ? 2 : 1;
+  constexpr bool TIED = !msv_padfree_c(R, K);
   const int nitems = (a.ngroups - a.group_first) * K;
   if (*a.counter >= nitems) return;            // this lane's groups are all taken: skip the table load
   {
@@ -438,9 +458,13 @@ __device__ __forceinline__ void msv_fast_body(const MsvArgs &a, uint32_t *lds)
       return max(max(a.base, xJ) - tjbm, 0);
     };
 
+    // The group's last 16-residue tile: when the group's longest target (its first slot: slots are sorted by decreasing
+    // length) ends in the tile's first half, the second half holds the pad residue in every lane.  Pad emissions clamp
+    // every cell to the floor and raise no maximum, so those eight rows are left out.
+    const int nhb = 2 * nblk - (a.slot_len[it.g * 64] <= 16 * nblk - 8 ? 1 : 0);
     uint2 cur = tp[0];
-    for (int hb = 0; hb < 2 * nblk; ++hb) {          // 8 residues at a time
-      const uint2 nxt = (hb + 1 < 2 * nblk) ? tp[(size_t) ((hb + 1) >> 1) * 128 + ((hb + 1) & 1)] : cur;
+    for (int hb = 0; hb < nhb; ++hb) {               // 8 residues at a time
+      const uint2 nxt = (hb + 1 < nhb) ? tp[(size_t) ((hb + 1) >> 1) * 128 + ((hb + 1) & 1)] : cur;
       uint32_t w0 = cur.x, w1 = cur.y;
 #pragma unroll 1
       for (int c = 0; c < 4; ++c) {
@@ -457,12 +481,12 @@ __device__ __forceinline__ void msv_fast_body(const MsvArgs &a, uint32_t *lds)
           } else if (half == 0) {        // odd row
             const uint32_t addr = x0 * (uint32_t) (S * 4) + lane_col;
             const s2 carry = carry_in<K>(v[R - 1], floorv, it.h);
-            RowChunks<R, 0, true, NT - 1, MODE>::template issue<NT - 1>(addr, ca);
-            RowChunks<R, 0, true, NT - 1, MODE>::run(v, addr, ca, cb, floorv, carry, accA, accB);
+            RowChunks<R, 0, true, NT - 1, MODE, false, TIED>::template issue<NT - 1>(addr, ca);
+            RowChunks<R, 0, true, NT - 1, MODE, false, TIED>::run(v, addr, ca, cb, floorv, carry, accA, accB);
           } else {                // even row
             const uint32_t addr = x1 * (uint32_t) (S * 4) + lane_col + (uint32_t) msv_even_add_c(R, K);
-            RowChunks<R, msv_even_imm_c(R, K), false, 0, MODE>::template issue<0>(addr, ca);
-            RowChunks<R, msv_even_imm_c(R, K), false, 0, MODE>::run(v, addr, ca, cb, floorv, floorv, accA, accB);
+            RowChunks<R, msv_even_imm_c(R, K), false, 0, MODE, false, TIED>::template issue<0>(addr, ca);
+            RowChunks<R, msv_even_imm_c(R, K), false, 0, MODE, false, TIED>::run(v, addr, ca, cb, floorv, floorv, accA, accB);
           }
           const s2 m2 = target_max<K, H>(mx(accA, accB));
           if (__builtin_expect(__any(as_u32(mx(m2, Tv)) != as_u32(Tv)), 0)) {
