@@ -374,7 +374,17 @@ int  p7x_debug_ensemble(const p7x_oprofile *om, const p7x_seqdb *db, int64_t tar
  *   of target <target> of <db>; what the kernel leaves untouched -- row 0 of the cells, node 0 -- is zero) or as the host
  *   twin forms them for every cell (use_device == 0; with db == NULL the region is of dsq1[1..L], else dsq1 / L are ignored).
  *   md (may be NULL): md[(j-i+2)][M+1][2], the scaled Forward values M(r, k) and D(r, k) kept beside the records: the E
- *   state chooses among them, each times the row's factor (float) (1 / xE) in word 4 of its row record. */
+ *   state chooses among them, each times the row's factor (float) (1 / xE) in word 4 of its row record.
+ * p7x_debug_ens_walk_plan: host code, no device.  What the walk kernel keeps in LDS for a region of Lr residues of a model
+ *   of M nodes, in a launch whose longest model has maxM >= M nodes and whose longest region maxLr >= Lr residues (the
+ *   launch's LDS is sized for those), under an LDS cap of lds_kb KiB; lds_kb <= 0: what the library would choose now, the
+ *   option "ens_lds_kb" honoured.  out[38]: lds_bytes, least, want; rows, residues in LDS (0 / 1); the accumulators' home
+ *   (0 registers, 1 LDS, 2 memory); odds, Forward rows in LDS; index bits of the match cache and of the insert / delete
+ *   cache; match cache by row; cell numbers fit the tags; bytes used before and after the caches; then (offset, bytes) of
+ *   the twelve sections in LDS order -- visit counts, null2 vector, its partial sums, Forward-row tags, row records, 1 / xE,
+ *   residues, accumulators, odds, Forward rows, match cache, insert / delete cache -- offset -1 for a piece kept in memory.
+ *   Returns the number of words written, or a negative status. */
+int  p7x_debug_ens_walk_plan(int M, int Lr, int maxM, int maxLr, int lds_kb, int32_t *out);
 int  p7x_debug_ensemble_traces(const p7x_oprofile *om, const uint8_t *dsq1, int32_t L, int32_t i, int32_t j, uint32_t seed,
                                int8_t *st, int32_t *k, int32_t *pos, int64_t step_cap, int32_t *off201, int64_t *nsteps,
                                int32_t *ndom, int32_t *dom, int32_t dom_cap, float *n2);

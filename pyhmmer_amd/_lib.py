@@ -248,6 +248,7 @@ _SIGNATURES = {
     "p7x_debug_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "p7x_longtargets_release_resident": (C.c_int, [C.c_int, C.c_uint64]),
     "p7x_debug_ensemble": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int, _VP, _VP, C.c_int32, _VP, _VP]),
+    "p7x_debug_ens_walk_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "p7x_debug_ensemble_traces": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "p7x_debug_ensemble_records": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int, _VP, _VP, _VP]),
     "p7x_search_batch_raw": (C.c_int, [C.POINTER(PipelineCfg), C.POINTER(_VP), C.c_size_t, _VP, _VP, _VP, _VP, _VP]),

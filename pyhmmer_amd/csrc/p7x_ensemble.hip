@@ -23,6 +23,7 @@
 #include "p7x_launch.hpp"
 #include "p7x_waverows.hpp"
 #include "p7x_choice.hpp"
+#include "p7x_ens_plan.hpp"
 #include "p7x_host.hpp"
 #include <algorithm>
 #include <cstring>
@@ -216,55 +217,45 @@ __global__ void __launch_bounds__(64) ens_walk_kernel(const EnsArgs a)
   const EnsRegion reg = a.regions[r];
   const EnsJob job = a.jobs[reg.job];
   const int M = job.M, Mrow = M + 1, Lr = reg.Lr, Q = job.Q, K = job.K, Kp = job.Kp;
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(smem);                          // [M + 2]
-  float *n2v = reinterpret_cast<float *>(cnt + ((M + 2 + 31) & ~31));          // [32]
-  float *accz = n2v + 32;                                                      // [4][32]
-  int *mdtag = reinterpret_cast<int *>(accz + 128);                            // [8]
-  size_t used = (size_t) (((M + 2 + 31) & ~31) + 32 + 128 + 8) * 4;
-  const size_t cap = (size_t) a.lds_bytes - 4096;               // the record caches' minimum stays free
+  // what lives where (p7x_ens_plan.hpp): every piece that fits below the caches' minimum is in LDS, the rest stays in memory
+  const EnsWalkPlan plan = ens_walk_plan(M, Lr, a.lds_bytes);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(smem + plan.off[ENS_SEC_CNT]);     // [M + 2]
+  float *n2v = reinterpret_cast<float *>(smem + plan.off[ENS_SEC_N2V]);           // [32]
+  float *accz = reinterpret_cast<float *>(smem + plan.off[ENS_SEC_ACCZ]);         // [4][32]
+  int *mdtag = reinterpret_cast<int *>(smem + plan.off[ENS_SEC_MDTAG]);           // [8]
   const ChoiceRow *__restrict__ rows = a.rows + reg.row0;
   // rows' records C / J / B (16 bytes each) and select_e's factor 1 / xE(i)
-  const bool rows_in_lds = used + (size_t) (Lr + 1) * 20 + 16 <= cap;
-  uint4 *rowl = reinterpret_cast<uint4 *>(smem + used);
-  float *norml = reinterpret_cast<float *>(rowl + (Lr + 1));
-  if (rows_in_lds) used += ((size_t) (Lr + 1) * 20 + 15) & ~(size_t) 15;
+  const bool rows_in_lds = plan.rows_in_lds;
+  uint4 *rowl = reinterpret_cast<uint4 *>(smem + plan.off[ENS_SEC_ROWS]);
+  float *norml = reinterpret_cast<float *>(smem + plan.off[ENS_SEC_NORM]);
   // the region's residues (the finished domains look their odds up by residue)
   const uint8_t *__restrict__ sqg = a.dsq + reg.sq;
-  const bool sq_in_lds = used + (size_t) Lr + 16 <= cap;
-  uint8_t *sql = smem + used;
-  if (sq_in_lds) { for (int q = lane; q < Lr; q += 64) sql[q] = sqg[q]; used += ((size_t) Lr + 15) & ~(size_t) 15; }
+  const bool sq_in_lds = plan.sq_in_lds;
+  uint8_t *sql = smem + plan.off[ENS_SEC_SQ];
+  if (sq_in_lds) for (int q = lane; q < Lr; q += 64) sql[q] = sqg[q];
   // accumulators: lane l keeps residues l + 1 + 64 j, j < 8, in registers when the region is short enough
-  constexpr int NR = 8;
-  const bool n2_in_regs = Lr <= 64 * NR && sq_in_lds;
-  const bool n2_in_lds = !n2_in_regs && used + (size_t) (Lr + 1) * 4 + 16 <= cap;
+  constexpr int NR = ENS_N2_PER_LANE;
+  const bool n2_in_regs = plan.n2_home == ENS_N2_REGS, n2_in_lds = plan.n2_home == ENS_N2_LDS;
   float *n2g = a.n2acc + reg.row0;
-  float *n2 = n2_in_lds ? reinterpret_cast<float *>(smem + used) : n2g;
-  if (n2_in_lds) used += (size_t) (((Lr + 1) + 3) & ~3) * 4;
+  float *n2 = n2_in_lds ? reinterpret_cast<float *>(smem + plan.off[ENS_SEC_N2]) : n2g;
   // match odds
-  const bool rft_in_lds = used + (size_t) (M + 1) * 128 <= cap;
-  const float *rft = rft_in_lds ? reinterpret_cast<const float *>(smem + used) : job.rft;
+  const bool rft_in_lds = plan.rft_in_lds;
+  const float *rft = rft_in_lds ? reinterpret_cast<const float *>(smem + plan.off[ENS_SEC_RFT]) : job.rft;
   if (rft_in_lds) {
-    float4 *dst = reinterpret_cast<float4 *>(smem + used);
+    float4 *dst = reinterpret_cast<float4 *>(smem + plan.off[ENS_SEC_RFT]);
     const float4 *src = reinterpret_cast<const float4 *>(job.rft);
     for (int q = lane; q < (M + 1) * 8; q += 64) dst[q] = src[q];
-    used += (size_t) (M + 1) * 128;
   }
   // eight Forward rows (M and D cells) for select_e: a sample's domains end where the last sample's did, give or take
-  const bool md_in_lds = used + (size_t) 8 * Mrow * 8 + 16 <= cap;
-  float2 *mdl = reinterpret_cast<float2 *>(smem + used);
-  if (md_in_lds) used += ((size_t) 8 * Mrow * 8 + 15) & ~(size_t) 15;
-  // the record caches of the core walk (see there): 16-byte entries, powers of two; the match cells' gets about three
-  // quarters of what is left (at most 4096 entries), the insert / delete cells' the rest (at most 1024)
-  used = (used + 15) & ~(size_t) 15;
-  const size_t left = (size_t) a.lds_bytes - used;
-  int mbits = 7, idbits = 6;
-  while (mbits < 12 && ((size_t) 32 << mbits) <= left - left / 4) ++mbits;
-  while (idbits < 10 && ((size_t) 16 << mbits) + ((size_t) 32 << idbits) <= left) ++idbits;
-  uint4 *mcache = reinterpret_cast<uint4 *>(smem + used);
+  const bool md_in_lds = plan.md_in_lds;
+  float2 *mdl = reinterpret_cast<float2 *>(smem + plan.off[ENS_SEC_MD]);
+  // the record caches of the core walk (see there): 16-byte entries, powers of two
+  const int mbits = plan.mbits, idbits = plan.idbits;
+  uint4 *mcache = reinterpret_cast<uint4 *>(smem + plan.off[ENS_SEC_MCACHE]);
   const unsigned idbase = 1u << mbits;                                                 // the insert / delete cache follows the match cache
   for (int q = lane; q < (1 << mbits) + (1 << idbits); q += 64) mcache[q] = make_uint4(0u, 0u, 0u, 0u);
-  const bool cache_ok = (size_t) (Lr + 1) * (size_t) Mrow < ((size_t) 1 << 27) - 2;      // cell numbers fit the 27-bit tags
-  const bool by_row = Lr < (1 << (mbits - 2));                                         // every row has its own four entries
+  const bool cache_ok = plan.cache_ok;                                                 // cell numbers fit the 27-bit tags
+  const bool by_row = plan.by_row;                                                     // every row has its own four entries
   if (rows_in_lds) for (int q = lane; q <= Lr; q += 64) { rowl[q] = *reinterpret_cast<const uint4 *>(rows[q].x); norml[q] = bitsf(rows[q].e[0]); }
   for (int k = lane; k < M + 2; k += 64) cnt[k] = 0;
   if (lane < 8) mdtag[lane] = -1;
@@ -585,6 +576,12 @@ struct EnsBuffers {
   hipStream_t stream = nullptr;
 };
 size_t align256(size_t v) { return (v + 255) & ~(size_t) 255; }
+// the walk kernel's LDS cap: <lds_kb> KiB, or with lds_kb <= 0 the option ens_lds_kb, or the default
+size_t ens_lds_most(int lds_kb)
+{
+  if (lds_kb <= 0) lds_kb = debug_opt(OPT_ENS_LDS_KB);
+  return lds_kb > 0 ? (size_t) lds_kb * 1024 : ENS_LDS_DEFAULT_MOST;
+}
 } // namespace
 
 class DeviceEnsembleRunner final : public EnsembleRunner {
@@ -782,21 +779,13 @@ private:
     a.n2acc = reinterpret_cast<float *>(d_out + o_n2_);
     a.dom = reinterpret_cast<int32_t *>(d_out + o_dom_);
     a.out_ndom = reinterpret_cast<int32_t *>(d_out + o_ndom_); a.out_status = reinterpret_cast<int32_t *>(d_out + o_status_);
-    {   // LDS of the walk kernel: node counts and the null2 scratch always; then, as far as 128 KiB go, the largest region's row
-        // records, residues and accumulators, the longest model's odds table and eight of its Forward rows (each region
-        // takes what fits, in that order), and the record caches of the core walk in the rest (48 KiB when there is room,
-        // never less than 4 KiB)
-      const size_t least = (size_t) (((maxM + 2 + 31) & ~31) + 32 + 128 + 8) * 4 + 64 + 4096;
-      const size_t want = least + (size_t) (maxLr + 1) * 25 + 128 + (size_t) (maxM + 1) * (128 + 64) + 44 * 1024;
-      // ... but no more than 32 KiB by default (option ens_lds_kb): a walk is one wavefront per workgroup, a latency chain that
-      // needs no throughput, and what it holds is missing for the filter kernels' blocks -- three MSV blocks of a Pfam-sized
-      // model take 100 of a CU's 160 KiB, and with 109 KiB gone to a walk only one of them fits.  Round 5, headline workload:
-      // 19.0-20.0 TCUPS with the full 128 KiB, 20.3-21.0 with 16-40 KiB (profiles/r05_ens_lds.txt); the host stage even waits less
-      // for the ensembles (23-30 ms instead of 30-36), because more walks are resident at once.
-      size_t most = (size_t) 32 * 1024;
-      if (debug_opt(OPT_ENS_LDS_KB) > 0) most = (size_t) debug_opt(OPT_ENS_LDS_KB) * 1024;
-      a.lds_bytes = (int) std::max(least, std::min(want, most));
-    }
+    // LDS of the walk kernel (ens_walk_lds_budget): what the launch's largest region and longest model could use, but no more
+    // than 32 KiB by default (option ens_lds_kb): a walk is one wavefront per workgroup, a latency chain that
+    // needs no throughput, and what it holds is missing for the filter kernels' blocks -- three MSV blocks of a Pfam-sized
+    // model take 100 of a CU's 160 KiB, and with 109 KiB gone to a walk only one of them fits.  Round 5, headline workload:
+    // 19.0-20.0 TCUPS with the full 128 KiB, 20.3-21.0 with 16-40 KiB (profiles/r05_ens_lds.txt); the host stage even waits less
+    // for the ensembles (23-30 ms instead of 30-36), because more walks are resident at once.
+    a.lds_bytes = (int) ens_walk_lds_budget(maxM, maxLr, ens_lds_most(0)).lds_bytes;
     const int32_t *d_lists = reinterpret_cast<const int32_t *>(d_in + o_lists);
     for (const auto &run : runs)
       if ((st = ens_forward_launch(run.first, a, d_lists + run.second.first, run.second.second, s)) != P7X_OK) return st;
@@ -826,6 +815,26 @@ std::unique_ptr<EnsembleRunner> make_device_ensemble_runner(DeviceCtx *ctx, cons
 }
 
 } // namespace p7x
+
+// Test seam (host code, no device): the walk kernel's LDS budget for a launch whose longest model has maxM nodes and whose
+// longest region maxLr residues, and the plan of a region of Lr residues of a model of M nodes inside it.
+extern "C" int p7x_debug_ens_walk_plan(int M, int Lr, int maxM, int maxLr, int lds_kb, int32_t *out)
+{
+  using namespace p7x;
+  if (!out || M < 1 || Lr < 1 || maxM < M || maxLr < Lr || maxM > p7x_max_model_length() || lds_kb > 1024 ||
+      (int64_t) maxLr * 25 + (int64_t) maxM * 200 > ((int64_t) 1 << 30)) {
+    set_error("p7x_debug_ens_walk_plan: bad arguments"); return P7X_EINVAL;
+  }
+  const EnsLdsBudget b = ens_walk_lds_budget(maxM, maxLr, ens_lds_most(lds_kb));
+  const EnsWalkPlan p = ens_walk_plan(M, Lr, (int) b.lds_bytes);
+  int n = 0;
+  out[n++] = (int32_t) b.lds_bytes; out[n++] = (int32_t) b.least; out[n++] = (int32_t) b.want;
+  out[n++] = p.rows_in_lds; out[n++] = p.sq_in_lds; out[n++] = p.n2_home; out[n++] = p.rft_in_lds; out[n++] = p.md_in_lds;
+  out[n++] = p.mbits; out[n++] = p.idbits; out[n++] = p.by_row; out[n++] = p.cache_ok;
+  out[n++] = (int32_t) p.used_before_caches; out[n++] = (int32_t) p.used_after_caches;
+  for (int s = 0; s < ENS_NSEC; ++s) { out[n++] = p.off[s]; out[n++] = (int32_t) p.bytes[s]; }
+  return n;
+}
 
 // Test seam: the ensemble of region i..j of one target, as the device samples it (use_device != 0) or as the host twin does:
 // the sampled domains (sample, sqfrom, sqto inside the region, hmmfrom, hmmto; a sample's domains first to last) and the

@@ -7,6 +7,7 @@ through the C-ABI of ``libp7x.so`` (``include/p7x.h``); there is no Python or CP
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -3110,9 +3111,10 @@ class SequenceDatabase:
     def ensemble(self, om: OptimizedProfile, target: int, start: int, end: int, *, seed: int = 42, device: bool = True):
         """Test seam (``p7x_debug_ensemble``): the 200 stochastic tracebacks of region ``start..end`` (1-based) of one
         target, sampled by the device kernels or by the host twin.  Returns ``(status, domains[n, 5], null2_sums[Lr + 1])``:
-        ``domains`` rows are (sample, first residue, last residue, first node, last node), residues counted inside the region."""
+        ``domains`` rows are (sample, first residue, last residue, first node, last node), residues counted inside the region.
+        The buffer holds the most the walk kernel itself records, 64 domains per sample; more raise ``ValueError``."""
         Lr = end - start + 1
-        cap = 200 * 16
+        cap = 200 * 64
         ndom, status = C.c_int32(0), C.c_int32(0)
         dom = np.zeros((cap, 5), dtype=np.int32)
         n2 = np.zeros(Lr + 1, dtype=np.float32)
@@ -3120,7 +3122,11 @@ class SequenceDatabase:
                                            C.byref(ndom), dom.ctypes.data, cap, n2.ctypes.data, C.byref(status))
         if st != 0:
             raise status_to_exception(st, "p7x_debug_ensemble", _lib.last_error())
-        return status.value, dom[:min(ndom.value, cap)].copy(), n2
+        if status.value != 0:                     # the kernel gave the region up (its count may exceed what it recorded): no records
+            return status.value, dom[:0].copy(), n2
+        if ndom.value > cap:
+            raise ValueError("p7x_debug_ensemble: more domains than the buffer holds")
+        return status.value, dom[:ndom.value].copy(), n2
 
     def filters(self, om: OptimizedProfile, msv=True, viterbi=False, forward=False, bias=False):
         """Raw per-target filter outputs (``p7x_filters_batch``): dict of numpy arrays in target order."""
@@ -3592,3 +3598,27 @@ def ensemble_records(om: "OptimizedProfile", start: int, end: int, *, residues=N
     if rc != 0:
         raise status_to_exception(rc, "p7x_debug_ensemble_records", _lib.last_error())
     return cells, rows, md
+
+
+ENS_WALK_SECTIONS = ("cnt", "n2v", "accz", "mdtag", "rows", "norm", "sq", "n2", "rft", "md", "mcache", "idcache")
+ENS_N2_HOMES = ("regs", "lds", "global")
+EnsWalkPlan = collections.namedtuple("EnsWalkPlan", "lds_bytes least want rows_in_lds sq_in_lds n2_home rft_in_lds md_in_lds mbits idbits "
+                                                    "by_row cache_ok used_before_caches used_after_caches sections")
+
+
+def ens_walk_plan(M: int, Lr: int, *, maxM: Optional[int] = None, maxLr: Optional[int] = None, lds_kb: Optional[int] = None):
+    """Test seam (``p7x_debug_ens_walk_plan``, host code): what the ensemble walk kernel keeps in LDS for a region of ``Lr``
+    residues of a model of ``M`` nodes, in a launch sized for the longest model ``maxM`` and the longest region ``maxLr``
+    (default: this region alone) under an LDS cap of ``lds_kb`` KiB (default: the library's, debug option ``ens_lds_kb``
+    honoured).  ``n2_home`` is one of ``ENS_N2_HOMES``; ``sections`` maps each name of ``ENS_WALK_SECTIONS`` to
+    ``(offset, bytes)``, in LDS order, or to ``None`` for a piece that stays in memory."""
+    out = np.zeros(40, dtype=np.int32)
+    n = _lib.lib().p7x_debug_ens_walk_plan(int(M), int(Lr), int(M if maxM is None else maxM), int(Lr if maxLr is None else maxLr),
+                                           int(lds_kb or 0), out.ctypes.data)
+    if n < 0:
+        raise status_to_exception(n, "p7x_debug_ens_walk_plan", _lib.last_error())
+    v = [int(x) for x in out[:n]]
+    sections = {name: ((v[14 + 2 * s], v[15 + 2 * s]) if v[14 + 2 * s] >= 0 else None) for s, name in enumerate(ENS_WALK_SECTIONS)}
+    assert n == 14 + 2 * len(ENS_WALK_SECTIONS)
+    return EnsWalkPlan(v[0], v[1], v[2], bool(v[3]), bool(v[4]), ENS_N2_HOMES[v[5]], bool(v[6]), bool(v[7]), v[8], v[9], bool(v[10]),
+                       bool(v[11]), v[12], v[13], sections)

@@ -10,7 +10,14 @@ on the first of the three is left out and the region is 80 residues (the referen
 
 Gap-rich cases, where the I and D choice points carry weight: gap_models.gappy_hmm with bridge targets over its deletion
 corridors and through its insert-rich node, and the long-insert model of tests/test_host_emit.py.  One background-only
-target and one KR protein of three emitted copies complete the list."""
+target and one KR protein of three emitted copies complete the list.
+
+Region-length cases (_len_case): the tier-2 model on regions of 63 / 64 / 65, 511 / 512 / 513 and 1,500 residues, the lengths
+at which the walk kernel's C / J runs and its per-lane accumulators change path.
+
+PLACEMENTS: the (case, LDS cap) pairs under which tests/test_gpu_ens_walk_placement.py runs the walk kernel, one for every
+placement of its working set that the plan (p7x_ens_plan.hpp, through plan7.ens_walk_plan) yields for six of the cases;
+tests/test_host_ens_walk_plan.py holds the list of placement classes they must cover."""
 import contextlib
 from types import SimpleNamespace
 
@@ -38,7 +45,10 @@ def tier_lengths():
 
 TIER_NAMES = tuple(f"tier{c}_M{m}" for c, m in tier_lengths())
 OTHER_NAMES = ("gappy", "long_insert", "background", "KR_x3")
-NAMES = TIER_NAMES + OTHER_NAMES
+LEN_MODEL = 65                                      # the model of tier2_M65
+LEN_SPARSE, LEN_DENSE = (63, 64, 65, 511, 512, 1500), (513,)
+LEN_NAMES = tuple(f"len{n}" for n in sorted(LEN_SPARSE + LEN_DENSE))
+NAMES = TIER_NAMES + OTHER_NAMES + LEN_NAMES
 
 
 def _consensus(hmm):
@@ -107,6 +117,35 @@ def _kr_case():
     return SimpleNamespace(name="KR_x3", hmm=hmm, seq=seq, start=1, end=len(seq))
 
 
+def _len_case(name, Lr):
+    """Region-length edges of the walk kernel on the tier-2 model, the full region 1..Lr: a C / J run looks at min(64, i) rows
+    at once and lane l keeps the accumulators of residues l + 1 + 64 j, j < 8 (63 / 64 / 65; 511 / 512 / 513).  Sparse: three
+    consensus fragments (nodes 36.., 33.., 1..) in background residues, four roughly equal spacers, so that the C / J runs
+    between the domains are long.  Dense (513): tandem fragments between SPACER-residue spacers, cycling through the three
+    start nodes, about ten domains per sample, so that finished domains keep moving over the accumulators' lanes."""
+    hmm = random_hmm(LEN_MODEL, seed=7000 + LEN_MODEL)
+    cons, starts = _consensus(hmm), (36, 33, 1)
+    if Lr in LEN_DENSE:
+        rng = np.random.default_rng([LEN_MODEL, Lr, 41])
+        parts, total, z = [_spacer(rng)], SPACER, 0
+        while total < Lr:
+            k = starts[z % 3]
+            parts += [cons[k - 1:k - 1 + FRAGMENT], _spacer(rng)]
+            total, z = total + FRAGMENT + SPACER, z + 1
+        seq = np.concatenate(parts)[:Lr]
+    else:
+        rng = np.random.default_rng([LEN_MODEL, Lr, 37])
+        n = FRAGMENT if Lr >= 3 * FRAGMENT + 40 else (Lr - 8) // 3
+        bg = Lr - 3 * n
+        gaps = [bg // 4 + (1 if g < bg % 4 else 0) for g in range(4)]
+        parts = [_spacer(rng, gaps[0])]
+        for g, k in enumerate(starts, start=1):
+            parts += [cons[k - 1:k - 1 + n], _spacer(rng, gaps[g])]
+        seq = np.concatenate(parts)
+    assert len(seq) == Lr
+    return SimpleNamespace(name=name, hmm=hmm, seq=seq, start=1, end=Lr)
+
+
 _cases, _refs = {}, {}
 
 
@@ -114,6 +153,8 @@ def case(name):
     if name not in _cases:
         if name in TIER_NAMES:
             c = _tier_case(name, *tier_lengths()[TIER_NAMES.index(name)])
+        elif name in LEN_NAMES:
+            c = _len_case(name, int(name[3:]))
         else:
             c = {"gappy": _gappy_case, "long_insert": _long_insert_case, "background": _background_case, "KR_x3": _kr_case}[name]()
         c.om = plan7.OptimizedProfile(c.hmm, plan7.Background(c.hmm.alphabet), 400)
@@ -220,3 +261,45 @@ def null2_bound(name, n2ref):
     """Per residue, for the device order: four times the upstream order's distance, or 200 float32 roundings of the sum."""
     return np.maximum(4.0 * null2_ref_distance(name), NSAMPLES * 2.0 ** -23 * n2ref)
 
+
+
+# ---- the placements of the walk kernel's working set (p7x_ens_plan.hpp) that the cases are run under
+PLACEMENT_CASES = ("tier2_M65", "KR_x3", "len513", "len1500", "tier48_M2049", "len63")
+LDS_KB_RANGE = range(1, 129)                       # what option ens_lds_kb is swept over
+
+
+def plan(name, lds_kb=None):
+    """The plan of a case's region in a launch of its own (what SequenceDatabase.ensemble makes) under an LDS cap of lds_kb KiB."""
+    c = case(name)
+    return plan7.ens_walk_plan(c.hmm.M, c.Lr, lds_kb=lds_kb)
+
+
+def placement_class(p):
+    """rows R/r, residues S/s - the accumulators' home - odds F/f, Forward rows D/d; a capital means in LDS."""
+    return f"{'R' if p.rows_in_lds else 'r'}{'S' if p.sq_in_lds else 's'}-{p.n2_home}-{'F' if p.rft_in_lds else 'f'}{'D' if p.md_in_lds else 'd'}"
+
+
+def _placements():
+    """[(case, lds_kb)]: for each case of PLACEMENT_CASES the smallest cap of every distinct placement of the five pieces, the
+    smallest caps that give the smallest cache geometry (fewest match bits; fewest insert / delete bits) and the largest,
+    and 128 KiB."""
+    out = []
+    for name in PLACEMENT_CASES:
+        plans = {kb: plan(name, kb) for kb in LDS_KB_RANGE}
+        keep, seen = set(), set()
+        for kb in LDS_KB_RANGE:
+            cls = placement_class(plans[kb])
+            if cls not in seen:
+                seen.add(cls)
+                keep.add(kb)
+        # (7 match bits always come with 7 insert / delete bits: 4 KiB are left at the least; 6 come with 8 match bits)
+        geometry = {kb: (p.mbits, p.idbits) for kb, p in plans.items()}
+        fewest_id = min(g[::-1] for g in geometry.values())[::-1]
+        for g in (min(geometry.values()), fewest_id, max(geometry.values())):
+            keep.add(min(kb for kb in LDS_KB_RANGE if geometry[kb] == g))
+        keep.add(LDS_KB_RANGE[-1])
+        out += [(name, kb) for kb in sorted(keep)]
+    return out
+
+
+PLACEMENTS = _placements()
