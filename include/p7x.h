@@ -758,6 +758,41 @@ void    p7x_emitted_destroy(p7x_emitted *b);
 int p7x_debug_philox(const uint32_t *key2, const uint32_t *ctr4, uint32_t *out4);
 int p7x_debug_emit_bytes(int64_t n, int64_t cap, int traces, int64_t budget, int64_t *bytes);
 
+/* ------------------------------------------------------------------ translation: p7x_translate.cpp, p7x_translate.hip
+ * Nucleotide codes ACGT-RYMKSWHBVDN*~ = 0..17 (RNA: U at 3), amino codes as everywhere; definitions: DESIGN.md 3.18.
+ * p7x_gencode_table: genetic code <table> (NCBI id): aa64[64] amino codes in NCBI order (first base slowest, each base in
+ * the order T, C, A, G), a description, and lut[18 * 18 * 18], indexed (c1 * 18 + c2) * 18 + c3: low seven bits the amino
+ * acid (a degenerate codon whose expansions agree translates to what they give, else to X), bit 7 set when the codon holds
+ * a gap, * or ~.  Any of the three may be NULL.  P7X_EINVAL for an unknown id.
+ * p7x_translate_codons: seq[len] in frame into out[len / 3] on the host; P7X_EINVAL when len is no multiple of three
+ * (*err_pos = -1) or a codon has bit 7 (*err_pos = its first base, from 0).
+ * p7x_translate_block: the same for every sequence of a block packed as p7x_seqdb_create takes it (255 x1..xL 255 ...,
+ * nres residues in all) on <device>: out_dsq[nres / 3 + n + 1] in the same packing, out_offsets / out_lengths[n].
+ * P7X_EINVAL with *err_seq and *err_pos for the first sequence whose length is no multiple of three (*err_pos = -1), else
+ * for the first codon that cannot be translated.  Debug option "host_translate" = 1 runs the host twin: the same bytes.
+ * p7x_orfs_find: the open reading frames of at least min_length codons of both strands (strands: P7X_STRAND_*), in the
+ * order sequence, watson before crick, first base along the translated strand.  The unit of work is a span of
+ * "orf_chunk" (debug option; 3..384, default 196) positions of the packed array, whatever the sequences: the output does
+ * not depend on it.  p7x_orfs_find_host is the twin ("host_translate" = 1 makes p7x_orfs_find call it); p7x_orfs_plan
+ * gives the chunk length in force and the chunks a block of nres residues in nseq sequences takes per pass and strand.
+ * P7X_ENODEVICE without a device, P7X_EMEM when workspace and output do not fit the device's free memory.
+ * info: 0 ORFs, 1 residues, 2 chunks, 3 microseconds of the kernels (device events), 4 found on the device, 5 chunk length,
+ * 6-9 microseconds of the passes (summaries, counts, heads, continuations), 10 of the host scans between them.
+ * copy: dsq[residues + n + 1], offsets / lengths / source / frame / start / end[n]. */
+typedef struct p7x_orfs p7x_orfs;
+int     p7x_gencode_table(int32_t table, uint8_t *aa64, char *desc, size_t desc_cap, uint8_t *lut);
+int     p7x_translate_codons(int32_t table, const uint8_t *seq, int64_t len, uint8_t *out, int64_t *err_pos);
+int     p7x_translate_block(int32_t table, int device, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, size_t n, int64_t nres,
+                            uint8_t *out_dsq, int64_t *out_offsets, int32_t *out_lengths, int64_t *err_seq, int64_t *err_pos);
+int     p7x_orfs_find(int32_t table, int device, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, size_t n, int64_t nres,
+                      int32_t min_length, int strands, p7x_orfs **out);
+int     p7x_orfs_find_host(int32_t table, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, size_t n, int64_t nres,
+                           int32_t min_length, int strands, int threads, p7x_orfs **out);
+int     p7x_orfs_plan(int64_t nres, int64_t nseq, int32_t *orf_chunk, int64_t *chunks);
+int64_t p7x_orfs_info(const p7x_orfs *b, int which);
+int     p7x_orfs_copy(const p7x_orfs *b, uint8_t *dsq, int64_t *offsets, int32_t *lengths, int64_t *source, int8_t *frame, int64_t *start, int64_t *end);
+void    p7x_orfs_destroy(p7x_orfs *b);
+
 /* ------------------------------------------------------------------ Builder.build_msa: p7x_msabuild.cpp, p7x_msabuild.hip
  * A protein alignment as a query (hmmbuild).  ax[N * L]: the digital codes of the rows, one after the other (gap 20).
  * p7x_msa_checksum: Jenkins' one-at-a-time hash over them, the CKSUM of the model.

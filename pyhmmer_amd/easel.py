@@ -6,7 +6,7 @@ Reference: ``src/pyhmmer/easel.pyx`` -- ``Alphabet`` (:183-528), ``TextSequence`
 (:7483), ``DigitalSequence`` (:7741), ``DigitalSequenceBlock`` (:8629-8665),
 ``SequenceFile`` (read / read_block), ``MSA`` / ``TextMSA`` / ``DigitalMSA`` as far as hmmalign needs them, and
 ``Randomness`` (:7006-7161), the generator the emitters of ``plan7`` draw from.  Everything else in ``pyhmmer.easel``
-(SSI, matrices, genetic codes, ...) is out of scope.
+(SSI, matrices, ...) is out of scope.
 
 The one deliberate difference from the reference: a ``DigitalSequenceBlock`` here can
 be *packed* once (``block.packed()``) into the flat ``dsq_concat + offsets + lengths``
@@ -21,8 +21,8 @@ from typing import Iterable, Iterator, List, Optional, Sequence as _Seq
 import numpy as np
 
 __all__ = [
-    "Alphabet", "Sequence", "TextSequence", "DigitalSequence",
-    "TextSequenceBlock", "DigitalSequenceBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness", "KeyHash",
+    "Alphabet", "GeneticCode", "Sequence", "TextSequence", "DigitalSequence",
+    "TextSequenceBlock", "DigitalSequenceBlock", "TranslatedBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness", "KeyHash",
 ]
 
 _AMINO = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -122,6 +122,96 @@ class Alphabet:
         return "".join(self.symbols[i] for i in arr.tolist())
 
 
+# reverse complement over Easel's nucleotide codes: A<->T C<->G R<->Y M<->K H<->D B<->V; S W N - * ~ stay
+_NT_COMPLEMENT = np.array([3, 2, 1, 0, 4, 6, 5, 8, 7, 9, 10, 14, 13, 12, 11, 15, 16, 17], dtype=np.uint8)
+_STRANDS = {None: 0, "watson": 1, "crick": 2}           # P7X_STRAND_*
+
+
+def _text_complement_table() -> bytes:
+    """IUPAC complement of a text sequence, case kept; any other byte maps to 0 (the caller writes N and warns)."""
+    tab = bytearray(256)
+    for a, b in zip("ACGTURYMKSWHBVDN", "TGCAAYRKMSWDVBHN"):
+        tab[ord(a)], tab[ord(a.lower())] = ord(b), ord(b.lower())
+    return bytes(tab)
+
+
+_TEXT_COMPLEMENT = _text_complement_table()
+# the same for the rows of an alignment: whatever is no IUPAC letter (gaps, *, ~) stays
+_TEXT_COMPLEMENT_KEEP = bytes(c or i for i, c in enumerate(_TEXT_COMPLEMENT))
+
+
+class GeneticCode:
+    """A genetic code table for translation (reference ``easel.pyx:557-716``).  The tables are NCBI's, written from the
+    standard code and the published differences; ``description`` is this package's own wording."""
+
+    __slots__ = ("nucleotide_alphabet", "amino_alphabet", "_table", "_description")
+
+    def __init__(self, translation_table: int = 1, *, nucleotide_alphabet: Optional[Alphabet] = None,
+                 amino_alphabet: Optional[Alphabet] = None):
+        from .errors import InvalidParameter
+        nucleotide_alphabet = Alphabet.dna() if nucleotide_alphabet is None else nucleotide_alphabet
+        amino_alphabet = Alphabet.amino() if amino_alphabet is None else amino_alphabet
+        if not nucleotide_alphabet.is_nucleotide():
+            raise InvalidParameter("nucleotide_alphabet", nucleotide_alphabet, hint="nucleotide alphabet")
+        if not amino_alphabet.is_amino():
+            raise InvalidParameter("amino_alphabet", amino_alphabet, hint="amino alphabet")
+        self.nucleotide_alphabet, self.amino_alphabet = nucleotide_alphabet, amino_alphabet
+        self.translation_table = translation_table
+
+    def __repr__(self) -> str:
+        ty = type(self).__name__
+        if self.nucleotide_alphabet.is_dna():
+            return f"{ty}({self.translation_table!r})"
+        return f"{ty}({self.translation_table!r}, nucleotide_alphabet={self.nucleotide_alphabet!r})"
+
+    def __reduce__(self):
+        import functools
+        return functools.partial(type(self), translation_table=self.translation_table,
+                                 nucleotide_alphabet=self.nucleotide_alphabet, amino_alphabet=self.amino_alphabet), ()
+
+    @property
+    def translation_table(self) -> int:
+        return self._table
+
+    @translation_table.setter
+    def translation_table(self, translation_table: int) -> None:
+        import ctypes as C
+        from . import _lib
+        from .errors import InvalidParameter
+        table = int(translation_table)
+        desc = C.create_string_buffer(128)
+        if not -2 ** 31 <= table < 2 ** 31 or _lib.lib().p7x_gencode_table(table, None, desc, 128, None) != 0:
+            raise InvalidParameter("translation_table", translation_table, hint="translation table code")
+        self._table, self._description = table, desc.value.decode("ascii")
+
+    @property
+    def description(self) -> str:
+        return self._description
+
+    def _tables(self):
+        """``(aa64, lut)``: the 64 amino codes in NCBI order and the Kp^3 codon lookup the library translates with."""
+        from . import _lib
+        aa64, lut = np.empty(64, dtype=np.uint8), np.empty(18 ** 3, dtype=np.uint8)
+        _lib.lib().p7x_gencode_table(self._table, aa64.ctypes.data, None, 0, lut.ctypes.data)
+        return aa64, lut
+
+    def translate(self, sequence) -> np.ndarray:
+        """Translate a raw digital nucleotide sequence (any buffer of codes) in frame: a ``uint8`` array of amino codes
+        (a numpy array where the reference returns a ``VectorU8``).  Degenerate codons whose expansions agree translate
+        to what they give (``GGR`` -> ``G``), the others to ``X``; `ValueError` for a length that is no multiple of three
+        and for a codon that holds a gap, ``*`` or ``~``."""
+        import ctypes as C
+        from . import _lib
+        seq = np.ascontiguousarray(np.frombuffer(sequence, dtype=np.uint8) if not isinstance(sequence, np.ndarray) else sequence, dtype=np.uint8)
+        if seq.shape[0] % 3 != 0:
+            raise ValueError(f"Invalid sequence of length {seq.shape[0]!r}")
+        out = np.empty(seq.shape[0] // 3, dtype=np.uint8)
+        bad = C.c_int64(-1)
+        if _lib.lib().p7x_translate_codons(self._table, seq.ctypes.data, seq.shape[0], out.ctypes.data, C.byref(bad)) != 0:
+            raise ValueError(_lib.last_error())
+        return out
+
+
 class Sequence:
     """Abstract biological sequence with metadata (reference ``easel.pyx`` ``Sequence``)."""
 
@@ -155,6 +245,22 @@ class TextSequence(Sequence):
     def copy(self) -> "TextSequence":
         return TextSequence(self.name, self.description, self.accession, self.sequence, self.source)
 
+    def reverse_complement(self, inplace: bool = False) -> Optional["TextSequence"]:
+        """The reverse complement, IUPAC letters complemented with their case kept; any other letter becomes ``N``, with a
+        `UserWarning` (reference ``easel.pyx:7688-7738``)."""
+        import warnings
+        raw = self.sequence.encode("ascii", "replace")[::-1]
+        rc = raw.translate(_TEXT_COMPLEMENT)
+        if 0 in rc:
+            rc = rc.replace(b"\0", b"N")
+            warnings.warn("reverse-complementing a text sequence with non-DNA characters", UserWarning, stacklevel=2)
+        if inplace:
+            self.sequence = rc.decode("ascii")
+            return None
+        out = self.copy()
+        out.sequence = rc.decode("ascii")
+        return out
+
 
 class DigitalSequence(Sequence):
     """A sequence stored as digital residue codes 0..Kp-1 (reference ``easel.pyx:7741``)."""
@@ -180,6 +286,29 @@ class DigitalSequence(Sequence):
     def copy(self) -> "DigitalSequence":
         return DigitalSequence(self.alphabet, self.name, self.description, self.accession,
                                self.sequence.copy(), self.source)
+
+    def translate(self, genetic_code: Optional["GeneticCode"] = None) -> "DigitalSequence":
+        """Translate the whole sequence in frame (reference ``easel.pyx:7996-8068``); the metadata is carried over."""
+        from .errors import AlphabetMismatch
+        genetic_code = GeneticCode() if genetic_code is None else genetic_code
+        if self.alphabet != genetic_code.nucleotide_alphabet:
+            raise AlphabetMismatch(genetic_code.nucleotide_alphabet, self.alphabet)
+        if len(self) % 3 != 0:
+            raise ValueError(f"Incomplete sequence of length {len(self)!r}")
+        return DigitalSequence(genetic_code.amino_alphabet, self.name, self.description, self.accession,
+                               genetic_code.translate(self.sequence), self.source)
+
+    def reverse_complement(self, inplace: bool = False) -> Optional["DigitalSequence"]:
+        """The reverse complement (reference ``easel.pyx:8070-8110``); `ValueError` for an alphabet without complements."""
+        if not self.alphabet.is_nucleotide():
+            raise ValueError(f"{self.alphabet} has no defined complement")
+        rc = _NT_COMPLEMENT[self.sequence[::-1]]
+        if inplace:
+            self.sequence = rc
+            return None
+        out = self.copy()
+        out.sequence = rc
+        return out
 
 
 class PackedBlock:
@@ -323,6 +452,68 @@ class DigitalSequenceBlock(_SequenceBlock):
             self._packed = PackedBlock(self._seqs)
         return self._packed
 
+    def _check_translatable(self, genetic_code: "GeneticCode") -> None:
+        from .errors import AlphabetMismatch
+        if self.alphabet != genetic_code.nucleotide_alphabet:
+            raise AlphabetMismatch(genetic_code.nucleotide_alphabet, self.alphabet)
+
+    def translate(self, genetic_code: Optional["GeneticCode"] = None, device: int = 0) -> "DigitalSequenceBlock":
+        """Translate every sequence whole and in frame, stops kept as ``*`` (reference ``easel.pyx:8765``), the whole block
+        at once on ``device`` (``p7x_translate.hip``; test seam ``host_translate``: the host twin).  Names, descriptions,
+        accessions and sources are carried over.  `ValueError` for a sequence whose length is no multiple of three or
+        that holds a codon with a gap, ``*`` or ``~``."""
+        import ctypes as C
+        from . import _lib
+        from .errors import status_to_exception
+        genetic_code = GeneticCode() if genetic_code is None else genetic_code
+        self._check_translatable(genetic_code)
+        pk = self.packed()
+        if pk.n == 0:
+            return DigitalSequenceBlock(genetic_code.amino_alphabet)
+        bad = np.flatnonzero(pk.lengths % 3)
+        if bad.size:
+            raise ValueError(f"Incomplete sequence of length {int(pk.lengths[bad[0]])!r} at index {int(bad[0])!r}")
+        dsq = np.empty(pk.total_residues // 3 + pk.n + 1, dtype=np.uint8)
+        offsets, lengths = np.empty(pk.n, dtype=np.int64), np.empty(pk.n, dtype=np.int32)
+        eseq, epos = C.c_int64(-1), C.c_int64(-1)
+        st = _lib.lib().p7x_translate_block(genetic_code.translation_table, int(device), pk.dsq.ctypes.data, pk.offsets.ctypes.data,
+                                            pk.lengths.ctypes.data, pk.n, pk.total_residues, dsq.ctypes.data, offsets.ctypes.data,
+                                            lengths.ctypes.data, C.byref(eseq), C.byref(epos))
+        if st == 11 and eseq.value >= 0:
+            raise ValueError(f"Failed to translate codon at index {epos.value!r} of the sequence at index {eseq.value!r}")
+        if st != 0:
+            raise status_to_exception(st, "p7x_translate_block", _lib.last_error())
+        abc = genetic_code.amino_alphabet
+        return DigitalSequenceBlock(abc, (DigitalSequence(abc, s.name, s.description, s.accession, dsq[o:o + L], s.source)
+                                          for s, o, L in zip(self, offsets.tolist(), lengths.tolist())))
+
+    def translate_orfs(self, genetic_code: Optional["GeneticCode"] = None, *, min_length: int = 20, strand: Optional[str] = None,
+                       device: int = 0) -> "TranslatedBlock":
+        """The open reading frames of the block (an extension): every maximal run of at least
+        ``min_length`` codons without a stop, in the three frames of both strands (``strand``: `None`, ``"watson"`` or
+        ``"crick"``), found on ``device`` for the whole block at once.  No start codon is asked for.  The result is an
+        amino `TranslatedBlock` for `hmmsearch` / `hmmscan` / `phmmer` / `hmmalign`, ordered by source sequence, watson
+        before crick, then by the first base along the translated strand."""
+        import ctypes as C
+        from . import _lib
+        from .errors import InvalidParameter, status_to_exception
+        genetic_code = GeneticCode() if genetic_code is None else genetic_code
+        self._check_translatable(genetic_code)
+        if strand not in _STRANDS:
+            raise InvalidParameter("strand", strand, choices=["watson", "crick", None])
+        if int(min_length) < 1:
+            raise InvalidParameter("min_length", min_length, hint="at least one codon")
+        pk = self.packed()
+        h = C.c_void_p()
+        st = _lib.lib().p7x_orfs_find(genetic_code.translation_table, int(device), pk.dsq.ctypes.data, pk.offsets.ctypes.data,
+                                      pk.lengths.ctypes.data, pk.n, pk.total_residues, int(min_length), _STRANDS[strand], C.byref(h))
+        if st != 0:
+            raise status_to_exception(st, "p7x_orfs_find", _lib.last_error())
+        try:
+            return TranslatedBlock(genetic_code.amino_alphabet, self, h)
+        finally:
+            _lib.lib().p7x_orfs_destroy(h)
+
 
 class _LazyDigitalSequenceBlock(DigitalSequenceBlock):
     """A block that exists only as the packed arrays the native FASTA parser produced (``p7x_fasta_parse``): a
@@ -379,6 +570,94 @@ class _LazyDigitalSequenceBlock(DigitalSequenceBlock):
 
     def packed(self) -> PackedBlock:
         return self._pk if self._list is None else super().packed()
+
+
+class TranslatedBlock(_LazyDigitalSequenceBlock):
+    """What `DigitalSequenceBlock.translate_orfs` returns: an amino block kept as packed arrays, and where every ORF
+    came from.  ``source_index`` (the sequence of the source block), ``frame`` (int8: 1..3 watson, -1..-3 crick), ``start``
+    and ``end`` (int64, in the source's own numbering from 1; ``start > end`` on crick) are numpy arrays with one entry per
+    ORF.  ORF ``n`` (from 1) is the `DigitalSequence` ``orf{n}``, made on demand, with the description
+    ``source={name} coords={start}..{end} length={aa} frame={frame}`` and ``source`` the source sequence's name; the name
+    and description tables a search reads are built when first asked for."""
+
+    __slots__ = ("source_block", "source_index", "frame", "start", "end", "on_device", "chunks", "orf_chunk", "kernel_us",
+                 "pass_us", "stitch_us", "_tables")
+
+    def __init__(self, alphabet: Alphabet, source: DigitalSequenceBlock, handle):
+        from . import _lib
+        from .errors import status_to_exception
+        lib = _lib.lib()
+        n, nres = int(lib.p7x_orfs_info(handle, 0)), int(lib.p7x_orfs_info(handle, 1))
+        self.chunks, self.kernel_us = int(lib.p7x_orfs_info(handle, 2)), int(lib.p7x_orfs_info(handle, 3))
+        self.on_device, self.orf_chunk = bool(lib.p7x_orfs_info(handle, 4)), int(lib.p7x_orfs_info(handle, 5))
+        self.pass_us = tuple(int(lib.p7x_orfs_info(handle, k)) for k in (6, 7, 8, 9))
+        self.stitch_us = int(lib.p7x_orfs_info(handle, 10))
+        dsq = np.empty(nres + n + 1, dtype=np.uint8)
+        offsets, lengths = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
+        self.source_index, self.frame = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int8)
+        self.start, self.end = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+        st = lib.p7x_orfs_copy(handle, dsq.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, self.source_index.ctypes.data,
+                               self.frame.ctypes.data, self.start.ctypes.data, self.end.ctypes.data)
+        if st != 0:
+            raise status_to_exception(st, "p7x_orfs_copy", _lib.last_error())
+        self.source_block = source
+        self._tables = None
+        self._list = None
+        self._pk = PackedBlock.from_arrays(dsq, offsets, lengths)
+        self.alphabet = alphabet
+        self._packed = self._pk
+        self._version = 0
+
+    def _source_name(self, i: int) -> str:
+        return self.source_block[int(self.source_index[i])].name
+
+    def _description(self, i: int) -> str:
+        return (f"source={self._source_name(i)} coords={int(self.start[i])}..{int(self.end[i])} "
+                f"length={int(self._pk.lengths[i])} frame={int(self.frame[i])}")
+
+    def _make(self, t: int) -> DigitalSequence:
+        o, L = int(self._pk.offsets[t]), int(self._pk.lengths[t])
+        return DigitalSequence(self.alphabet, name=f"orf{t + 1}", description=self._description(t), sequence=self._pk.dsq[o:o + L],
+                               source=self._source_name(t))
+
+    def _string_tables(self):
+        """The NUL-terminated string table of names and descriptions and the offsets into it, as the native FASTA parser
+        lays them out (`SequenceDatabase` hands pointers into it to the library)."""
+        if self._tables is None:
+            n = self._pk.n
+            names = [f"orf{i + 1}".encode() for i in range(n)]
+            src = [s.name for s in self.source_block]
+            descs = [f"source={src[k]} coords={a}..{b} length={L} frame={f}".encode()
+                     for k, a, b, L, f in zip(self.source_index.tolist(), self.start.tolist(), self.end.tolist(),
+                                              self._pk.lengths.tolist(), self.frame.tolist())]
+            sizes = np.fromiter((len(b) + 1 for pair in zip(names, descs) for b in pair), dtype=np.int64, count=2 * n)
+            at = np.zeros(2 * n + 1, dtype=np.int64)
+            np.cumsum(sizes, out=at[1:])
+            strtab = np.frombuffer(b"".join(b + b"\0" for pair in zip(names, descs) for b in pair) + b"\0", dtype=np.uint8)
+            self._tables = (strtab, at[0:2 * n:2].copy(), at[1:2 * n:2].copy())
+        return self._tables
+
+    _strtab = property(lambda self: self._string_tables()[0])
+    _name_off = property(lambda self: self._string_tables()[1])
+    _desc_off = property(lambda self: self._string_tables()[2])
+
+    def locate(self, x):
+        """Where a `Domain` (or the best domain of a `Hit`) of a search against this block lies on its source sequence:
+        ``(source_name, source_index, nt_from, nt_to, frame)``, nucleotides in the source's own numbering, ``nt_from >
+        nt_to`` on crick.  The ORF is found from the hit's name."""
+        dom = x.best_domain if hasattr(x, "best_domain") else x
+        name = dom.hit.name
+        if not name.startswith("orf") or not name[3:].isdigit() or not 1 <= int(name[3:]) <= self._pk.n:
+            raise ValueError(f"{name!r} is not an ORF of this block")
+        t = int(name[3:]) - 1
+        i, j = int(dom.alignment.target_from), int(dom.alignment.target_to)
+        start, frame = int(self.start[t]), int(self.frame[t])
+        if frame > 0:
+            nt = (start + 3 * (i - 1), start + 3 * j - 1)
+        else:
+            nt = (start - 3 * (i - 1), start - 3 * j + 1)
+        k = int(self.source_index[t])
+        return (self.source_block[k].name, k, nt[0], nt[1], frame)
 
 
 class SequenceFile:
@@ -847,6 +1126,24 @@ class DigitalMSA(MSA):
                                  self.pp_consensus, self.reference, self.secondary_structure)
         out._weights = None if self._weights is None else self._weights.copy()
         return out
+
+    def reverse_complement(self, inplace: bool = False) -> Optional["DigitalMSA"]:
+        """The reverse complement of every row, gaps kept (reference ``easel.pyx:6479-6523``); per-column annotation is
+        reversed with the columns.  `ValueError` for an alphabet without complements."""
+        if not self.alphabet.is_nucleotide():
+            raise ValueError(f"{self.alphabet} has no defined complement")
+        rev = lambda x: None if x is None else x[::-1]
+        rows = [r.encode("ascii")[::-1].translate(_TEXT_COMPLEMENT_KEEP).decode("ascii") for r in self._rows]
+        pp = None if self.posterior_probabilities is None else [rev(r) for r in self.posterior_probabilities]
+        out = self if inplace else DigitalMSA._from_rows(self._names, rows, self._descs, self._accs, alphabet=self.alphabet)
+        out._rows, out._code_matrix = rows, None
+        out.posterior_probabilities, out.pp_consensus = pp, rev(self.pp_consensus)
+        out.reference, out.secondary_structure = rev(self.reference), rev(self.secondary_structure)
+        if not inplace:
+            out.name, out.description, out.accession, out.author = self.name, self.description, self.accession, self.author
+            out._weights = None if self._weights is None else self._weights.copy()
+            return out
+        return None
 
     def _residue_mask(self) -> np.ndarray:
         """Residues are the canonical and the degenerate codes; the gap, ``*`` and ``~`` are none."""
