@@ -362,6 +362,14 @@ int64_t p7x_debug_ssv_merge_rows(int Q16, size_t n, const int64_t *pos, const in
  * model), "ssv_parts" (2 / 3 / 4: the scan in that many chained parts, for any model with two nodes for each; 0: the
  * library's plan).  Traces on stderr: "trace_finish", "trace_longtarget", "trace_envelope", "host_profile" (1: on). */
 int  p7x_debug_set_option(const char *name, int value);
+/* Test seam of the envelope kernel's schedule (csrc/p7x_envscore.hip: DeviceEnvelopeScorer::begin, all three modes), no HIP
+ * call: process-wide totals since the last reset, read before <reset> != 0 clears them.  out[0] = begin calls that had
+ * envelopes, [1] = jobs with envelopes, [2] = envelopes, [3] = kernel launches, [4] = wavefronts launched (the sum over jobs
+ * of nblocks * env_waves(C)), [5] = the sum over jobs of max(0, nenv - nblocks * env_waves(C)): at least this many envelopes
+ * came second or later in their wavefront, on a workspace slab another envelope had used, [6] = jobs whose queue order is
+ * not the identity, [7] = the most jobs in any one launch.  The option "env_blocks" = n (p7x_debug_set_option) gives a job at
+ * most n blocks, so that a small input runs the queue a library search runs. */
+int  p7x_debug_env_plan(int64_t out[8], int reset);
 int  p7x_debug_ensemble(const p7x_oprofile *om, const p7x_seqdb *db, int64_t target, int32_t i, int32_t j, uint32_t seed,
                         int use_device, int32_t *ndom, int32_t *dom, int32_t dom_cap, float *n2, int32_t *status);
 /* Test seams of the float64 reference of the ensembles (tests/ensemble_reference.py); additions, the ABI number stays.

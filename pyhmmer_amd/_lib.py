@@ -246,6 +246,7 @@ _SIGNATURES = {
     "p7x_debug_ssv_part_tables": (C.c_int64, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t]),
     "p7x_debug_ssv_merge_rows": (C.c_int64, [C.c_int, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "p7x_debug_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+    "p7x_debug_env_plan": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "p7x_longtargets_release_resident": (C.c_int, [C.c_int, C.c_uint64]),
     "p7x_debug_ensemble": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int, _VP, _VP, C.c_int32, _VP, _VP]),
     "p7x_debug_ens_walk_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -379,3 +380,11 @@ def set_debug_option(name: str, value: int) -> None:
     """Test / diagnostic seam (``p7x_debug_set_option``): kernel-family choices for parity tests, traces.  -1 unsets."""
     if lib().p7x_debug_set_option(name.encode(), int(value)) != 0:
         raise ValueError(last_error())
+
+
+def env_plan(reset: bool = False):
+    """Test seam (``p7x_debug_env_plan``): the eight totals of the envelope kernel's schedule since the last reset."""
+    out = (C.c_int64 * 8)()
+    if lib().p7x_debug_env_plan(out, int(bool(reset))) != 0:
+        raise ValueError(last_error())
+    return [int(v) for v in out]

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 
 namespace p7x {
@@ -36,6 +37,10 @@ static size_t env_budget_bytes(int option)
 }
 
 size_t align_budget_bytes() { return env_budget_bytes(OPT_ALIGN_WORKSPACE_GB); }
+
+// What begin() planned, process-wide, for the test seam p7x_debug_env_plan (include/p7x.h names the eight fields).
+static std::mutex g_env_plan_mu;
+static int64_t g_env_plan[8];
 
 class DeviceEnvelopeScorer final : public EnvelopeScorer {
 public:
@@ -131,7 +136,9 @@ public:
         // the jobs share the resident blocks in proportion to their envelopes; a job with more envelopes than wavefronts
         // hands them out longest first (EnvArgs::order / cursor)
         const int share = (int) std::max<int64_t>(1, (int64_t) cap_blocks * m.nenv / nenv_tot);
-        m.nblocks = std::max(1, std::min(share, (m.nenv + env_waves(m.C) - 1) / env_waves(m.C)) / shrink);
+        // (test seam "env_blocks": at most that many blocks per job, so that a few envelopes queue up behind each wavefront)
+        const int forced = debug_opt(OPT_ENV_BLOCKS) > 0 ? debug_opt(OPT_ENV_BLOCKS) : share;
+        m.nblocks = std::max(1, std::min({ share, (m.nenv + env_waves(m.C) - 1) / env_waves(m.C), forced }) / shrink);
         m.stride = env_work_floats(m.C, class_Lmax[m.C]);
         work_floats += (size_t) m.nblocks * env_waves(m.C) * m.stride;
       }
@@ -217,6 +224,21 @@ public:
       if ((st = env_launch(mode, ar, s)) != P7X_OK) return st;
     }
     tick("launches");
+    {
+      int64_t plan[8] = { 1, 0, nenv_tot, (int64_t) runs.size(), 0, 0, 0, 0 };
+      for (size_t j = 0; j < nj; ++j) {
+        const JobMeta &m = meta_[j];
+        if (m.nenv == 0) continue;
+        const int64_t waves = (int64_t) m.nblocks * env_waves(m.C);
+        plan[1] += 1; plan[4] += waves; plan[5] += std::max<int64_t>(0, m.nenv - waves);
+        const int32_t *ord = env_order + m.first;
+        for (int r = 0; r < m.nenv; ++r) if (ord[r] != r) { plan[6] += 1; break; }
+      }
+      for (const auto &run : runs) plan[7] = std::max<int64_t>(plan[7], run.second);
+      std::lock_guard<std::mutex> lock(g_env_plan_mu);
+      for (int f = 0; f < 7; ++f) g_env_plan[f] += plan[f];
+      g_env_plan[7] = std::max(g_env_plan[7], plan[7]);
+    }
     P7X_HIP(hipMemcpyAsync(eb->h_out.as<void>(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
     tick("d2h");
     if (debug) std::fprintf(stderr, "[env begin] jobs %zu envelopes %lld runs %zu work %.1f MB out %.1f MB:%s ms\n", nj, (long long) nenv_tot, runs.size(),
@@ -286,3 +308,11 @@ std::unique_ptr<EnvelopeScorer> make_device_align_scorer(DeviceCtx *ctx, const p
 }
 
 } // namespace p7x
+
+extern "C" int p7x_debug_env_plan(int64_t out[8], int reset)
+{
+  if (!out) { p7x::set_error("p7x_debug_env_plan: bad arguments"); return P7X_EINVAL; }
+  std::lock_guard<std::mutex> lock(p7x::g_env_plan_mu);
+  for (int f = 0; f < 8; ++f) { out[f] = p7x::g_env_plan[f]; if (reset) p7x::g_env_plan[f] = 0; }
+  return P7X_OK;
+}

@@ -13,7 +13,16 @@ three times.
 
 "rnd1100 long": a full-length emission of random_hmm(1100), about 1,000 residues -- float32 sums over Ld rows.
 "rnd300 edges": an envelope from residue 1 to residue L (no flanks), a homologue with X, B and Z in 10 % of its residues, and
-a homologue followed by '*'."""
+a homologue followed by '*'.
+
+"rnd<M> queue" (QUEUE_LABELS, not part of LABELS): many short fragments of one model, so that a search forced onto one block
+(the test option env_blocks) hands every wavefront several envelopes of different lengths, one after the other through the
+same workspace slab -- tests/test_gpu_envelope_queue.py.  M = 64, 320, 512, 1025, 2049 and 4097: eight wavefronts per block,
+four of them from 512 on, emissions out of LDS, rolled loops, transitions through L2.  QUEUE_TARGETS[M] targets of one
+fragment each, the window lengths spread evenly from QUEUE_MIN_NODES nodes to min(M, 300) (120 from M = 2049 on), every
+third window ending at node M and every third lying across nodes 32 C and 32 C + 1; the block lists them shortest first, the
+reverse of the queue's order.  One more target carries six fragments 80 random residues apart: six envelopes of one item at
+different offsets into the sequence."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -31,10 +40,16 @@ MAX_FLANK = 50
 # A seed is replaced here when a fragment of random_hmm(M, seed = 7000 + M) is not one single-domain hit (M = 5: the third
 # emission of seed 7005 lies in a region that the traceback ensemble resolves).
 MODEL_SEEDS = {5: 7108}
-TARGET_SALTS = {}
+# ("rnd2049 queue", "q01"): the 44-node fragment of salt 0 passes no filter; salt 1 is a hit.
+TARGET_SALTS = {("rnd2049 queue", "q01"): 1}
 # The whole emission of a 5-node model scores 2-10 bits: no filter lets it through, so this model's searches run with the
 # filters open and every target reaches the domain definition.
 PIPELINE_OPTIONS = {"rnd5": dict(F1=1.0, F2=1.0, F3=1.0, E=1e3, domE=1e3)}
+QUEUE_LENGTHS = (64, 320, 512, 1025, 2049, 4097)
+QUEUE_TARGETS = {64: 36, 320: 36, 512: 18, 1025: 18, 2049: 10, 4097: 10}
+QUEUE_MIN_NODES = 40
+QUEUE_SPACER = 80
+QUEUE_MULTI = 6
 
 _models, _ref_models, _refs = {}, {}, {}
 
@@ -105,7 +120,9 @@ def targets(label):
     hmm = model(label)
     M = hmm.M
     named = []
-    if label.endswith(" long"):
+    if label.endswith(" queue"):
+        named = _queue_targets(label, hmm)
+    elif label.endswith(" long"):
         rng = _rng(label, "full")
         named.append((f"{label}_full".replace(" ", "_"), _between_flanks(rng, emit_window(hmm, rng, 1, M))))
     elif label.endswith(" edges"):
@@ -126,9 +143,75 @@ def targets(label):
     return named
 
 
+def queue_windows(M):
+    """(name, first node, last node) of the single-fragment targets of "rnd<M> queue", shortest first."""
+    top = min(M, FRAGMENT_NODES) if M <= 1025 else 120
+    mid = 32 * tier_of(M)
+    out = []
+    for t, n in enumerate(np.linspace(QUEUE_MIN_NODES, top, QUEUE_TARGETS[M]).round().astype(int)):
+        n = int(n)
+        if t % 3 == 0:
+            a = M - n + 1                                                    # ends at node M
+        elif t % 3 == 1:
+            a = min(max(1, mid - n // 2 + 1), M - n + 1)                     # across nodes 32 C and 32 C + 1
+        else:
+            a = 1 + (7919 * (t + 1)) % (M - n + 1)                           # anywhere
+        out.append((f"q{t:02d}", a, a + n - 1))
+    return out
+
+
+def _queue_targets(label, hmm):
+    M = hmm.M
+    named = []
+    for name, first, last in queue_windows(M):
+        rng = _rng(label, name)
+        named.append((f"rnd{M}_{name}", _between_flanks(rng, emit_window(hmm, rng, first, last))))
+    rng = _rng(label, "multi")
+    wins = queue_windows(M)
+    parts = [_flank(rng)]
+    for f in range(QUEUE_MULTI):                                             # lengths from both ends of the range, mixed
+        _, first, last = wins[(f * 7 + 3) % len(wins)]
+        parts += [emit_window(hmm, rng, first, last), rng.integers(0, 20, size=QUEUE_SPACER)]
+    parts[-1] = _flank(rng)
+    named.append((f"rnd{M}_multi", np.concatenate(parts).astype(np.uint8)))
+    return named
+
+
+BATCH_FRAGMENTS = {300: 26, 310: 9, 320: 1, 100: 5}      # single-fragment targets per query; M = 300 gets one more with four fragments
+BATCH_NODES = {300: (60, 150), 310: (60, 150), 320: (320, 320), 100: (60, 100)}
+BATCH_SILENT = 200                                       # a query with no fragment in the block
+_batch = []
+
+
+def batch_case():
+    """(models, [(name, residues)]): five queries for one batched search against one block -- three of one nodes-per-lane
+    class (M = 300, 310, 320: C = 5) with about 30, 9 and 1 envelopes, one of another class (M = 100) and one that hits
+    nothing.  The one envelope of M = 320 is the whole model, the class's longest by a factor of two: the slabs of the
+    other two jobs are sized by it and not by their own fragments of 60 to 150 nodes (shortest first per query; one target
+    holds four fragments of the first model)."""
+    if not _batch:
+        named = []
+        for M, n in BATCH_FRAGMENTS.items():
+            hmm = model(label_of(M))
+            for t, nodes in enumerate(np.linspace(*BATCH_NODES[M], n).round().astype(int)):
+                rng = _rng("batch", f"b{M}_{t}")
+                first = 1 + (7919 * (t + 1)) % (M - int(nodes) + 1)
+                named.append((f"b{M}_{t:02d}", _between_flanks(rng, emit_window(hmm, rng, first, first + int(nodes) - 1))))
+        hmm = model(label_of(300))
+        rng = _rng("batch", "four")
+        parts = [_flank(rng)]
+        for first, last in ((1, 90), (151, 300), (40, 180), (200, 300)):
+            parts += [emit_window(hmm, rng, first, last), rng.integers(0, 20, size=QUEUE_SPACER)]
+        parts[-1] = _flank(rng)
+        named.append(("b300_four", np.concatenate(parts).astype(np.uint8)))
+        _batch.append(([model(label_of(M)) for M in (300, 310, 320, 100, BATCH_SILENT)], named))
+    return _batch[0]
+
+
 TIER_LABELS = tuple(label_of(M) for M in TIER_LENGTHS)
 EXTRA_LABELS = ("rnd1100 long", "rnd300 edges")
 LABELS = TIER_LABELS + EXTRA_LABELS
+QUEUE_LABELS = tuple(f"rnd{M} queue" for M in QUEUE_LENGTHS)
 
 
 def pipeline_options(label):

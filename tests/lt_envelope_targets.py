@@ -16,7 +16,12 @@ Models shorter than the window: the whole emission, three times.  Searches run w
 "rnd1100 long": full-length emissions of random_hmm(1100), about 1,000 residues each, one per strand -- float32 sums over
 Ld rows, and nothing for the second round to trim.
 "rnd300 edges": full-length emissions, one per strand, with N and the two-letter IUPAC codes in 10 % of their residues: the
-degenerate rows of the per-envelope table and the fractional counts of the composition."""
+degenerate rows of the per-envelope table and the fractional counts of the composition.
+
+QUEUE_LABEL, "rnd320 queue" (not part of LABELS): the DNA model of the tier C = 5 and one contig with QUEUE_FRAGMENTS planted
+fragments of 60 nodes up to the whole model (320: the model has no 400), alternating strands, shortest first, 1,400 residues
+apart -- so that a search forced onto one block (the test option env_blocks) hands every wavefront several envelopes, each
+with its own emission table, through one workspace slab: tests/test_gpu_envelope_queue.py."""
 import numpy as np
 
 import envelope_targets as ET
@@ -45,6 +50,10 @@ TARGET_SALTS = {("rnd64", "boundary"): 2, ("rnd65", "first"): 1, ("rnd2049", "bo
                 # are no hits; salt 3 is one and has no such cell.  The "last" fragment keeps its near-tie.
                 ("rnd8193", "boundary"): 3}
 DEGENERATE_CODES = (15, 5, 6, 7, 8, 9, 10)          # N; R Y M K S W
+QUEUE_LABEL = "rnd320 queue"
+QUEUE_FRAGMENTS = 16
+QUEUE_NODES = (60, 400)
+QUEUE_FIRST, QUEUE_STEP = 1_000, 1_400
 
 _models, _targets, _ref_models, _refs = {}, {}, {}, {}
 
@@ -73,6 +82,17 @@ def windows(M):
     return (("first", 1, n, False), ("last", M - n + 1, M, True), ("boundary", a, a + n - 1, False))
 
 
+def queue_windows(M):
+    """(name, first node, last node, reverse strand) of the fragments of QUEUE_LABEL, shortest first."""
+    mid = 32 * ET.tier_of(M)
+    out = []
+    for t, n in enumerate(np.linspace(QUEUE_NODES[0], min(QUEUE_NODES[1], M), QUEUE_FRAGMENTS).round().astype(int)):
+        n = int(n)
+        a = (M - n + 1, min(max(1, mid - n // 2 + 1), M - n + 1), 1 + (7919 * (t + 1)) % (M - n + 1))[t % 3]
+        out.append((f"q{t:02d}", a, a + n - 1, t % 2 == 1))
+    return out
+
+
 def _rng(label, name):
     return np.random.default_rng([sum(label.encode()), sum(name.encode()), TARGET_SALTS.get((label, name), 0), 16])
 
@@ -90,8 +110,12 @@ def target(label):
         plan = (("degenerate", 1, M, False), ("degenerate_rev", 1, M, True))
     else:
         plan = windows(M)
+    positions = POSITIONS
+    if label.endswith(" queue"):
+        plan = queue_windows(M)
+        positions = tuple(QUEUE_FIRST + QUEUE_STEP * t for t in range(len(plan)))
     planted = []
-    for pos, (name, first, last, rev) in zip(POSITIONS, plan):
+    for pos, (name, first, last, rev) in zip(positions, plan):
         rng = _rng(label, name)
         frag = ET.emit_window(hmm, rng, first, last).astype(np.uint8)
         if label.endswith(" edges"):

@@ -60,6 +60,13 @@ MEASURED_ENV = {
     "rnd12288": dict(envsc=5.5e-05, corr=2.5e-04, oasc=1.4e-04),
     "rnd300 edges": dict(envsc=5.6e-05, corr=7.5e-05, oasc=1.7e-04),
     "rnd1100 long": dict(envsc=1.6e-04, corr=2.2e-03, oasc=3.7e-04),
+    # the queue labels (T.QUEUE_LABELS, profiles/r29_envelope_queue.md): 43-47 envelopes, 25-26 at M = 512 and 1025, 16-17 from 2049 on
+    "rnd64 queue": dict(envsc=7.8e-06, corr=4.5e-05, oasc=4.8e-05),
+    "rnd320 queue": dict(envsc=4.6e-05, corr=3.5e-04, oasc=3.5e-04),
+    "rnd512 queue": dict(envsc=6.1e-05, corr=2.9e-04, oasc=1.7e-04),
+    "rnd1025 queue": dict(envsc=5.4e-05, corr=3.8e-04, oasc=5.3e-04),
+    "rnd2049 queue": dict(envsc=1.2e-05, corr=7.9e-05, oasc=6.2e-05),
+    "rnd4097 queue": dict(envsc=7.4e-06, corr=1.1e-04, oasc=9.9e-05),
     "KR": dict(envsc=2.6e-06, corr=2.3e-04, oasc=3.3e-04),                 # 12 envelopes of 9 hits, 2 of them clustered
     "PF02826": dict(envsc=7.9e-06, corr=1.4e-04, oasc=1.0e-04),            # 38 envelopes of 22 hits, 8 of them clustered
     "Thioesterase": dict(envsc=2.3e-07, corr=2.7e-06, oasc=3.8e-06),       # its one hit
@@ -215,7 +222,7 @@ def oracle_distances(oracle, key, hmm, named, planted=True):
     return w
 
 
-@pytest.mark.parametrize("label", T.LABELS)
+@pytest.mark.parametrize("label", T.LABELS + T.QUEUE_LABELS)
 def test_oracle_envelopes_against_the_reference(libp7x, oracle, label, report):
     hmm = T.model(label)
     w = oracle_distances(oracle, label.split()[0], hmm, T.targets(label))
@@ -262,7 +269,7 @@ def host_distances(oracle, key, label, hmm, block, named, factor, planted=True):
     return w
 
 
-@pytest.mark.parametrize("label", T.LABELS)
+@pytest.mark.parametrize("label", T.LABELS + T.QUEUE_LABELS)
 def test_host_stage_envelopes_against_the_reference(libp7x, oracle, label, report):
     """Upstream's order: the oracle's operations on the oracle's operands, so the oracle's bound (CPU_FACTOR).  score, bias and
     accuracy follow through finish_one's formulas."""
@@ -273,7 +280,7 @@ def test_host_stage_envelopes_against_the_reference(libp7x, oracle, label, repor
     assert w.full >= len(named)
 
 
-@pytest.mark.parametrize("label", T.LABELS)
+@pytest.mark.parametrize("label", T.LABELS + T.QUEUE_LABELS)
 def test_host_stage_in_the_device_order_against_the_reference(libp7x, oracle, device_order, label, report):
     """host_order = 1, the lane-chunk association of the kernels: the device's bound (DEVICE_FACTOR, with the floors)."""
     hmm = T.model(label)
@@ -310,3 +317,31 @@ def test_fixture_envelopes_against_the_reference(libp7x, oracle, proteome, name,
             _lib.set_debug_option("host_order", -1)
         report(f"host stage {name}, {'device' if order == 1 else 'upstream'}'s order: {wh.line()}")
         assert wh.n >= w.full
+
+
+# ------------------------------------------------------------------------------------------------ the queue labels' inputs
+@pytest.mark.parametrize("label", T.QUEUE_LABELS)
+def test_queue_targets_are_what_the_queue_tests_need(libp7x, oracle, label):
+    """The block lists the fragments shortest first (the queue hands them out longest first: a real permutation), a window
+    ends at node M and one lies across nodes 32 C and 32 C + 1, every target is a hit of single-domain regions, and the last
+    target gives one envelope per planted fragment at least -- several envelopes of one item."""
+    hmm = T.model(label)
+    M = hmm.M
+    wins = T.queue_windows(M)
+    assert len(wins) == T.QUEUE_TARGETS[M]
+    nodes = [last - first + 1 for _, first, last in wins]
+    assert nodes == sorted(nodes) and nodes[0] == T.QUEUE_MIN_NODES and nodes[-1] == (min(M, T.FRAGMENT_NODES) if M <= 1025 else 120)
+    mid = 32 * T.tier_of(M)
+    assert any(last == M for _, _, last in wins) and any(first <= mid < last for _, first, last in wins)
+    assert all(1 <= first <= last <= M for _, first, last in wins)
+    named = T.targets(label)
+    assert len(named) == len(wins) + 1 and len({n for n, _ in named}) == len(named)
+    opts = T.pipeline_options(label)
+    hits = host_pipeline.host_search(oracle, hmm, T.search_block(hmm, named), pipeline=plan7.Pipeline(hmm.alphabet, **opts),
+                                     F=(opts.get("F1", 0.02), opts.get("F2", 1e-3), opts.get("F3", 1e-5)))
+    by_name = {h.name: h for h in hits}
+    for name, _ in named:
+        assert name in by_name and by_name[name].nclustered == 0 and len(by_name[name].domains) >= 1, (label, name)
+    assert len(by_name[named[-1][0]].domains) >= T.QUEUE_MULTI
+    nenv = sum(len(by_name[name].domains) for name, _ in named)
+    assert nenv >= 2 * (8 if M <= 448 else 4)                   # twice env_waves(C) of p7x_envkernel.hpp, at the least

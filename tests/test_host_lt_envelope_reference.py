@@ -68,6 +68,7 @@ MEASURED_LT = {
     "rnd12288": dict(orig=3.1e-06, corr=1.2e-05, oasc=2.2e-04),
     "rnd1100 long": dict(orig=8.5e-05, corr=1.1e-04, oasc=2.1e-03),
     "rnd300 edges": dict(orig=3.9e-06, corr=1.1e-05, oasc=3.4e-04),
+    "rnd320 queue": dict(orig=6.5e-06, corr=1.8e-05, oasc=2.6e-04),          # T.QUEUE_LABEL: 17 envelopes of 16 fragments (profiles/r29_envelope_queue.md)
 }
 CPU_FACTOR = 2.0
 DEVICE_FACTOR = 4.0               # another association of the same float32 terms
@@ -266,7 +267,7 @@ def oracle_distances(oracle, label):
     return w
 
 
-@pytest.mark.parametrize("label", T.LABELS)
+@pytest.mark.parametrize("label", T.LABELS + (T.QUEUE_LABEL,))
 def test_oracle_envelopes_against_the_reference(libp7x, oracle, label, report):
     w = oracle_distances(oracle, label)
     report(f"oracle {label}: {w.line()}")
@@ -314,7 +315,7 @@ def hits_against_the_reference(label, hits, wins, factor, line=None):
     return w, derived
 
 
-@pytest.mark.parametrize("label", T.LABELS)
+@pytest.mark.parametrize("label", T.LABELS + (T.QUEUE_LABEL,))
 def test_host_stage_envelopes_against_the_reference(libp7x, oracle, label, report):
     """The host workers (upstream's order of operations, the oracle's): the oracle's bound, CPU_FACTOR.  Score, bias and
     accuracy follow through lt_window_hits' formula."""
