@@ -360,7 +360,8 @@ int64_t p7x_debug_ssv_merge_rows(int Q16, size_t n, const int64_t *pos, const in
  * with host ensembles, where their clustered envelopes are rescored), "env_workspace_gb" (cap of the envelope kernel's
  * workspace), "ssv_kernel" (long-target SSV scan: 3 = the row maximum in every row, 4 = in every second row whatever the
  * model), "ssv_parts" (2 / 3 / 4: the scan in that many chained parts, for any model with two nodes for each; 0: the
- * library's plan).  Traces on stderr: "trace_finish", "trace_longtarget", "trace_envelope", "host_profile" (1: on). */
+ * library's plan), "ssv_scan_chunk" (n: the chunk length of the batched scan, a multiple of 64 >= 64 whatever the model).
+ * Traces on stderr: "trace_finish", "trace_longtarget", "trace_envelope", "host_profile" (1: on). */
 int  p7x_debug_set_option(const char *name, int value);
 /* Test seam of the envelope kernel's schedule (csrc/p7x_envscore.hip: DeviceEnvelopeScorer::begin, all three modes), no HIP
  * call: process-wide totals since the last reset, read before <reset> != 0 clears them.  out[0] = begin calls that had
@@ -436,6 +437,60 @@ int p7x_longtarget_from_seeds(const p7x_pipeline_cfg *cfg, const p7x_oprofile *o
                               const char *const *names, const char *const *accs, const char *const *descs,
                               const int64_t *seed_target, const int64_t *seed_block, const int32_t *seed_strand,
                               const int64_t *seeds, size_t nseeds, p7x_tophits **out);
+
+/* nhmmscan: ONE long nucleotide sequence against a library of models (the scan orientation of p7x_search_longtargets; an
+ * extension: pyhmmer's LongTargetsPipeline.scan_seq raises).  Additions of ABI 8: the number and p7x_pipeline_cfg stay.
+ *
+ * p7x_lt_library: the SSV tables of a batch of optimized profiles on one device, built and uploaded once and scanned by any
+ * number of query sequences.  The profiles must outlive it.  Which launch a model goes into (p7x_debug_ssv_batch_plan) is
+ * fixed when the library is created, from the options "ssv_kernel" / "ssv_parts" as they are then.
+ *
+ * p7x_scan_longtargets: sequence dsq[1..L] (dsq[0] and dsq[L+1] hold a code outside the alphabet) against oms[0..nmodels-1].
+ * The SSV scan of all models runs as one launch per (register tile, row flavour) group over one upload of the sequence
+ * (resident_key != 0: the upload is kept as cfg.lt_resident_key keeps it); a model that the scan takes in chained parts
+ * (M > 6,141, or "ssv_parts") goes through the single-model scan.  Then, per model and side by side on the cfg.host_threads
+ * workers, exactly what p7x_search_longtargets does with that model's rows: seeds per (block, strand), windows, domains.
+ * out[m] is what a lone p7x_search_longtargets of model m against the sequence returns -- E-values for this sequence's
+ * residues, duplicates removed, thresholds applied --; a model without seeds gets its empty list without touching the
+ * device again.  evalue_window_lengths (may be NULL): per model, what cfg.evalue_window_length is for a lone search of it
+ * (<= 0: the scan's).  lib (may be NULL: tables built for this call) must have been created from the same oms. */
+typedef struct p7x_lt_library p7x_lt_library;
+int  p7x_lt_library_create(const p7x_oprofile *const *oms, size_t nmodels, int device, p7x_lt_library **out);
+void p7x_lt_library_destroy(p7x_lt_library *lib);
+int  p7x_scan_longtargets(const p7x_pipeline_cfg *cfg, const p7x_oprofile *const *oms, size_t nmodels, int device,
+                          const uint8_t *dsq, int64_t L, const char *name, const char *acc, const char *desc,
+                          const int32_t *evalue_window_lengths, p7x_lt_library *lib, uint64_t resident_key, p7x_tophits **out);
+/* The per-model lists of one query sequence (p7x_scan_longtargets, or any finished or unfinished long-target lists of
+ * single-model searches against that one sequence) -> one scan-mode hit list.  Host code, no device.  Every model's hits are
+ * finished as its lone search finishes them (an unfinished list: p7_tophits_ComputeNhmmerEvalues with its own residue count
+ * and window length, duplicates removed WITHIN the model), renamed to the model's name / accession / description, numbered
+ * model_index[m] (NULL: in the order they come, continuing a list begun earlier), and appended to *inout (NULL: a new list
+ * for the sequence name / acc / desc / length).  Hits of different models that overlap on the sequence are all kept.
+ * nmodels_total > 0 finishes the list: the lnP of every hit and domain gets + log(nmodels_total) -- upstream's nhmmscan
+ * scales the E-value by the number of models the same way --, the hits are sorted by key, and reporting and inclusion are
+ * thresholded on the scaled values.  nmodels_total == 0: more batches follow (a library of unknown size: finish with a last
+ * call, nmodels = 0 allowed); nmodels_total < 0: finish, the models collected so far are the whole library (none: an empty
+ * list).  The per-model lists are left to the caller.  The result does not depend on how the models
+ * were dealt into calls, nor on their order when model_index is given. */
+int  p7x_scan_collect_longtargets(p7x_tophits *const *per_model, const int64_t *model_index, size_t nmodels, int64_t nmodels_total,
+                                  const p7x_pipeline_cfg *cfg, const char *name, const char *acc, const char *desc, int64_t length,
+                                  p7x_tophits **inout);
+/* Test seam: the seeds of one strand of dsq[0..L-1] for every model of a batch through the batched scan, as
+ * p7x_ssv_longtarget_seeds gives them for one: model after model in <seeds> (cap x 3 int64), count[m] of them for model m.
+ * Returns the total (may exceed cap) or a negative status. */
+int64_t p7x_ssv_longtarget_seeds_batch(const p7x_pipeline_cfg *cfg, const p7x_oprofile *const *oms, size_t nmodels, int device,
+                                       const uint8_t *dsq, int64_t L, int complement, int64_t *seeds, size_t cap, int64_t *count);
+/* Host only: the launches of the batched scan for models of M[i] nodes that lose at most pair_slack[i] units per row, under
+ * the options as they are.  launch_of[i] = the model's launch, -1: it goes through the single-model scan (chained parts).
+ * Per launch (at most cap are written): R, PAIR (0 / 1) and the dynamic LDS in bytes.  lds_limit (may be NULL): the most a
+ * launch may ask for.  Returns the number of launches or a negative status. */
+int  p7x_debug_ssv_batch_plan(const int32_t *M, const int32_t *pair_slack, int n, int32_t *launch_of, int32_t *launch_R,
+                              int32_t *launch_pair, int64_t *launch_lds, int cap, int64_t *lds_limit);
+/* Process-wide totals of the batched scan since the last reset (read before <reset> != 0 clears them): out[0] = libraries
+ * whose tables were built and uploaded, [1] = scans, [2] = batched launches, [3] = models scanned in batched launches,
+ * [4] = models that went through the single-model scan, [5] = scans repeated with a larger record buffer, [6] = the last
+ * scan's kernel time in microseconds (HIP events), [7] = its cells (rows x nodes, warm-up not counted). */
+int  p7x_debug_ssv_batch_stats(int64_t out[8], int reset);
 
 /* The Forward parser score (nats) of residues dsq[1..L] in the summation order of the reference's striped vectors
  * (impl_sse/fwdback.c forward_engine, do_full = FALSE; multihit, length model of L): what the host stage uses to decide

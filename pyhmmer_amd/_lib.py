@@ -255,6 +255,16 @@ _SIGNATURES = {
     "p7x_search_batch_raw": (C.c_int, [C.POINTER(PipelineCfg), C.POINTER(_VP), C.c_size_t, _VP, _VP, _VP, _VP, _VP]),
     "p7x_search_longtargets": (C.c_int, [C.POINTER(PipelineCfg), _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.POINTER(_VP)]),
     "p7x_ssv_longtarget_seeds": (C.c_int64, [C.POINTER(PipelineCfg), _VP, C.c_int, _VP, C.c_int64, C.c_int, _VP, C.c_size_t]),
+    "p7x_lt_library_create": (C.c_int, [C.POINTER(_VP), C.c_size_t, C.c_int, C.POINTER(_VP)]),
+    "p7x_lt_library_destroy": (None, [_VP]),
+    "p7x_scan_longtargets": (C.c_int, [C.POINTER(PipelineCfg), C.POINTER(_VP), C.c_size_t, C.c_int, _VP, C.c_int64, C.c_char_p, C.c_char_p,
+                                       C.c_char_p, _VP, _VP, C.c_uint64, C.POINTER(_VP)]),
+    "p7x_scan_collect_longtargets": (C.c_int, [C.POINTER(_VP), _VP, C.c_size_t, C.c_int64, C.POINTER(PipelineCfg), C.c_char_p, C.c_char_p,
+                                               C.c_char_p, C.c_int64, C.POINTER(_VP)]),
+    "p7x_ssv_longtarget_seeds_batch": (C.c_int64, [C.POINTER(PipelineCfg), C.POINTER(_VP), C.c_size_t, C.c_int, _VP, C.c_int64, C.c_int, _VP,
+                                                   C.c_size_t, _VP]),
+    "p7x_debug_ssv_batch_plan": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, _VP]),
+    "p7x_debug_ssv_batch_stats": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "p7x_forward_parser_exact": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_float)]),
     "p7x_longtarget_from_seeds": (C.c_int, [C.POINTER(PipelineCfg), _VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                             C.c_size_t, C.POINTER(_VP)]),

@@ -312,5 +312,33 @@ int  ssvlong_capacity(int R, bool pair, bool half, int num_cu, long long *waves)
 // <bin> / <bout>: the part takes its cell 0 from the boundary buffer / leaves its last cell there
 int  ssvlong_launch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st, bool bin = false, bool bout = false);
 
+// ---- the batched long-target SSV scan (p7x_ssvlong.hip; nhmmscan): one target, many models, a model per blockIdx.y.
+// What a block reads of its model.  Every model of a launch has the launch's R, rows (PAIR) and cells (H).
+struct SsvModelRec {
+  long long tab4q_off;        // of its quads in SsvMultiArgs.tab4q, in uint4 (2 x 4 x ceil(R/4) x 64 of them)
+  long long full_off;         // of its full table in SsvMultiArgs.tab_full, in dwords ([2][Kp][R][64])
+  long long chunks_per_strand;
+  int M, Q16;
+  int thresh_s, xB;           // as in SsvLongArgs
+  int pair_slack;
+  int chunk_len;              // rows per chunk of this model: any multiple of 64 (the warm-up is M rows whatever it is)
+  int index;                  // the model's number in the batch: what its rows are labelled with
+  int pad_;
+};
+struct SsvMultiArgs {
+  const uint32_t *tab4q, *tab_full;     // the tables of every model of the library, end to end
+  const SsvModelRec *models;            // [gridDim.y] the models of this launch
+  const uint8_t *dsq, *comp;            // the target (1-based) and the complement table: shared by all blocks
+  long long L;
+  int Kp, nstrands, strand0;            // chunk c of a model is on strand strand0 + c / chunks_per_strand
+  int *nrec; long long *rec_pos; uint8_t *rec_strand; int *rec_k; int *rec_sc; int *rec_model; int rec_cap;      // one counter per scan
+};
+// one launch: <nmodels> models (at most 65,535) whose longest chunk list has <max_chunks> entries
+int  ssvlong_multi_launch(int R, bool pair, bool half, const SsvMultiArgs &a, int nmodels, long long max_chunks, int num_cu, hipStream_t st);
+int  ssvlong_multi_capacity(int R, bool pair, bool half, int num_cu, long long *waves);
+size_t ssvlong_lds_bytes(int R);         // dynamic LDS of both scan kernels with R registers per lane
+int  ssvlong_tile_count();               // the kernels' register tiles, ascending
+int  ssvlong_tile(int i);
+
 // ---- thread-per-sequence small stages (p7x_pipeline.hip)
 } // namespace p7x

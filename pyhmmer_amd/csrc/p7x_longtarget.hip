@@ -632,3 +632,450 @@ int64_t p7x_debug_ssv_merge_rows(int Q16, size_t n, const int64_t *pos, const in
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------- nhmmscan
+// One query sequence against a library of models: the scan orientation of the search above (an extension: the reference's
+// LongTargetsPipeline.scan_seq raises).  The SSV scan of all models is one launch per (R, PAIR) group of
+// ssvlong_multi_kernel over one upload of the sequence; everything behind the rows is the search's own code, per model.
+#include <atomic>
+#include <thread>
+
+namespace {
+
+// how the options choose cells and rows, as scan_target reads them
+struct SsvFlavour { bool half; int opt; int forced; };
+SsvFlavour ssv_flavour()
+{
+  SsvFlavour f{ true, debug_opt(OPT_SSV_KERNEL), debug_opt(OPT_SSV_PARTS) };
+  f.half = !(f.opt >= 5 && f.opt <= 7);
+  if (!f.half) f.opt = f.opt == 5 ? -1 : (f.opt == 6 ? 3 : 4);
+  return f;
+}
+// the row flavour of a model (scan_target: kMaxPairSlack and the overrides of option ssv_kernel)
+bool ssv_pair_of(const SsvFlavour &f, int pair_slack)
+{
+  constexpr int kMaxPairSlack = 16;
+  bool pair = f.opt != 3;
+  if (pair && f.opt != 4 && pair_slack > kMaxPairSlack) pair = false;
+  return pair;
+}
+int ssv_pair_slack(const Profile &p)
+{
+  std::vector<uint32_t> t4, tf;
+  int slack = 0;
+  ssvlong_build_tables(p, 2, false, t4, tf, &slack, 1, 1);
+  return slack;
+}
+
+// The launches of a batch: the models grouped by (R, PAIR), groups in order of their first model.  A model that the scan
+// takes in chained parts is in no launch (launch_of = -1): it goes through scan_target.  One rule for both row flavours --
+// a model is batched when one launch holds it WITH the virtual node of PAIR (M <= 6,141) --, so the path a model takes
+// depends on its length and on option ssv_parts, never on its emissions.
+struct SsvBatchLaunch { int R; bool pair; std::vector<int> models; };
+void ssv_batch_plan(const int *M, const int *slack, int n, const SsvFlavour &f, std::vector<SsvBatchLaunch> &launches, std::vector<int> &launch_of)
+{
+  launches.clear(); launch_of.assign((size_t) std::max(n, 0), -1);
+  std::map<std::pair<int, int>, int> at;
+  for (int i = 0; i < n; ++i) {
+    if (M[i] < 1) continue;
+    const bool pair = ssv_pair_of(f, slack[i]);
+    if (ssvlong_plan(M[i], true, f.forced).size() != 1 || ssvlong_plan(M[i], pair, f.forced).size() != 1) continue;
+    const int R = ssvlong_pick_R(M[i], pair);
+    if (R < 0) continue;
+    auto it = at.find({ R, pair ? 1 : 0 });
+    if (it == at.end()) { it = at.emplace(std::make_pair(R, pair ? 1 : 0), (int) launches.size()).first; launches.push_back(SsvBatchLaunch{ R, pair, {} }); }
+    launches[(size_t) it->second].models.push_back(i);
+    launch_of[(size_t) i] = it->second;
+  }
+}
+
+std::atomic<int64_t> g_batch_stats[8];
+
+} // namespace
+
+struct p7x_lt_library {
+  int device = 0;
+  DeviceCtx *ctx = nullptr;
+  SsvFlavour flavour{};
+  int Kp = 0, abc_type = 0;
+  std::vector<const p7x_oprofile *> oms;
+  std::vector<int> slack, M;
+  std::vector<std::string> names;
+  std::vector<SsvBatchLaunch> launches;
+  std::vector<int> launch_of;
+  std::vector<long long> tab4q_off, full_off;      // per model: uint4 / dwords into the two buffers
+  DeviceBuf d_tab4q, d_full, d_comp;
+};
+
+namespace {
+
+int lt_library_build(const p7x_oprofile *const *oms, size_t n, int device, std::unique_ptr<p7x_lt_library> &out)
+{
+  auto lib = std::make_unique<p7x_lt_library>();
+  int st;
+  if ((st = get_ctx(device, &lib->ctx)) != P7X_OK) return st;
+  lib->device = device; lib->flavour = ssv_flavour();
+  lib->oms.assign(oms, oms + n);
+  lib->slack.resize(n);
+  std::vector<int> M(n);
+  for (size_t m = 0; m < n; ++m) {
+    if (!oms[m]) { set_error("long-target library: missing profile"); return P7X_EINVAL; }
+    const Profile &p = oms[m]->p;
+    if (p.abc_type != P7X_DNA && p.abc_type != P7X_RNA) { set_error("long-target pipeline needs a nucleotide model"); return P7X_EINVAL; }
+    if (m == 0) { lib->Kp = p.Kp; lib->abc_type = p.abc_type; }
+    else if (p.Kp != lib->Kp) { set_error("long-target library: models of different alphabets"); return P7X_EINVAL; }
+    M[m] = p.M;
+  }
+  host_parallel_for((int) n, 0, [&](int m) { lib->slack[(size_t) m] = ssv_pair_slack(oms[m]->p); });
+  lib->M = M;
+  lib->names.resize(n);
+  for (size_t m = 0; m < n; ++m) lib->names[m] = oms[m]->p.name;
+  ssv_batch_plan(M.data(), lib->slack.data(), (int) n, lib->flavour, lib->launches, lib->launch_of);
+  lib->tab4q_off.assign(n, -1); lib->full_off.assign(n, -1);
+  long long q_at = 0, f_at = 0;
+  for (const SsvBatchLaunch &ln : lib->launches)
+    for (int m : ln.models) {
+      lib->tab4q_off[(size_t) m] = q_at; lib->full_off[(size_t) m] = f_at;
+      q_at += (long long) (ssvlong_lds_bytes(ln.R) / 16);
+      f_at += (long long) 2 * lib->Kp * ln.R * 64;
+    }
+  if (q_at == 0) { out = std::move(lib); return P7X_OK; }           // nothing batched: no device tables
+  std::vector<uint32_t> h4((size_t) q_at * 4), hf((size_t) f_at);
+  for (const SsvBatchLaunch &ln : lib->launches)
+    host_parallel_for((int) ln.models.size(), 0, [&](int j) {
+      const int m = ln.models[(size_t) j];
+      std::vector<uint32_t> t4, tf;
+      ssvlong_build_tables(oms[m]->p, ln.R, ln.pair, t4, tf, nullptr);
+      std::memcpy(h4.data() + (size_t) lib->tab4q_off[(size_t) m] * 4, t4.data(), t4.size() * 4);
+      std::memcpy(hf.data() + (size_t) lib->full_off[(size_t) m], tf.data(), tf.size() * 4);
+    });
+  DeviceCtx *ctx = lib->ctx;
+  if ((st = alloc(lib->d_tab4q, ctx, h4.size() * 4)) || (st = alloc(lib->d_full, ctx, hf.size() * 4)) || (st = alloc(lib->d_comp, ctx, 32))) return st;
+  {
+    std::lock_guard<std::mutex> turn(ctx->lt_scan_mu);
+    P7X_HIP(hipSetDevice(device));
+    P7X_HIP(hipMemcpyAsync(lib->d_tab4q.as<void>(), h4.data(), h4.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    P7X_HIP(hipMemcpyAsync(lib->d_full.as<void>(), hf.data(), hf.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    P7X_HIP(hipMemcpyAsync(lib->d_comp.as<void>(), longtarget_complement(lib->abc_type), 18, hipMemcpyHostToDevice, ctx->stream));
+    P7X_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  g_batch_stats[0]++;
+  out = std::move(lib);
+  return P7X_OK;
+}
+
+bool lt_library_matches(const p7x_lt_library *lib, const p7x_oprofile *const *oms, size_t n, int device)
+{
+  if (!lib || lib->device != device || lib->oms.size() != n) return false;
+  // the same profile objects, and still the models the tables were built from (a freed profile's address may come back)
+  for (size_t m = 0; m < n; ++m) if (lib->oms[m] != oms[m] || !oms[m] || oms[m]->p.M != lib->M[m] || oms[m]->p.name != lib->names[m]) return false;
+  const SsvFlavour f = ssv_flavour();
+  return f.half == lib->flavour.half && f.opt == lib->flavour.opt && f.forced == lib->flavour.forced;
+}
+
+// The reset-free scan of one target with every model of <lib>: rows[m] = the rows of model m that reach its threshold, in
+// order of (strand, position).  Chunks: per model at least 8 M rows, a multiple of 64, and short enough that the chunk
+// lists of a launch's models together fill the device once; option ssv_scan_chunk forces the length.  The rows do not
+// depend on it.
+int scan_target_batched(const p7x_pipeline_cfg &cfg, p7x_lt_library *lib, const uint8_t *seq1, int64_t L, const int *sc_thresh, const int *xB,
+                        int strands_mask, std::vector<std::vector<ScanRow>> &rows, double *ms, uint64_t resident_key)
+{
+  const size_t n = lib->oms.size();
+  DeviceCtx *ctx = lib->ctx;
+  const int device = lib->device;
+  rows.assign(n, {});
+  if (ms) *ms = 0.0;
+  g_batch_stats[1]++;
+  const int nstrands = strands_mask == 3 ? 2 : 1;
+  int st;
+  size_t nbatched = 0;
+  for (const SsvBatchLaunch &ln : lib->launches) nbatched += ln.models.size();
+  if (nbatched) {
+    std::lock_guard<std::mutex> scan_turn(ctx->lt_scan_mu);      // one scan, single or batched, per device at a time
+    P7X_HIP(hipSetDevice(device));
+    hipStream_t s = ctx->stream;
+    std::shared_ptr<ResidentTargets> d_seq;
+    bool uploaded = false;
+    if ((st = resident_targets(ctx, device, resident_key, seq1, L, d_seq, &uploaded)) != P7X_OK) return st;
+    // the records of every launch, end to end
+    const int forced_chunk = debug_opt(OPT_SSV_SCAN_CHUNK);
+    std::vector<SsvModelRec> recs; recs.reserve(nbatched);
+    std::vector<long long> max_chunks(lib->launches.size(), 0);
+    double cells = 0.0;
+    for (size_t g = 0; g < lib->launches.size(); ++g) {
+      const SsvBatchLaunch &ln = lib->launches[g];
+      long long waves = 0;
+      if ((st = ssvlong_multi_capacity(ln.R, ln.pair, lib->flavour.half, ctx->num_cu, &waves)) != P7X_OK) return st;
+      const int64_t want = std::max<int64_t>(1, waves / (int64_t) ln.models.size() / nstrands);      // chunks per model and strand
+      for (int m : ln.models) {
+        const Profile &p = lib->oms[(size_t) m]->p;
+        int64_t len = std::max<int64_t>(8 * (int64_t) p.M, std::min<int64_t>(1 << 16, (L + want - 1) / want));
+        if (forced_chunk > 0) len = forced_chunk;
+        len = std::max<int64_t>(64, ((len + 63) / 64) * 64);
+        SsvModelRec r{};
+        r.tab4q_off = lib->tab4q_off[(size_t) m]; r.full_off = lib->full_off[(size_t) m];
+        r.chunk_len = (int) len; r.chunks_per_strand = (L + len - 1) / len;
+        r.M = p.M; r.Q16 = p.Q16(); r.thresh_s = sc_thresh[m] - xB[m] - 32768; r.xB = xB[m];
+        r.pair_slack = lib->slack[(size_t) m]; r.index = m;
+        max_chunks[g] = std::max(max_chunks[g], r.chunks_per_strand * nstrands);
+        recs.push_back(r);
+        cells += (double) L * nstrands * p.M;
+      }
+    }
+    DeviceBuf d_recs, d_nrec, d_pos, d_strand, d_k, d_sc, d_model;
+    if ((st = alloc(d_recs, ctx, recs.size() * sizeof(SsvModelRec))) || (st = alloc(d_nrec, ctx, 4))) return st;
+    P7X_HIP(hipMemcpyAsync(d_recs.as<void>(), recs.data(), recs.size() * sizeof(SsvModelRec), hipMemcpyHostToDevice, s));
+    SsvMultiArgs a{};
+    a.tab4q = lib->d_tab4q.as<const uint32_t>(); a.tab_full = lib->d_full.as<const uint32_t>();
+    a.dsq = static_cast<const uint8_t *>(d_seq->p); a.comp = lib->d_comp.as<const uint8_t>();
+    a.L = L; a.Kp = lib->Kp; a.nstrands = nstrands; a.strand0 = strands_mask == 2 ? 1 : 0;
+    a.nrec = d_nrec.as<int>();
+    struct Events {
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      ~Events() { if (e0) (void) hipEventDestroy(e0); if (e1) (void) hipEventDestroy(e1); }
+    } ev;
+    P7X_HIP(hipEventCreate(&ev.e0)); P7X_HIP(hipEventCreate(&ev.e1));
+    // one record counter per scan; a buffer that turns out too small is grown to what the scan counted and the scan repeated
+    int cap = (int) std::min<int64_t>(std::max<int64_t>(4096, (L * nstrands / 256 + 16) * (int64_t) nbatched), 1 << 24);
+    bool done = false;
+    for (int attempt = 0; attempt < 2 && !done; ++attempt) {
+      if ((st = alloc(d_pos, ctx, (size_t) cap * 8)) || (st = alloc(d_strand, ctx, (size_t) cap)) || (st = alloc(d_k, ctx, (size_t) cap * 4)) ||
+          (st = alloc(d_sc, ctx, (size_t) cap * 4)) || (st = alloc(d_model, ctx, (size_t) cap * 4))) return st;
+      a.rec_pos = d_pos.as<long long>(); a.rec_strand = d_strand.as<uint8_t>(); a.rec_k = d_k.as<int>(); a.rec_sc = d_sc.as<int>();
+      a.rec_model = d_model.as<int>(); a.rec_cap = cap;
+      P7X_HIP(hipMemsetAsync(d_nrec.as<void>(), 0, 4, s));
+      P7X_HIP(hipEventRecord(ev.e0, s));
+      size_t at = 0;
+      for (size_t g = 0; g < lib->launches.size(); ++g) {
+        const SsvBatchLaunch &ln = lib->launches[g];
+        for (size_t j0 = 0; j0 < ln.models.size(); j0 += 32768) {          // gridDim.y holds 65,535
+          const int nm = (int) std::min<size_t>(32768, ln.models.size() - j0);
+          a.models = d_recs.as<const SsvModelRec>() + at + j0;
+          if ((st = ssvlong_multi_launch(ln.R, ln.pair, lib->flavour.half, a, nm, max_chunks[g], ctx->num_cu, s)) != P7X_OK) return st;
+          if (attempt == 0) g_batch_stats[2]++;
+        }
+        at += ln.models.size();
+      }
+      P7X_HIP(hipEventRecord(ev.e1, s));
+      int nrec = 0;
+      P7X_HIP(hipMemcpyAsync(&nrec, d_nrec.as<void>(), 4, hipMemcpyDeviceToHost, s));
+      P7X_HIP(hipStreamSynchronize(s));
+      float t = 0; (void) hipEventElapsedTime(&t, ev.e0, ev.e1);
+      if (ms) *ms = t;
+      g_batch_stats[6] = (int64_t) (t * 1000.0f); g_batch_stats[7] = (int64_t) cells;
+      if (nrec > cap) { cap = nrec + 1024; g_batch_stats[5]++; continue; }
+      std::vector<long long> pos((size_t) nrec); std::vector<uint8_t> strand((size_t) nrec); std::vector<int> k((size_t) nrec), sc((size_t) nrec), mo((size_t) nrec);
+      if (nrec) {
+        P7X_HIP(hipMemcpy(pos.data(), d_pos.as<void>(), (size_t) nrec * 8, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(strand.data(), d_strand.as<void>(), (size_t) nrec, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(k.data(), d_k.as<void>(), (size_t) nrec * 4, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(sc.data(), d_sc.as<void>(), (size_t) nrec * 4, hipMemcpyDeviceToHost));
+        P7X_HIP(hipMemcpy(mo.data(), d_model.as<void>(), (size_t) nrec * 4, hipMemcpyDeviceToHost));
+      }
+      for (int i = 0; i < nrec; ++i) {
+        if (mo[(size_t) i] < 0 || (size_t) mo[(size_t) i] >= n) { set_error("batched long-target SSV scan: a row of no model"); return P7X_EDEVICE; }
+        rows[(size_t) mo[(size_t) i]].push_back(ScanRow{ pos[(size_t) i], strand[(size_t) i], k[(size_t) i], sc[(size_t) i] });
+      }
+      done = true;
+    }
+    if (!done) { set_error("batched long-target SSV scan: record buffer could not be sized"); return P7X_EMEM; }
+    g_batch_stats[3] += (int64_t) nbatched;
+    if ((debug_opt(OPT_TRACE_LONGTARGET) > 0))
+      std::fprintf(stderr, "[lt] batched scan: %zu models in %zu launches, %lld positions (%s), kernel %.2f ms\n", nbatched, lib->launches.size(), (long long) L,
+                   uploaded ? "uploaded" : "resident", ms ? *ms : 0.0);
+  }
+  host_parallel_for((int) n, cfg.host_threads, [&](int m) {
+    std::sort(rows[(size_t) m].begin(), rows[(size_t) m].end(), [](const ScanRow &x, const ScanRow &y) { return x.strand != y.strand ? x.strand < y.strand : x.pos < y.pos; });
+  });
+  // the models one launch does not hold: the chained parts of the single-model scan, one model at a time
+  for (size_t m = 0; m < n; ++m) {
+    if (lib->launch_of[m] >= 0) continue;
+    double t = 0.0;
+    if ((st = scan_target(cfg, lib->oms[m]->p, ctx, seq1, L, sc_thresh[m], xB[m], strands_mask, rows[m], &t, nullptr, device, resident_key)) != P7X_OK) return st;
+    if (ms) *ms += t;
+    g_batch_stats[4]++;
+  }
+  return P7X_OK;
+}
+
+// the (block, strand) units of one sequence of L residues, as p7x_search_longtargets counts them for one target
+struct ScanUnit { int64_t i, bn; int strand; };
+void scan_units(int64_t L, int64_t W, int64_t C, int mask, std::vector<ScanUnit> &units)
+{
+  units.clear();
+  for (int64_t i = 0; i < L; i += W - C) {
+    const int64_t bc = i == 0 ? 0 : std::min<int64_t>(C, L - i);
+    const int64_t bw = std::min<int64_t>(W, L - i - bc);
+    const int64_t bn = bc + bw;
+    if (bn <= 0) break;
+    for (int strand = 0; strand < 2; ++strand) if (mask & (1 << strand)) units.push_back(ScanUnit{ i, bn, strand });
+  }
+}
+
+} // namespace
+
+extern "C" {
+
+int p7x_lt_library_create(const p7x_oprofile *const *oms, size_t nmodels, int device, p7x_lt_library **out)
+{
+  if (!out || (nmodels && !oms)) { set_error("p7x_lt_library_create: bad arguments"); return P7X_EINVAL; }
+  *out = nullptr;
+  std::unique_ptr<p7x_lt_library> lib;
+  const int st = lt_library_build(oms, nmodels, device, lib);
+  if (st != P7X_OK) return st;
+  *out = lib.release();
+  return P7X_OK;
+}
+
+void p7x_lt_library_destroy(p7x_lt_library *lib) { delete lib; }
+
+int p7x_scan_longtargets(const p7x_pipeline_cfg *cfg, const p7x_oprofile *const *oms, size_t nmodels, int device,
+                         const uint8_t *dsq, int64_t L, const char *name, const char *acc, const char *desc,
+                         const int32_t *evalue_window_lengths, p7x_lt_library *lib_in, uint64_t resident_key, p7x_tophits **out)
+{
+  if (!cfg || !out || !dsq || L < 0 || (nmodels && !oms)) { set_error("p7x_scan_longtargets: bad arguments"); return P7X_EINVAL; }
+  if (!cfg->long_targets) { set_error("p7x_scan_longtargets: cfg.long_targets is not set"); return P7X_EINVAL; }
+  for (size_t m = 0; m < nmodels; ++m) out[m] = nullptr;
+  if (nmodels == 0) return P7X_OK;
+  const auto t_begin = std::chrono::steady_clock::now();
+  std::unique_ptr<p7x_lt_library> own;
+  p7x_lt_library *lib = lib_in;
+  int st;
+  if (!lt_library_matches(lib, oms, nmodels, device)) {
+    if ((st = lt_library_build(oms, nmodels, device, own)) != P7X_OK) return st;
+    lib = own.get();
+  }
+  std::vector<int> max_length(nmodels), sc_thresh(nmodels), xB(nmodels);
+  for (size_t m = 0; m < nmodels; ++m)
+    if ((st = longtarget_setup(*cfg, oms[m]->p, &max_length[m], &sc_thresh[m], &xB[m])) != P7X_OK) return st;
+  const int mask = cfg->strands == P7X_STRAND_TOPONLY ? 1 : (cfg->strands == P7X_STRAND_BOTTOMONLY ? 2 : 3);
+  std::vector<std::vector<ScanRow>> rows;
+  double scan_ms = 0.0;
+  if (L > 0 && (st = scan_target_batched(*cfg, lib, dsq, L, sc_thresh.data(), xB.data(), mask, rows, &scan_ms, resident_key)) != P7X_OK) return st;
+  rows.resize(nmodels);
+  const auto t_scan = std::chrono::steady_clock::now();
+  // seeds: upstream's bookkeeping per (model, block, strand), all of them side by side
+  struct Job { size_t m; ScanUnit u; std::vector<int64_t> s3; };
+  std::vector<Job> jobs;
+  std::vector<ScanUnit> units;
+  for (size_t m = 0; m < nmodels; ++m) {
+    if (rows[m].empty()) continue;
+    scan_units(L, cfg->block_length, max_length[m], mask, units);
+    for (const ScanUnit &u : units) jobs.push_back(Job{ m, u, {} });
+  }
+  host_parallel_for((int) jobs.size(), cfg->host_threads, [&](int j) {
+    Job &jb = jobs[(size_t) j];
+    block_seeds(oms[jb.m]->p, dsq, L, jb.u.i, jb.u.bn, jb.u.strand, rows[jb.m], sc_thresh[jb.m], xB[jb.m], jb.s3, 0);
+  });
+  std::vector<std::vector<LongTargetSeed>> seeds(nmodels);
+  for (const Job &jb : jobs)
+    for (size_t q = 0; q + 2 < jb.s3.size(); q += 3) seeds[jb.m].push_back(LongTargetSeed{ 0, jb.u.i, jb.u.strand, jb.s3[q], (int) jb.s3[q + 1], jb.s3[q + 2] });
+  const auto t_seeds = std::chrono::steady_clock::now();
+  // the tails: the search's own code per model, several models at a time on threads of their own (a tail waits for its
+  // small device batches; its host phases share the workers)
+  const int64_t offsets[1] = { 1 }, lengths[1] = { L };
+  const char *names[1] = { name ? name : "" }, *accs[1] = { acc ? acc : "" }, *descs[1] = { desc ? desc : "" };
+  std::vector<size_t> busy;
+  for (size_t m = 0; m < nmodels; ++m) if (!seeds[m].empty()) busy.push_back(m);
+  const int usable = cfg->host_threads > 0 ? cfg->host_threads : tophits_usable_cpus();
+  const int side = (int) std::max<size_t>(1, std::min<size_t>(std::min<size_t>(busy.size(), 8), (size_t) usable));
+  std::atomic<size_t> next{ 0 };
+  std::atomic<int> failed{ P7X_OK };
+  std::mutex err_mu; std::string err;
+  auto tail = [&](size_t m, bool with_device) -> int {
+    p7x_pipeline_cfg c = *cfg;
+    c.lt_part = 0; c.lt_nparts = 1;
+    c.evalue_window_length = evalue_window_lengths ? evalue_window_lengths[m] : cfg->evalue_window_length;
+    if (with_device) c.host_threads = std::max(1, usable / side);
+    DeviceWindowScorer scorer(oms[m], device, cfg->oa_guard);
+    const int rc = longtarget_run_host(c, oms[m], dsq, offsets, lengths, 1, names, accs, descs, seeds[m], &out[m], with_device ? &scorer : nullptr);
+    if (rc == P7X_OK && out[m]) {
+      out[m]->cfg.host_threads = cfg->host_threads;
+      out[m]->ms[P7X_MS_BIAS] = scorer.ms;
+    }
+    return rc;
+  };
+  auto worker = [&]() {
+    const hipError_t de = hipSetDevice(device);
+    if (de != hipSuccess) {
+      std::lock_guard<std::mutex> lk(err_mu);
+      if (failed.load() == P7X_OK) { failed = P7X_EDEVICE; err = std::string("hipSetDevice: ") + hipGetErrorString(de); }
+      return;
+    }
+    for (;;) {
+      const size_t j = next.fetch_add(1);
+      if (j >= busy.size() || failed.load() != P7X_OK) break;
+      const int rc = tail(busy[j], true);
+      if (rc != P7X_OK) { std::lock_guard<std::mutex> lk(err_mu); if (failed.load() == P7X_OK) { failed = rc; err = p7x_last_error(); } }
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (int w = 1; w < side; ++w) th.emplace_back(worker);
+    worker();
+    for (std::thread &t : th) t.join();
+  }
+  st = failed.load();
+  if (st != P7X_OK) set_error(err);
+  // a model without seeds: its empty list, no device
+  for (size_t m = 0; st == P7X_OK && m < nmodels; ++m) if (seeds[m].empty()) st = tail(m, false);
+  if (st != P7X_OK) { p7x_tophits_destroy_many(out, nmodels); return st; }
+  const auto t_end = std::chrono::steady_clock::now();
+  // the scan's timing slots on the first list (enum p7x_timing, the long-target meanings): kernel, scan + seeds, tails
+  if (out[0]) {
+    out[0]->ms[P7X_MS_MSV_KERNEL] = scan_ms;
+    out[0]->ms[P7X_MS_MSV] = std::chrono::duration<double, std::milli>(t_seeds - t_begin).count();
+    out[0]->ms[P7X_MS_STAGE1] = std::chrono::duration<double, std::milli>(t_scan - t_begin).count();
+    out[0]->ms[P7X_MS_HOST_DOMAINDEF] = std::chrono::duration<double, std::milli>(t_end - t_seeds).count();
+  }
+  return P7X_OK;
+}
+
+int64_t p7x_ssv_longtarget_seeds_batch(const p7x_pipeline_cfg *cfg, const p7x_oprofile *const *oms, size_t nmodels, int device,
+                                       const uint8_t *dsq, int64_t L, int complement, int64_t *seeds, size_t cap, int64_t *count)
+{
+  if (!cfg || !oms || !nmodels || !dsq || L <= 0 || !count || (cap && !seeds)) { set_error("p7x_ssv_longtarget_seeds_batch: bad arguments"); return -P7X_EINVAL; }
+  std::unique_ptr<p7x_lt_library> lib;
+  int st = lt_library_build(oms, nmodels, device, lib);
+  if (st != P7X_OK) return -st;
+  std::vector<int> max_length(nmodels), sc_thresh(nmodels), xB(nmodels);
+  for (size_t m = 0; m < nmodels; ++m)
+    if ((st = longtarget_setup(*cfg, oms[m]->p, &max_length[m], &sc_thresh[m], &xB[m])) != P7X_OK) return -st;
+  std::vector<std::vector<ScanRow>> rows;
+  if ((st = scan_target_batched(*cfg, lib.get(), dsq - 1, L, sc_thresh.data(), xB.data(), complement ? 2 : 1, rows, nullptr, 0)) != P7X_OK) return -st;
+  std::vector<std::vector<int64_t>> s3(nmodels);
+  host_parallel_for((int) nmodels, cfg->host_threads, [&](int m) {
+    block_seeds(oms[m]->p, dsq - 1, L, 0, L, complement ? 1 : 0, rows[(size_t) m], sc_thresh[(size_t) m], xB[(size_t) m], s3[(size_t) m]);
+  });
+  size_t at = 0;
+  for (size_t m = 0; m < nmodels; ++m) {
+    count[m] = (int64_t) (s3[m].size() / 3);
+    for (size_t q = 0; q < s3[m].size(); ++q, ++at) if (at < cap * 3) seeds[at] = s3[m][q];
+  }
+  return (int64_t) (at / 3);
+}
+
+int p7x_debug_ssv_batch_plan(const int32_t *M, const int32_t *pair_slack, int n, int32_t *launch_of, int32_t *launch_R,
+                             int32_t *launch_pair, int64_t *launch_lds, int cap, int64_t *lds_limit)
+{
+  if (n < 0 || (n && (!M || !pair_slack || !launch_of))) { set_error("p7x_debug_ssv_batch_plan: bad arguments"); return -P7X_EINVAL; }
+  std::vector<SsvBatchLaunch> launches; std::vector<int> of;
+  ssv_batch_plan(M, pair_slack, n, ssv_flavour(), launches, of);
+  for (int i = 0; i < n; ++i) launch_of[i] = of[(size_t) i];
+  for (size_t g = 0; g < launches.size() && (int) g < cap; ++g) {
+    if (launch_R) launch_R[g] = launches[g].R;
+    if (launch_pair) launch_pair[g] = launches[g].pair ? 1 : 0;
+    if (launch_lds) launch_lds[g] = (int64_t) ssvlong_lds_bytes(launches[g].R);
+  }
+  if (lds_limit) *lds_limit = (int64_t) ssvlong_lds_bytes(ssvlong_tile(ssvlong_tile_count() - 1));
+  return (int) launches.size();
+}
+
+int p7x_debug_ssv_batch_stats(int64_t out[8], int reset)
+{
+  if (!out) { set_error("p7x_debug_ssv_batch_stats: bad arguments"); return P7X_EINVAL; }
+  for (int i = 0; i < 8; ++i) { out[i] = g_batch_stats[i].load(); if (reset) g_batch_stats[i] = 0; }
+  return P7X_OK;
+}
+
+} // extern "C"

@@ -154,6 +154,8 @@ __device__ __forceinline__ void ssv_row(uint32_t (&v)[R], const uint32_t (&e)[RE
   }
 }
 
+// (ssvlong_multi_kernel below is this kernel's twin for a batch of models, without the chained parts: a change to the row
+// loop, the report or the fetches here belongs there too.)
 template <int R, bool PAIR, bool H, bool BIN, bool BOUT>
 __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
 {
@@ -337,6 +339,156 @@ __global__ void __launch_bounds__(256) ssvlong_quad_kernel(const SsvLongArgs a)
   }
 }
 
+// ---------------------------------------------------------------------------- the batched scan (nhmmscan)
+// One target against the models of a library: a contig of 45 kb against a model of 1,200 nodes is ten chunks of 8 M rows,
+// ten wavefronts on a device that holds thousands, and a launch per model pays its upload, events and read-back for them.
+// Here a block serves ONE model, blockIdx.y: it reads the model's record (SsvModelRec), stages that model's quads in LDS as
+// the kernel above does, and its four wavefronts take the model's (chunk, strand) list in turns with the other blocks of
+// the same y.  All models of a launch share R, PAIR and H (the host groups them, p7x_longtarget.hip: batch plan); the target,
+// the complement table and the record buffer are the launch's.  The rows are the arithmetic of the kernel above without the
+// chained parts -- ssv_row, the 64-row fast block and its exact repeat, M rows of warm-up, the same tie-break key -- and a
+// reported row carries its model's number.  The chunk length is per model and may be shorter than the model (a library
+// batch fills the device with short chunks; the warm-up stays M rows): it only changes which wavefront computes a row.
+// The kernel above is left as it is, text and code: nhmmer's scan is compared bit for bit and timed.
+template <int R, bool PAIR, bool H>
+__global__ void __launch_bounds__(256) ssvlong_multi_kernel(const SsvMultiArgs a)
+{
+  constexpr uint32_t kFloorV = H ? 0u : kFloor2;
+  constexpr int R4 = (R + 3) / 4;
+  constexpr int RE = 4 * R4;
+  constexpr int XS = R4 * 64;
+  extern __shared__ __attribute__((aligned(16))) uint4 ldsq[];
+  const SsvModelRec m = a.models[blockIdx.y];                // the same for the whole block
+  const long long nchunks = m.chunks_per_strand * a.nstrands;
+  if ((long long) blockIdx.x * 4 >= nchunks) return;         // no wavefront of this block has a chunk (all of them leave: no barrier is missed)
+  {
+    const uint4 *g = reinterpret_cast<const uint4 *>(a.tab4q) + m.tab4q_off;
+    for (int i = threadIdx.x; i < 8 * XS; i += 256) {
+      uint4 w = g[i];
+      if constexpr (H) { w.x = h_of_i16_pair_u(w.x); w.y = h_of_i16_pair_u(w.y); w.z = h_of_i16_pair_u(w.z); w.w = h_of_i16_pair_u(w.w); }
+      ldsq[i] = w;
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = rfl((int) (blockIdx.x * 4 + (threadIdx.x >> 6)));
+  const int nwaves = (int) gridDim.x * 4;
+  const uint4 *lq = ldsq + lane;
+  const int thr_exact = m.thresh_s + 32768;
+  const int thr_fast = PAIR ? thr_exact - m.pair_slack : thr_exact;
+  const int sc_thresh = m.thresh_s + m.xB + 32768;
+
+  auto load_quads = [&](uint32_t (&e)[RE], uint32_t xs, int par) {
+    const uint4 *p = lq + xs + par * 4 * XS;
+#pragma unroll
+    for (int q = 0; q < R4; ++q) { const uint4 t = p[q * 64]; e[4 * q] = t.x; e[4 * q + 1] = t.y; e[4 * q + 2] = t.z; e[4 * q + 3] = t.w; }
+  };
+  // the cell upstream would pick in a row that reaches the threshold (see the kernel above), and the model it belongs to
+  auto report = [&](const uint32_t (&v)[R], bool odd, long long i, int strand) {
+    int best = INT_MIN, bestkey = INT_MAX;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int g = lane * R + j, c0 = odd ? 2 * g - 1 : 2 * g;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int k = c0 + h;
+        const int sv = rel_half<H>(v[j], h);
+        if (k >= 1 && k <= m.M) {
+          const int val = min(255, sv + m.xB);
+          const int key = ((k - 1) % m.Q16) * 16 + (k - 1) / m.Q16;
+          if (val > best || (val == best && key < bestkey)) { best = val; bestkey = key; }
+        }
+      }
+    }
+    const int smax = wave_max_i32(best);
+    if (smax < sc_thresh) return;
+    const int kmin = -wave_max_i32(best == smax ? -bestkey : INT_MIN);
+    if (lane == 0) {
+      const int slot = atomicAdd(a.nrec, 1);
+      if (slot < a.rec_cap) {
+        a.rec_pos[slot] = i; a.rec_strand[slot] = (uint8_t) strand; a.rec_model[slot] = m.index;
+        a.rec_k[slot] = (kmin / 16) + m.Q16 * (kmin % 16) + 1; a.rec_sc[slot] = smax;
+      }
+    }
+  };
+  auto fast_block = [&](uint32_t (&v)[R], uint32_t xsv) -> bool {
+    uint32_t eA[RE], eB[RE];
+    load_quads(eA, (uint32_t) __builtin_amdgcn_readlane((int) xsv, 0), 0);
+    for (int r0 = 0; r0 < 64; r0 += 16) {
+      uint32_t acc0 = kFloorV, acc1 = kFloorV;
+#pragma unroll
+      for (int rr = 0; rr < 16; rr += 2) {
+        load_quads(eB, (uint32_t) __builtin_amdgcn_readlane((int) xsv, r0 + rr + 1), 1);
+        ssv_row<R, true, !PAIR, RE, H>(v, eA, acc0, acc1);
+        __builtin_amdgcn_sched_barrier(0);
+        load_quads(eA, (uint32_t) __builtin_amdgcn_readlane((int) xsv, (r0 + rr + 2) & 63), 0);
+        ssv_row<R, false, true, RE, H>(v, eB, acc0, acc1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (ssv_reached<H>(H ? h_max_u(acc0, acc1) : pk_max_u(acc0, acc1), thr_fast)) return false;
+    }
+    return true;
+  };
+
+  const uint32_t *full = a.tab_full + m.full_off;
+  for (long long ch = wave; ch < nchunks; ch += nwaves) {
+    const int strand = a.strand0 + (int) (ch / m.chunks_per_strand);
+    const long long c0 = (ch % m.chunks_per_strand) * (long long) m.chunk_len;
+    const long long first = c0 + 1, last = min(a.L, c0 + m.chunk_len);
+    const long long warm = max(1LL, first - m.M);
+    uint32_t v[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) v[j] = kFloorV;
+    auto fetch = [&](long long i0) -> uint32_t {           // positions 1 .. L of the target, whichever strand
+      const long long pos = i0 + lane;
+      if (pos > last) return 0u;
+      return a.dsq[strand == 0 ? pos : a.L - pos + 1];
+    };
+    auto on_strand = [&](uint32_t x) -> uint32_t {
+      return strand == 0 ? x : (x < 4 ? 3u - x : (x >= (uint32_t) a.Kp ? x : (uint32_t) a.comp[x]));
+    };
+    uint32_t raw_next = fetch(warm);
+    for (long long i0 = warm; i0 <= last; i0 += 64) {
+      const int nrow = (int) min(64LL, last - i0 + 1);
+      __builtin_amdgcn_s_waitcnt(0x0f70);            // vmcnt(0): the bytes fetched during the previous block, before the next fetch is issued
+      const uint32_t res = on_strand(raw_next);
+      raw_next = fetch(i0 + 64);
+      if (nrow == 64 && __all(res < 4u)) {
+        uint32_t saved[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) saved[j] = v[j];
+        if (fast_block(v, res * (uint32_t) XS)) continue;
+#pragma unroll
+        for (int j = 0; j < R; ++j) v[j] = saved[j];
+      }
+      for (int r = 0; r < nrow; r += 2) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (r + h >= nrow) break;
+          const int x = __builtin_amdgcn_readlane((int) res, r + h);
+          uint32_t acc0 = kFloorV, acc1 = kFloorV;
+          if (x < 4) {
+            uint32_t e[RE];
+            load_quads(e, (uint32_t) x * XS, h);
+            if (h == 0) ssv_row<R, true, true, RE, H>(v, e, acc0, acc1); else ssv_row<R, false, true, RE, H>(v, e, acc0, acc1);
+          } else if (x >= a.Kp) {     // between two records laid end to end: every diagonal ends here
+#pragma unroll
+            for (int j = 0; j < R; ++j) v[j] = kFloorV;
+          } else {                    // degenerate residue: the model's full table, [parity][Kp][R][64]
+            const uint32_t *eg = full + ((size_t) ((h == 0 ? 0 : a.Kp) + x) * R) * 64 + lane;
+            uint32_t e[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) e[j] = H ? h_of_i16_pair_u(eg[j * 64]) : eg[j * 64];
+            if (h == 0) ssv_row<R, true, true, R, H>(v, e, acc0, acc1); else ssv_row<R, false, true, R, H>(v, e, acc0, acc1);
+          }
+          const long long i = i0 + r + h;
+          if (i >= first && ssv_reached<H>(H ? h_max_u(acc0, acc1) : pk_max_u(acc0, acc1), thr_exact)) report(v, h == 0, i, strand);
+        }
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------- host side
 // packed registers per lane: the instantiations, for ssvlong_pick_R, ssvlong_plan and the dispatch
 #define P7X_SSV_R(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(14) X(16) X(20) X(24) X(32) X(48)
@@ -482,6 +634,58 @@ int ssvlong_capacity(int R, bool pair, bool half, int num_cu, long long *waves)
 int ssvlong_launch(int R, bool pair, bool half, const SsvLongArgs &a, int num_cu, hipStream_t st, bool bin, bool bout)
 {
   return ssvlong_quad_dispatch(R, pair, half, bin, bout, a, num_cu, st, nullptr);
+}
+
+// ---- the batched scan
+size_t ssvlong_lds_bytes(int R) { return (size_t) 2 * 4 * ((R + 3) / 4) * 64 * 16; }
+int ssvlong_tile_count() { return (int) (sizeof(kSsvR) / sizeof(kSsvR[0])); }
+int ssvlong_tile(int i) { return i >= 0 && i < ssvlong_tile_count() ? kSsvR[i] : -1; }
+
+// grid: y = the models; x = enough blocks for the longest chunk list, and no more than fill the device once over all models
+// (the wavefronts of a model take its chunks in turns)
+template <int R, bool PAIR, bool H>
+static int launch_ssv_multi(const SsvMultiArgs &a, int nmodels, long long max_chunks, int num_cu, hipStream_t st, long long *cap_waves)
+{
+  const size_t lds = ssvlong_lds_bytes(R);
+  auto kern = ssvlong_multi_kernel<R, PAIR, H>;
+  int per_cu = 0;
+  const int pst = kernel_blocks_per_cu(kern, 256, lds, &per_cu);
+  if (pst != P7X_OK) return pst;
+  if (cap_waves) { *cap_waves = (long long) num_cu * per_cu * 4; return P7X_OK; }
+  if (nmodels < 1 || nmodels > 65535) { set_error("batched long-target SSV scan: 1 to 65,535 models per launch"); return P7X_EINVAL; }
+  const long long share = std::max<long long>(1, ((long long) num_cu * per_cu + nmodels - 1) / nmodels);
+  const long long gx = std::max<long long>(1, std::min<long long>((max_chunks + 3) / 4, share));
+  hipLaunchKernelGGL(kern, dim3((unsigned) gx, (unsigned) nmodels), dim3(256), lds, st, a);
+  P7X_HIP(hipGetLastError());
+  return P7X_OK;
+}
+
+template <int R>
+static int ssvlong_multi_flavour(bool pair, bool half, const SsvMultiArgs &a, int nmodels, long long max_chunks, int num_cu, hipStream_t st, long long *cap_waves)
+{
+  if (pair) return half ? launch_ssv_multi<R, true, true>(a, nmodels, max_chunks, num_cu, st, cap_waves) : launch_ssv_multi<R, true, false>(a, nmodels, max_chunks, num_cu, st, cap_waves);
+  return half ? launch_ssv_multi<R, false, true>(a, nmodels, max_chunks, num_cu, st, cap_waves) : launch_ssv_multi<R, false, false>(a, nmodels, max_chunks, num_cu, st, cap_waves);
+}
+
+static int ssvlong_multi_dispatch(int R, bool pair, bool half, const SsvMultiArgs &a, int nmodels, long long max_chunks, int num_cu, hipStream_t st, long long *cap_waves)
+{
+#define P7X_SM(RR) case RR: return ssvlong_multi_flavour<RR>(pair, half, a, nmodels, max_chunks, num_cu, st, cap_waves);
+  switch (R) {
+    P7X_SSV_R(P7X_SM)
+    default: set_error(model_too_long("model too long for the long-target SSV kernel")); return P7X_EINVAL;
+  }
+#undef P7X_SM
+}
+
+int ssvlong_multi_capacity(int R, bool pair, bool half, int num_cu, long long *waves)
+{
+  SsvMultiArgs none{};
+  return ssvlong_multi_dispatch(R, pair, half, none, 1, 1, num_cu, nullptr, waves);
+}
+
+int ssvlong_multi_launch(int R, bool pair, bool half, const SsvMultiArgs &a, int nmodels, long long max_chunks, int num_cu, hipStream_t st)
+{
+  return ssvlong_multi_dispatch(R, pair, half, a, nmodels, max_chunks, num_cu, st, nullptr);
 }
 
 } // namespace p7x

@@ -847,6 +847,85 @@ int p7x_scan_collect(p7x_tophits *const *per_model, size_t nmodels, const p7x_pi
   return p7x_scan_accum_finish(acc, out);
 }
 
+// nhmmscan: the per-model long-target lists of ONE query sequence -> its scan-mode list (include/p7x.h).  A model's hits are
+// what its lone search reports (E-values for the sequence's residues and the model's window length, duplicates removed
+// within the model); the list is finished by scaling every lnP by the number of models of the whole library, as upstream's
+// nhmmscan does, and thresholding on the scaled values (target_reportable & co. take a long-target lnP as the E-value).
+int p7x_scan_collect_longtargets(p7x_tophits *const *per_model, const int64_t *model_index, size_t nmodels, int64_t nmodels_total,
+                                 const p7x_pipeline_cfg *cfg_in, const char *name, const char *acc, const char *desc, int64_t length,
+                                 p7x_tophits **inout)
+{
+  const char *who = "p7x_scan_collect_longtargets";
+  if (!inout || (nmodels && !per_model) || (!*inout && !cfg_in)) { set_error(std::string(who) + ": bad arguments"); return P7X_EINVAL; }
+  for (size_t m = 0; m < nmodels; ++m) {
+    if (!per_model[m]) { set_error(std::string(who) + ": missing per-model result"); return P7X_EINVAL; }
+    if (!per_model[m]->cfg.long_targets || per_model[m]->scan_collected) { set_error(std::string(who) + ": not the list of a long-target search"); return P7X_EINVAL; }
+    if (model_index && model_index[m] < 0) { set_error(std::string(who) + ": negative model number"); return P7X_EINVAL; }
+  }
+  std::unique_ptr<p7x_tophits> fresh;
+  p7x_tophits *th = *inout;
+  if (!th) {
+    if (!cfg_in->long_targets) { set_error(std::string(who) + ": cfg.long_targets is not set"); return P7X_EINVAL; }
+    flogsum_init();
+    fresh = std::make_unique<p7x_tophits>();
+    th = fresh.get();
+    th->cfg = *cfg_in; th->cfg.mode = P7X_SCAN_MODELS; th->cfg.lt_part = 0; th->cfg.lt_nparts = 1;
+    th->scan_collected = true; th->lt_unfinished = true;
+    if (name) th->qname = name;
+    if (acc && acc[0]) { th->qacc = acc; th->q_has_acc = true; }
+    if (desc && desc[0]) { th->qdesc = desc; th->q_has_desc = true; }
+    th->ctr.nseqs = 1;
+    th->ctr.nres = (uint64_t) std::max<int64_t>(length, 0) * (cfg_in->strands == P7X_STRAND_BOTH ? 2 : 1);
+  } else if (!th->scan_collected || !th->lt_unfinished || !th->cfg.long_targets) {
+    set_error(std::string(who) + ": the list is not an unfinished long-target scan"); return P7X_EINVAL;
+  }
+  for (size_t m = 0; m < nmodels; ++m) {
+    const p7x_tophits *pm = per_model[m];
+    std::unique_ptr<p7x_tophits> done;
+    if (pm->lt_unfinished) {             // as the lone search finishes it
+      done = std::make_unique<p7x_tophits>(*pm);
+      longtarget_finalize(done.get(), done->lt_evalue_window, longtarget_res_count(done->cfg, done->ctr.nres));
+      pm = done.get();
+    }
+    const int64_t number = model_index ? model_index[m] : (int64_t) th->ctr.nmodels;
+    if (th->abc_type == 0) th->abc_type = pm->abc_type;
+    th->ctr.nmodels++; th->ctr.nnodes += (uint64_t) pm->M;
+    th->ctr.n_past_msv += pm->ctr.n_past_msv; th->ctr.n_past_bias += pm->ctr.n_past_bias; th->ctr.n_past_vit += pm->ctr.n_past_vit; th->ctr.n_past_fwd += pm->ctr.n_past_fwd;
+    th->ctr.pos_past_msv += pm->ctr.pos_past_msv; th->ctr.pos_past_bias += pm->ctr.pos_past_bias; th->ctr.pos_past_vit += pm->ctr.pos_past_vit; th->ctr.pos_past_fwd += pm->ctr.pos_past_fwd;
+    th->oa_redone += pm->oa_redone;
+    for (int b = 0; b < 8; ++b) th->oa_why[b] += pm->oa_why[b];
+    for (int s = 0; s < p7x_tophits::kMs; ++s) th->ms[s] += pm->ms[s];
+    for (size_t q = 0; q < pm->hits.size(); ++q) {
+      const Hit &h = pm->order.size() == pm->hits.size() ? pm->hits[(size_t) pm->order[q]] : pm->hits[q];
+      Hit copy = h;
+      copy.name = pm->qname; copy.acc = pm->qacc; copy.desc = pm->qdesc; copy.has_acc = pm->q_has_acc; copy.has_desc = pm->q_has_desc;
+      copy.seqidx = number;
+      th->hits.push_back(std::move(copy));
+    }
+  }
+  th->order.clear(); th->sorted_by_key = false;
+  if (nmodels_total != 0) {
+    if (nmodels_total < 0) nmodels_total = (int64_t) th->ctr.nmodels;      // the models collected are the library (none: an empty list)
+    const double scale = nmodels_total > 0 ? std::log((double) nmodels_total) : 0.0;
+    for (Hit &h : th->hits) {
+      h.lnP += scale;
+      for (Domain &d : h.dcl) d.lnP += scale;
+      h.sortkey = -1.0 * h.lnP;
+    }
+    // the order of the models first: ties of the key sort keep it, however the models were dealt into calls
+    std::stable_sort(th->hits.begin(), th->hits.end(), [](const Hit &a, const Hit &b) { return a.seqidx < b.seqidx; });
+    th->ctr.nmodels = std::max<uint64_t>(th->ctr.nmodels, (uint64_t) nmodels_total);
+    sort_by_key(*th);
+    threshold(*th);
+    th->ctr.n_output = th->ctr.pos_output = 0;
+    for (const Hit &h : th->hits)
+      if (h.flags & (P7X_IS_REPORTED | P7X_IS_INCLUDED)) { th->ctr.n_output++; th->ctr.pos_output += 1 + (uint64_t) std::llabs(h.dcl[0].jali - h.dcl[0].iali); }
+    th->lt_unfinished = false;
+  }
+  if (fresh) *inout = fresh.release();
+  return P7X_OK;
+}
+
 int p7x_tophits_sort_by_key(p7x_tophits *th) { if (!th) return P7X_EINVAL; sort_by_key(*th); return P7X_OK; }
 int p7x_tophits_threshold(p7x_tophits *th)   { if (!th) return P7X_EINVAL; threshold(*th); return P7X_OK; }
 

@@ -10,6 +10,7 @@ re-thresholded on the host.  No collective is involved.
 """
 from __future__ import annotations
 
+import itertools
 import os
 import sys
 import time
@@ -23,7 +24,7 @@ from .easel import Alphabet, DigitalMSA, DigitalSequence, DigitalSequenceBlock, 
 from .plan7 import (HMM, Builder, IterationResult, LongTargetsPipeline, OptimizedProfile, Pipeline, Profile, SequenceDatabase,
                     TopHits)
 
-__all__ = ["hmmsearch", "phmmer", "jackhmmer", "hmmscan", "nhmmer", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase",
+__all__ = ["hmmsearch", "phmmer", "jackhmmer", "hmmscan", "nhmmer", "nhmmscan", "hmmpress", "hmmalign", "make_chunks", "ShardedDatabase",
            "ReplicatedDatabase"]
 
 
@@ -1270,6 +1271,106 @@ def nhmmer(queries, sequences, *, cpus: int = 0, callback: Optional[Callable] = 
                     fut.result()
                 except BaseException:           # noqa: BLE001
                     pass
+
+
+def nhmmscan(queries, profiles, *, cpus: int = 0, callback: Optional[Callable] = None, device: int = 0, batch: int = 128,
+             **options) -> Iterator[TopHits]:
+    """Scan long nucleotide sequences against a library of nucleotide models; yields one ``TopHits`` per query sequence,
+    in query order, whose hits are the models (upstream's ``nhmmscan``; pyhmmer has no counterpart, its
+    ``LongTargetsPipeline.scan_seq`` raises).
+
+    ``queries``: a ``DigitalSequence``, a ``DigitalSequenceBlock``, an iterable of sequences or a digital ``SequenceFile``;
+    ``profiles``: what :func:`hmmscan` accepts.  Keyword arguments are those of
+    :class:`~pyhmmer_amd.plan7.LongTargetsPipeline`.
+
+    The loop ``nhmmer(model, [contig])`` over a library launches one SSV scan per model, each a handful of wavefronts.
+    Here the library is taken in batches of ``batch`` models: the optimized profiles and the device copy of their SSV
+    tables are built once (``plan7.LongTargetLibrary``) and kept for every query; a query is uploaded once and every batch
+    scans it with one launch per (register tile, row flavour) group, a model per ``blockIdx.y``
+    (``p7x_scan_longtargets``).  Behind the scan a model's windows go through nhmmer's own tail, several models at a time.
+    A model's hits are those of its lone search against the sequence; the E-values are multiplied by the number of models
+    in the library, as upstream's nhmmscan does, and reporting / inclusion act on the scaled values
+    (``p7x_scan_collect_longtargets``).  Hits of different models that overlap on the sequence are all kept.  One device."""
+    return _scan_long_queries(queries, profiles, lambda alphabet: LongTargetsPipeline(alphabet, device=device, host_threads=cpus, **options),
+                              callback, batch)
+
+
+def _scan_long_queries(queries, profiles, pipeline_for: Callable, callback: Optional[Callable], batch: int) -> Iterator[TopHits]:
+    """nhmmscan's loop, for `nhmmscan` and `LongTargetsPipeline.scan_seq`: ``pipeline_for(alphabet)`` gives the pipeline of
+    the scan once the first query's alphabet is known."""
+    from .easel import DigitalSequence
+    from .errors import AlphabetMismatch, DeviceUnavailable
+    from .plan7 import LongTargetLibrary
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    if isinstance(queries, DigitalSequence):
+        queries = (queries,)
+    if isinstance(profiles, (HMM, Profile, OptimizedProfile)):
+        profiles = (profiles,)
+    if isinstance(queries, SequenceFile) and not queries.digital:
+        raise ValueError("query sequences file is not in digital mode")
+    total = None
+    try:
+        total = len(queries)          # type: ignore[arg-type]
+    except TypeError:
+        pass
+
+    def sequences():
+        if isinstance(queries, SequenceFile):
+            while True:
+                seq = queries.read()
+                if seq is None:
+                    return
+                yield seq
+        else:
+            yield from queries
+
+    library: List[LongTargetLibrary] = []       # the batches of the library, prepared while the first query walks through them
+    source = None
+    pipeline = None
+    for query in sequences():
+        if not isinstance(query, DigitalSequence):
+            raise TypeError(f"Expected DigitalSequence, found {type(query).__name__}")
+        if pipeline is None:
+            pipeline = pipeline_for(query.alphabet)
+        if query.alphabet != pipeline.alphabet:
+            raise AlphabetMismatch(pipeline.alphabet, query.alphabet)
+        if source is None:
+            source = _batches(profiles, batch)
+
+        def batches():
+            yield from library
+            for models in source:                   # exhausted after the first query
+                library.append(LongTargetLibrary(pipeline, models))
+                yield library[-1]
+
+        token = next(_SCAN_TOKENS)                  # the query's device copy is kept while its batches run (one upload)
+        handle = None
+        try:
+            for lib in batches():
+                if _lib.lib().p7x_device_count() < 1:
+                    raise DeviceUnavailable("nhmmscan: no HIP device is usable and there is no CPU fallback")
+                if len(query) == 0:                 # nothing to scan: the list stays empty, the library's size is counted at the end
+                    continue
+                per_model = pipeline._scan_batch(query, lib, resident_key=token)
+                handle = pipeline._scan_collect(query, per_model, 0, handle)
+                del per_model
+            # the library's size is known now, also to a query that no batch scanned
+            handle = pipeline._scan_collect(query, None, sum(len(lib) for lib in library) or -1, handle)
+        except BaseException:
+            if handle is not None and handle.value:
+                _lib.lib().p7x_tophits_destroy(handle)
+            raise
+        finally:
+            _lib.lib().p7x_longtargets_release_resident(pipeline.device, token)
+        hits = TopHits(query, handle)
+        hits._library = library                     # the alignments refer to the profiles: keep them alive with the hits
+        if callback is not None:
+            callback(query, total)
+        yield hits
+
+
+_SCAN_TOKENS = itertools.count(1 << 40)         # residency keys of nhmmscan's queries, apart from plan7's (cfg.lt_resident_key)
 
 
 def hmmalign(hmm, sequences, *, cpus: int = 0, digitize: bool = False, trim: bool = False, all_consensus_cols: bool = True,

@@ -30,7 +30,7 @@ from .errors import (AlphabetMismatch, AllocationError, InvalidParameter, Missin
 
 __all__ = [
     "HMM", "HMMFile", "HMMPressedFile", "Background", "Profile", "OptimizedProfile", "OptimizedProfileBlock", "EvalueParameters", "Cutoffs",
-    "Builder", "Pipeline", "LongTargetsPipeline", "SequenceDatabase", "TopHits", "Hit", "Domain", "Domains", "Alignment",
+    "Builder", "Pipeline", "LongTargetsPipeline", "LongTargetLibrary", "SequenceDatabase", "TopHits", "Hit", "Domain", "Domains", "Alignment",
     "Trace", "Traces", "TraceAligner", "IterationResult", "IterativeSearch",
 ]
 
@@ -1945,6 +1945,9 @@ class TopHits:
         if format == "pfam":
             fh.write(self._xfam().encode())
             return
+        if format == "targets" and self.long_targets and self.mode == "scan":
+            fh.write(self._nhmmscan_table(header).encode())
+            return
         q = self.query
         qname = getattr(q, "name", None) if q is not None and not isinstance(q, str) else q
         qacc = getattr(q, "accession", None) if q is not None and not isinstance(q, str) else None
@@ -2006,6 +2009,35 @@ class TopHits:
                         math.exp(d.lnP) * Z, d.bitscore, d.dombias / math.log(2.0), d.hmmfrom, d.hmmto, d.sqfrom, d.sqto,
                         d.ienv, d.jenv, d.oasc / (1.0 + abs(float(d.jenv - d.ienv))), h.description or "-"))
         fh.write(("\n".join(out) + "\n").encode() if out else b"")
+
+    def _nhmmscan_table(self, header: bool) -> str:
+        """nhmmer's ``--tblout`` layout (the header of ``tests/golden/tables/bmyD1.tbl``) with the roles exchanged, as
+        upstream's nhmmscan writes it: the model in the target columns, the sequence in the query columns, and the model's
+        length in the length column under the heading ``modlen``.  No fixture pins nhmmscan's bytes: the rows are checked
+        against the hit objects."""
+        q = self.query
+        qname = (getattr(q, "name", None) if q is not None and not isinstance(q, str) else q) or "-"
+        qacc = (getattr(q, "accession", None) if q is not None and not isinstance(q, str) else None) or "-"
+        hits = [h for h in self if h.reported]
+        tnamew = max([20] + [len(h.name) for h in hits])
+        taccw = max([10] + [len(h.accession or "") for h in hits])
+        qnamew, qaccw = max(20, len(qname)), max(10, len(qacc))
+        out = []
+        if header:
+            out.append("#%-*s %-*s %-*s %-*s %s %s %s %s %s %s %s %s %9s %6s %5s  %s" % (
+                tnamew - 1, " target name", taccw, "accession", qnamew, "query name", qaccw, "accession", "hmmfrom", "hmm to",
+                "alifrom", " ali to", "envfrom", " env to", " modlen", "strand", "  E-value", " score", " bias", "description of target"))
+            out.append("#%*s %*s %*s %*s %s %s %s %s %s %s %s %s %9s %6s %5s %s" % (
+                tnamew - 1, "-------------------", taccw, "----------", qnamew, "--------------------", qaccw, "----------",
+                "-------", "-------", "-------", "-------", "-------", "-------", "-------", "------", "---------", "------", "-----",
+                "---------------------"))
+        for h in hits:
+            r, d = h._rec, h.best_domain._rec
+            out.append("%-*s %-*s %-*s %-*s %7d %7d %7d %7d %7d %7d %7d %6s %9.2g %6.1f %5.1f  %s" % (
+                tnamew, h.name, taccw, h.accession or "-", qnamew, qname, qaccw, qacc, d.hmmfrom, d.hmmto, d.iali, d.jali,
+                d.ienv, d.jenv, d.M, "   +  " if d.iali < d.jali else "   -  ", math.exp(r.lnP), r.score, d.dombias / math.log(2.0),
+                h.description or "-"))
+        return "\n".join(out) + "\n" if out else ""
 
     def _xfam(self) -> str:
         q = self.query
@@ -3028,8 +3060,114 @@ class LongTargetsPipeline(Pipeline):
         hits._om = om
         return hits
 
+    # -- the scan orientation: one sequence against a library of models (``nhmmscan``).  An extension: the reference's
+    #    ``LongTargetsPipeline.scan_seq`` raises.
+    def _scan_model(self, model):
+        """The optimized profile a library model is scanned with and the window length its E-values refer to (0: the
+        scan's), as `search_hmm` settles them for a query (`_windowed_om`); host code, no device."""
+        if not isinstance(model, (HMM, Profile, OptimizedProfile)):
+            raise TypeError(f"Expected HMM, Profile or OptimizedProfile, found {type(model).__name__}")
+        # a library may hold DNA and RNA models side by side (Dfam next to Rfam): the two alphabets share their residue codes
+        if not model.alphabet.is_nucleotide():
+            raise AlphabetMismatch(self.alphabet, model.alphabet)
+        if isinstance(model, (Profile, OptimizedProfile)) and self.window_length is None:
+            window = getattr(model, "max_length", None)
+            if window is None and isinstance(model, OptimizedProfile):
+                window = model._info.max_length         # what the profile was built with (a pressed library's MAXL)
+            if (window or -1) <= 0:
+                raise TypeError("Cannot use `Profile` or `OptimizedProfile` query without `max_length` set")     # plan7.pyx:7354
+        limit = _lib.lib().p7x_max_model_length()
+        if model.M > limit:
+            raise ValueError(f"nhmmscan: model {model.name!r} has {model.M} nodes: model too long for the device kernels (at most {limit})")
+        cfg = self._cfg()
+        om = self._windowed_om(model, self.L_HINT, cfg)
+        if self.bit_cutoffs is not None and not getattr(om.cutoffs, self.bit_cutoffs + "_available")():
+            raise MissingCutoffs(om.name, self.bit_cutoffs)
+        return om, max(0, int(cfg.evalue_window_length))
 
-_RESIDENT_TOKENS = itertools.count(1)          # one per packed image whose device copy may be kept (cfg.lt_resident_key)
+    def _scan_batch(self, query, library: "LongTargetLibrary", resident_key: int = 0) -> "HitHandles":
+        """`query` against the models of one library batch (``p7x_scan_longtargets``): the per-model hit lists."""
+        n = len(library)
+        cfg = self._cfg()
+        L = len(query)
+        dsq = np.full(L + 2, 255, dtype=np.uint8)
+        dsq[1:L + 1] = query.sequence
+        out = (C.c_void_p * max(n, 1))()
+        st = _lib.lib().p7x_scan_longtargets(C.byref(cfg), library._oms, n, self.device, dsq.ctypes.data, L, query.name.encode(),
+                                             (query.accession or "").encode(), (query.description or "").encode(), library._ewin,
+                                             library._device_tables(self.device), resident_key, out)
+        if st != 0:
+            raise status_to_exception(st, "p7x_scan_longtargets", _lib.last_error())
+        return HitHandles(out, n)
+
+    def _scan_collect(self, query, per_model: Optional["HitHandles"], total: int, handle=None):
+        """Folds per-model lists into the scan list of `query` (``p7x_scan_collect_longtargets``); ``total`` = 0: more follow,
+        -1: finish with the models collected.  Returns the list's handle."""
+        cfg = self._cfg()
+        inout = C.c_void_p(handle.value if handle is not None else None)
+        st = _lib.lib().p7x_scan_collect_longtargets(per_model.array if per_model is not None else None, None,
+                                                     len(per_model) if per_model is not None else 0, total, C.byref(cfg), query.name.encode(),
+                                                     (query.accession or "").encode(), (query.description or "").encode(), len(query), C.byref(inout))
+        if st != 0:
+            raise status_to_exception(st, "p7x_scan_collect_longtargets", _lib.last_error())
+        return inout
+
+    def scan_seq(self, query: DigitalSequence, optimized_profiles) -> "TopHits":
+        """``nhmmscan``: one nucleotide sequence against a collection of nucleotide models -- an `OptimizedProfileBlock`, a
+        list of `HMM` / `Profile` / `OptimizedProfile`, an `HMMFile` ... -- with the SSV scan of all models batched on the
+        device.  The hits are the models (``hits.mode == "scan"``); a model's hits are those of its own `search_hmm` against
+        the sequence with E-values times the number of models.  See :func:`pyhmmer_amd.hmmer.nhmmscan`."""
+        from .hmmer import _scan_long_queries
+        if not isinstance(query, DigitalSequence):
+            raise TypeError(f"Expected DigitalSequence, found {type(query).__name__}")
+        if query.alphabet != self.alphabet:
+            raise AlphabetMismatch(self.alphabet, query.alphabet)
+        for hits in _scan_long_queries(query, optimized_profiles, lambda alphabet: self, None, 128):
+            return hits
+
+
+class LongTargetLibrary:
+    """A batch of nucleotide models ready for `LongTargetsPipeline` scans: the optimized profiles, built once, and -- from
+    the first scan on -- the device copy of their SSV tables (``p7x_lt_library``), which every query sequence reuses."""
+
+    def __init__(self, pipeline: "LongTargetsPipeline", models):
+        self.models = list(models)
+        prepared = [pipeline._scan_model(m) for m in self.models]
+        self.profiles = [om for om, _ in prepared]
+        n = len(self.profiles)
+        self._oms = (C.c_void_p * max(n, 1))(*[om._handle for om in self.profiles])
+        self._ewin = (C.c_int32 * max(n, 1))(*[w for _, w in prepared])
+        self._tables = None
+        self._device = None
+
+    def __len__(self) -> int:
+        return len(self.profiles)
+
+    def _device_tables(self, device: int):
+        if len(self.profiles) == 0:
+            return None
+        if self._tables is None or self._device != device:
+            self._release()
+            out = C.c_void_p()
+            st = _lib.lib().p7x_lt_library_create(self._oms, len(self.profiles), device, C.byref(out))
+            if st != 0:
+                raise status_to_exception(st, "p7x_lt_library_create", _lib.last_error())
+            self._tables, self._device = out, device
+        return self._tables
+
+    def _release(self) -> None:
+        tables, self._tables = getattr(self, "_tables", None), None
+        if tables:
+            try:
+                _lib.lib().p7x_lt_library_destroy(tables)
+            except Exception:                       # noqa: BLE001 - interpreter shutdown
+                pass
+
+    def __del__(self):
+        self._release()
+
+
+_RESIDENT_TOKENS = itertools.count(1)         # one per packed image whose device copy may be kept (cfg.lt_resident_key)
 _RESIDENT_LOCK = threading.Lock()
 
 
