@@ -856,6 +856,31 @@ int64_t p7x_orfs_info(const p7x_orfs *b, int which);
 int     p7x_orfs_copy(const p7x_orfs *b, uint8_t *dsq, int64_t *offsets, int32_t *lengths, int64_t *source, int8_t *frame, int64_t *start, int64_t *end);
 void    p7x_orfs_destroy(p7x_orfs *b);
 
+/* ------------------------------------------------------------------ decoy sequences: p7x_shuffle.cpp, p7x_shuffle.hip
+ * DigitalSequenceBlock.shuffle (an extension; definitions: DESIGN.md 3.19): every sequence of a block packed as
+ * p7x_seqdb_create takes it (255 x1..xL 255 ..., nbytes = residues + n + 1) shuffled on <device>, one lane per sequence, into
+ * out_dsq[nbytes] in the same packing -- the offsets and lengths of the input hold for the output.  mode: P7X_SHUFFLE_MONO a
+ * uniform permutation, _DI a uniform draw among the sequences with the same first residue, last residue and adjacent-pair
+ * counts (sequences of fewer than three residues stay), _WINDOW a permutation within consecutive windows of <window>
+ * residues, _REVERSE the sequence backwards.  Every digital code is a symbol; abc_type only bounds the codes of _DI.  The
+ * draws are Philox-4x32-10 blocks keyed by <seed> with the counter (sequence index, attempt, step): sequence i depends on
+ * nothing but itself, its index, the mode, the window and the seed.  p7x_shuffle_host is the twin: same procedure, the same
+ * bytes; debug option "host_shuffle" = 1 makes p7x_shuffle_block call it.  A workgroup shuffles a run of consecutive
+ * sequences whose span fits "shuffle_slab" (debug option; a multiple of 64 from 64 up, default 65,536; _DI: half of it) bytes
+ * of LDS; a sequence that alone does not fit takes a second launch (the long path).  p7x_shuffle_plan gives the runs, the
+ * long sequences and the slab in force for lengths[n] (offsets may be NULL).  The output does not depend on the slab.
+ * P7X_ENODEVICE without a device (and without the seam); P7X_EINVAL for a block that is not packed as it says, an unknown
+ * mode, window < 0, window = 0 with _WINDOW, a code outside the alphabet with _DI; P7X_EMEM when input and output do not
+ * fit the device's free memory.
+ * stats[5] (may be NULL): nanoseconds of the kernels (device events; wall clock for the twin), nanoseconds of the upload,
+ * runs, long sequences, 1 when shuffled on the device. */
+enum { P7X_SHUFFLE_MONO = 0, P7X_SHUFFLE_DI = 1, P7X_SHUFFLE_WINDOW = 2, P7X_SHUFFLE_REVERSE = 3 };
+int p7x_shuffle_block(int32_t abc_type, int device, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, size_t n, int64_t nbytes,
+                      int mode, int32_t window, uint32_t seed, uint8_t *out_dsq, int64_t *stats);
+int p7x_shuffle_host(int32_t abc_type, const uint8_t *dsq, const int64_t *offsets, const int32_t *lengths, size_t n, int64_t nbytes, int mode,
+                     int32_t window, uint32_t seed, int threads, uint8_t *out_dsq, int64_t *stats);
+int p7x_shuffle_plan(const int64_t *offsets, const int32_t *lengths, size_t n, int mode, int64_t *runs, int64_t *long_sequences, int32_t *slab);
+
 /* ------------------------------------------------------------------ Builder.build_msa: p7x_msabuild.cpp, p7x_msabuild.hip
  * A protein alignment as a query (hmmbuild).  ax[N * L]: the digital codes of the rows, one after the other (gap 20).
  * p7x_msa_checksum: Jenkins' one-at-a-time hash over them, the CKSUM of the model.

@@ -19,7 +19,7 @@ LIB_PATH = _PKG / "libp7x.so"
 
 SOURCES = ["p7x_profile.cpp", "p7x_device.hip", "p7x_devmem.hip", "p7x_devimage.hip", "p7x_msv.hip", "p7x_vitfwd.hip", "p7x_vitpk.hip", "p7x_fwdpk.hip", "p7x_envelope.hip", "p7x_ensemble.hip", "p7x_ssvlong.hip", "p7x_longtarget.hip",
            "p7x_envscore.hip", "p7x_pipeline.hip", "p7x_domaindef.cpp", "p7x_logdp.cpp", "p7x_alignlog.hip", "p7x_longtarget_host.cpp", "p7x_tophits.cpp", "p7x_align.hip", "p7x_tracealign.cpp", "p7x_builder.cpp", "p7x_calibrate.hip",
-           "p7x_emit.cpp", "p7x_emit.hip", "p7x_msabuild.cpp", "p7x_msabuild.hip", "p7x_msapair.cpp", "p7x_msapair.hip", "p7x_translate.cpp", "p7x_translate.hip"]
+           "p7x_emit.cpp", "p7x_emit.hip", "p7x_msabuild.cpp", "p7x_msabuild.hip", "p7x_msapair.cpp", "p7x_msapair.hip", "p7x_translate.cpp", "p7x_translate.hip", "p7x_shuffle.cpp", "p7x_shuffle.hip"]
 
 
 def _hipcc() -> str:
@@ -352,6 +352,9 @@ _SIGNATURES = {
     "p7x_orfs_info": (C.c_int64, [_VP, C.c_int]),
     "p7x_orfs_copy": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "p7x_orfs_destroy": (None, [_VP]),
+    "p7x_shuffle_block": (C.c_int, [C.c_int32, C.c_int, _VP, _VP, _VP, C.c_size_t, C.c_int64, C.c_int, C.c_int32, C.c_uint32, _VP, _VP]),
+    "p7x_shuffle_host": (C.c_int, [C.c_int32, _VP, _VP, _VP, C.c_size_t, C.c_int64, C.c_int, C.c_int32, C.c_uint32, C.c_int, _VP, _VP]),
+    "p7x_shuffle_plan": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "p7x_last_error": (C.c_char_p, []),
 }
 

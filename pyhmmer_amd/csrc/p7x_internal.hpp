@@ -114,7 +114,7 @@ void set_error(const std::string &msg);
 // Test / diagnostic seam (p7x_debug_set_option, include/p7x.h): process-wide knobs that pick a kernel family for a parity test, bound
 // a workspace, or switch a trace on.  -1 = not set (the library decides).  The library reads no environment variables.
 enum { OPT_SMALL_BLOCK = 0, OPT_VIT_WAVE, OPT_MSV_EXACT, OPT_MSV_LONG_GROUPS, OPT_MSV_BLOCKS_PER_CU, OPT_ENV_WORKSPACE_GB, OPT_DEVICE_CLUSTERED,
-       OPT_TRACE_FINISH, OPT_TRACE_LONGTARGET, OPT_TRACE_ENVELOPE, OPT_HOST_PROFILE, OPT_SSV_KERNEL, OPT_MSV_F16, OPT_ENS_LDS_KB, OPT_ENS_FAIL, OPT_MSV_TIERS, OPT_STAGE_MERGE, OPT_EARLY_PACK, OPT_HOST_ORDER, OPT_VIT_LONG_CUT, OPT_FWD_GROUPED, OPT_REGION_GUARD_PPM, OPT_MSV_K8, OPT_MSV_LANE_BLOCKS, OPT_HOST_ALIGN, OPT_ALIGN_WORKSPACE_GB, OPT_CASCADE_STREAMS, OPT_CASCADE_SPLIT, OPT_SSV_PARTS, OPT_ALIGN_LOGSPACE, OPT_VIT_WIDE, OPT_HOST_EMIT, OPT_EMIT_CAP, OPT_EMIT_LDS, OPT_HOST_BUILD, OPT_BUILD_ROWS, OPT_HOST_PAIRID, OPT_PAIRID_TILE, OPT_MSA_CODES, OPT_HOST_TRANSLATE, OPT_ORF_CHUNK, OPT_ENV_BLOCKS, OPT_SSV_SCAN_CHUNK, OPT_COUNT };
+       OPT_TRACE_FINISH, OPT_TRACE_LONGTARGET, OPT_TRACE_ENVELOPE, OPT_HOST_PROFILE, OPT_SSV_KERNEL, OPT_MSV_F16, OPT_ENS_LDS_KB, OPT_ENS_FAIL, OPT_MSV_TIERS, OPT_STAGE_MERGE, OPT_EARLY_PACK, OPT_HOST_ORDER, OPT_VIT_LONG_CUT, OPT_FWD_GROUPED, OPT_REGION_GUARD_PPM, OPT_MSV_K8, OPT_MSV_LANE_BLOCKS, OPT_HOST_ALIGN, OPT_ALIGN_WORKSPACE_GB, OPT_CASCADE_STREAMS, OPT_CASCADE_SPLIT, OPT_SSV_PARTS, OPT_ALIGN_LOGSPACE, OPT_VIT_WIDE, OPT_HOST_EMIT, OPT_EMIT_CAP, OPT_EMIT_LDS, OPT_HOST_BUILD, OPT_BUILD_ROWS, OPT_HOST_PAIRID, OPT_PAIRID_TILE, OPT_MSA_CODES, OPT_HOST_TRANSLATE, OPT_ORF_CHUNK, OPT_ENV_BLOCKS, OPT_SSV_SCAN_CHUNK, OPT_HOST_SHUFFLE, OPT_SHUFFLE_SLAB, OPT_COUNT };
 int debug_opt(int which);
 
 }

@@ -22,7 +22,7 @@ import numpy as np
 
 __all__ = [
     "Alphabet", "GeneticCode", "Sequence", "TextSequence", "DigitalSequence",
-    "TextSequenceBlock", "DigitalSequenceBlock", "TranslatedBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness", "KeyHash",
+    "TextSequenceBlock", "DigitalSequenceBlock", "TranslatedBlock", "ShuffledBlock", "SequenceFile", "MSA", "TextMSA", "DigitalMSA", "MSAFile", "Randomness", "KeyHash",
 ]
 
 _AMINO = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -32,6 +32,7 @@ _RNA = "ACGU-RYMKSWHBVDN*~"
 eslRNA, eslDNA, eslAMINO = 1, 2, 3   # libeasel/alphabet.pxd type codes
 DSQ_SENTINEL = 255                   # libeasel/__init__.pxd:21 (eslDSQ_SENTINEL)
 _MSA_WEIGHT_PREFERENCES = ("conscover", "origorder", "random")      # easel.pyx:175-179
+_SHUFFLE_MODES = ("mono", "di", "window", "reverse")                # P7X_SHUFFLE_*: the index is the mode of the C-ABI
 
 
 class Alphabet:
@@ -298,6 +299,14 @@ class DigitalSequence(Sequence):
         return DigitalSequence(genetic_code.amino_alphabet, self.name, self.description, self.accession,
                                genetic_code.translate(self.sequence), self.source)
 
+    def shuffle(self, seed: int = 42, mode: str = "mono", window: int = 0) -> "DigitalSequence":
+        """A decoy of this sequence (an extension), shuffled on the host: what sequence 0 of
+        ``DigitalSequenceBlock(alphabet, [self]).shuffle(seed, mode, window)`` is."""
+        mode_code = _check_shuffle_arguments(seed, mode, window)
+        pk = PackedBlock([self])
+        dsq, _ = _shuffle_packed(self.alphabet, pk, mode_code, int(window), int(seed), host=True, threads=1)
+        return DigitalSequence(self.alphabet, f"{self.name}-shuffled", self.description, self.accession, dsq[1:1 + len(self)], self.source)
+
     def reverse_complement(self, inplace: bool = False) -> Optional["DigitalSequence"]:
         """The reverse complement (reference ``easel.pyx:8070-8110``); `ValueError` for an alphabet without complements."""
         if not self.alphabet.is_nucleotide():
@@ -341,6 +350,37 @@ class PackedBlock:
         self.dsq, self.offsets, self.lengths = dsq, offsets, lengths
         self.n, self.total_residues = int(lengths.shape[0]), int(lengths.sum(dtype=np.int64))
         return self
+
+
+def _check_shuffle_arguments(seed, mode, window) -> int:
+    """The argument checks of both ``shuffle`` methods; returns the mode of the C-ABI."""
+    from .errors import InvalidParameter
+    if mode not in _SHUFFLE_MODES:
+        raise InvalidParameter("mode", mode, choices=list(_SHUFFLE_MODES))
+    if int(window) < 0:
+        raise InvalidParameter("window", window, hint="a number of residues, 0 or more")
+    if mode == "window" and int(window) == 0:
+        raise InvalidParameter("window", window, hint="mode 'window' needs a window of at least one residue")
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise InvalidParameter("seed", seed, hint="an integer from 0 to 2**32 - 1")
+    return _SHUFFLE_MODES.index(mode)
+
+
+def _shuffle_packed(alphabet: "Alphabet", pk: "PackedBlock", mode_code: int, window: int, seed: int, *, host: bool, device: int = 0,
+                    threads: int = 0):
+    """``p7x_shuffle_block`` / ``p7x_shuffle_host`` over a packed block: the shuffled ``dsq`` and the five statistics."""
+    from . import _lib
+    from .errors import status_to_exception
+    dsq = np.empty(pk.dsq.shape[0], dtype=np.uint8)
+    stats = np.zeros(5, dtype=np.int64)
+    common = (pk.dsq.ctypes.data, pk.offsets.ctypes.data, pk.lengths.ctypes.data, pk.n, int(pk.dsq.shape[0]), mode_code, window, seed)
+    if host:
+        st, fn = _lib.lib().p7x_shuffle_host(alphabet.type_code, *common, int(threads), dsq.ctypes.data, stats.ctypes.data), "p7x_shuffle_host"
+    else:
+        st, fn = _lib.lib().p7x_shuffle_block(alphabet.type_code, int(device), *common, dsq.ctypes.data, stats.ctypes.data), "p7x_shuffle_block"
+    if st != 0:
+        raise status_to_exception(st, fn, _lib.last_error())
+    return dsq, stats
 
 
 class _SequenceBlock:
@@ -514,6 +554,19 @@ class DigitalSequenceBlock(_SequenceBlock):
         finally:
             _lib.lib().p7x_orfs_destroy(h)
 
+    def shuffle(self, seed: int = 42, mode: str = "mono", window: int = 0, device: int = 0) -> "ShuffledBlock":
+        """A decoy of every sequence (an extension): the same lengths and the same residues with the
+        homology destroyed, the whole block at once on ``device`` (``p7x_shuffle.hip``; test seam ``host_shuffle``: the host
+        twin, the same bytes).  ``mode``: ``"mono"`` a uniform permutation; ``"di"`` a uniform draw among the sequences
+        with the same first residue, last residue and count of every adjacent pair (Altschul & Erickson 1985; fewer than
+        three residues stay as they are); ``"window"`` a permutation within consecutive windows of ``window`` residues;
+        ``"reverse"`` the sequence backwards.  Every digital code is a symbol like any other.  Decoy ``i`` depends on
+        sequence ``i``, its index and ``seed`` (0 to 2**32 - 1; 0 is a seed like any other) only, so ``block[:k].shuffle(...)``
+        gives the first ``k`` decoys of ``block.shuffle(...)``."""
+        mode_code = _check_shuffle_arguments(seed, mode, window)
+        dsq, stats = _shuffle_packed(self.alphabet, self.packed(), mode_code, int(window), int(seed), host=False, device=device)
+        return ShuffledBlock(self, dsq, stats, mode, int(seed), int(window))
+
 
 class _LazyDigitalSequenceBlock(DigitalSequenceBlock):
     """A block that exists only as the packed arrays the native FASTA parser produced (``p7x_fasta_parse``): a
@@ -570,6 +623,17 @@ class _LazyDigitalSequenceBlock(DigitalSequenceBlock):
 
     def packed(self) -> PackedBlock:
         return self._pk if self._list is None else super().packed()
+
+
+def _string_table_of(names, descs):
+    """Names and descriptions (bytes, one of each per sequence) as the NUL-terminated string table of a packed-only block and
+    the offsets of the names and of the descriptions into it."""
+    n = len(names)
+    sizes = np.fromiter((len(b) + 1 for pair in zip(names, descs) for b in pair), dtype=np.int64, count=2 * n)
+    at = np.zeros(2 * n + 1, dtype=np.int64)
+    np.cumsum(sizes, out=at[1:])
+    strtab = np.frombuffer(b"".join(b + b"\0" for pair in zip(names, descs) for b in pair) + b"\0", dtype=np.uint8)
+    return strtab, at[0:2 * n:2].copy(), at[1:2 * n:2].copy()
 
 
 class TranslatedBlock(_LazyDigitalSequenceBlock):
@@ -630,11 +694,7 @@ class TranslatedBlock(_LazyDigitalSequenceBlock):
             descs = [f"source={src[k]} coords={a}..{b} length={L} frame={f}".encode()
                      for k, a, b, L, f in zip(self.source_index.tolist(), self.start.tolist(), self.end.tolist(),
                                               self._pk.lengths.tolist(), self.frame.tolist())]
-            sizes = np.fromiter((len(b) + 1 for pair in zip(names, descs) for b in pair), dtype=np.int64, count=2 * n)
-            at = np.zeros(2 * n + 1, dtype=np.int64)
-            np.cumsum(sizes, out=at[1:])
-            strtab = np.frombuffer(b"".join(b + b"\0" for pair in zip(names, descs) for b in pair) + b"\0", dtype=np.uint8)
-            self._tables = (strtab, at[0:2 * n:2].copy(), at[1:2 * n:2].copy())
+            self._tables = _string_table_of(names, descs)
         return self._tables
 
     _strtab = property(lambda self: self._string_tables()[0])
@@ -658,6 +718,57 @@ class TranslatedBlock(_LazyDigitalSequenceBlock):
             nt = (start - 3 * (i - 1), start - 3 * j + 1)
         k = int(self.source_index[t])
         return (self.source_block[k].name, k, nt[0], nt[1], frame)
+
+
+def _block_strings(block: DigitalSequenceBlock):
+    """The names and descriptions (bytes) of a block, without making the sequences of one that is kept packed."""
+    if getattr(block, "_list", 0) is None:
+        buf = block._strtab.tobytes()
+        cut = lambda offs: [buf[o:buf.index(b"\0", o)] for o in offs.tolist()]
+        return cut(block._name_off), cut(block._desc_off)
+    return [s.name.encode() for s in block], [(s.description or "").encode() for s in block]
+
+
+class ShuffledBlock(_LazyDigitalSequenceBlock):
+    """What `DigitalSequenceBlock.shuffle` returns: the decoys of ``source_block``, kept as packed arrays with the offsets and
+    lengths of the source's packed block.  Decoy ``i`` is the `DigitalSequence` ``{source name}-shuffled`` with the source's
+    description, accession and source, made on demand; the name and description tables a search reads are built when
+    first asked for.  ``mode``, ``seed`` and ``window`` are the arguments; ``on_device`` tells whether the kernels made the
+    block (or the host twin), ``kernel_us`` their time from device events, ``long_sequences`` how many sequences were too long
+    for a workgroup's slab and took the second launch, ``runs`` the workgroups of the first."""
+
+    __slots__ = ("source_block", "mode", "seed", "window", "on_device", "kernel_us", "upload_us", "runs", "long_sequences", "_tables")
+
+    def __init__(self, source: DigitalSequenceBlock, dsq: np.ndarray, stats, mode: str, seed: int, window: int):
+        pk = source.packed()
+        self.source_block, self.mode, self.seed, self.window = source, mode, seed, window
+        self.kernel_us, self.upload_us = int(stats[0]) // 1000, int(stats[1]) // 1000
+        self.runs, self.long_sequences, self.on_device = int(stats[2]), int(stats[3]), bool(stats[4])
+        self._tables = None
+        self._list = None
+        self._pk = PackedBlock.from_arrays(dsq, pk.offsets, pk.lengths)
+        self.alphabet = source.alphabet
+        self._packed = self._pk
+        self._version = 0
+
+    def _make(self, t: int) -> DigitalSequence:
+        src = self.source_block[t]
+        o, L = int(self._pk.offsets[t]), int(self._pk.lengths[t])
+        return DigitalSequence(self.alphabet, name=f"{src.name}-shuffled", description=src.description, accession=src.accession,
+                               sequence=self._pk.dsq[o:o + L], source=src.source)
+
+    def _string_tables(self):
+        """The NUL-terminated string table of names and descriptions and the offsets into it, as the native FASTA parser
+        lays them out (`SequenceDatabase` hands pointers into it to the library)."""
+        if self._tables is None:
+            names, descs = _block_strings(self.source_block)
+            names = [b + b"-shuffled" for b in names]
+            self._tables = _string_table_of(names, descs)
+        return self._tables
+
+    _strtab = property(lambda self: self._string_tables()[0])
+    _name_off = property(lambda self: self._string_tables()[1])
+    _desc_off = property(lambda self: self._string_tables()[2])
 
 
 class SequenceFile:
